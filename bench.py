@@ -2,8 +2,13 @@
 """bench.py -- car-steps/s of the 24-hour resample (src/resampling.jl + the saveresults
 histogram) on N MI355X, with the HBM roofline of the path and the CPU restatement timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times EXACTLY K steps and prints the headline line (its roofline comes from event pairs carried
+by launches inside those steps).  `--full` adds everything else listed below.  `--dump-outputs DIR` writes the count tensor of
+the last timed step (what a caller of the path receives) as DIR/parking.npy, DIR/driving.npy (Z x T) and DIR/sum_tt_q16.npy,
+float64; the inputs are fixed by the seeds, so two builds can be compared output for output.
 
 One "step" = one full T=24 hour resample of every car (tables, CDF and the post-IVP initial
 state already resident in HBM), through the zone x hour count tensor -- and, for N > 1, through
@@ -19,11 +24,11 @@ roofline: B = algorithmic HBM bytes of one hourly launch = rows +
 kernel (the hourly sampler launch: B over its hipEvent duration); `whole_resample` is 8(d)'s own figure, T*B over the wall
 time of a step; `kernels` lists every hourly kernel of the step with its own bytes, duration and measured traffic.
 
-Records outside the headline (N = 1 only, each a few seconds): `table_build` (the one pass from p_destin to the samplers' row
+Records outside the headline (`--full` only; N = 1 only, each a few seconds): `table_build` (the one pass from p_destin to the samplers' row
 tables), `per_dataset` (main.jl:79-95 at Melbourne's shape: createpdrive + createpdestin + IVP + resample with travel times),
 `skewed` (the headline workload on peaky destination tables), `two_resamples_in_flight`, `full_pipeline`, `cpu_baseline`.
 `--zones 2357 --cars-per-zone 100 --melbourne` is BASELINE.json configs[0]'s shape (the reference's own CPU-runnable case):
-its cpu_baseline times the faithful restatement on the Melbourne-shaped sparse tables.
+its cpu_baseline (with `--full`) times the faithful restatement on the Melbourne-shaped sparse tables.
 """
 import argparse
 import json
@@ -229,38 +234,30 @@ class Job:
         self.kernel_used = kernel_used
         return kernel_used
 
-    def timed(self, steps, min_window_s=0.0):
-        """wall time of a block of EXACTLY `steps` steps bracketed by barrier + synchronize on both sides, MAX over ranks; the block
-        is repeated until the blocks add up to min_window_s (every rank takes the same number of blocks: the decision is rank 0's,
-        broadcast): returns (median block, every block, the last count tensor)"""
+    def timed(self, steps):
+        """wall time of EXACTLY `steps` steps bracketed by barrier + synchronize on both sides, MAX over ranks:
+        returns (seconds, the last count tensor)"""
         import torch
         import torch.distributed as dist
         env = self.env
-        blocks = []
-        counts = None
-        while True:
-            env.barrier()
-            t0 = time.perf_counter()
-            counts = self.run_steps(steps)
-            env.barrier()
-            dt = time.perf_counter() - t0
+        env.barrier()
+        t0 = time.perf_counter()
+        counts = self.run_steps(steps)
+        env.barrier()
+        dt = time.perf_counter() - t0
+        if env.world > 1:
             tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if env.rehearse else "cuda")
-            if env.world > 1:
-                dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-            blocks.append(float(tmax.item()))
-            go = torch.tensor([1 if (sum(blocks) < min_window_s and len(blocks) < 200) else 0], device="cpu" if env.rehearse else "cuda")
-            if env.world > 1:
-                dist.broadcast(go, 0)
-            if int(go.item()) == 0:
-                break
-        return statistics.median(blocks), blocks, counts
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            dt = float(tmax.item())
+        return dt, counts
 
     def check(self, counts):
+        """the count tensor on the host: (parking (Z, T), driving (Z, T), sum_tt_q16)"""
         import carparkingmaps_amd as cpm
-        parking, driving, _ = cpm.distributed.split_counts(counts, self.Z, T)
+        parking, driving, sum_tt_q16 = cpm.distributed.split_counts(counts, self.Z, T)
         if os.environ.get("CPM_BENCH_NOCHECK") != "1":   # (timing-only ablation builds of tools/build_variants.sh produce invalid counts)
             assert (parking.sum(axis=0) == self.C).all(), "every hour must hold all C cars"
-        return parking, driving
+        return parking, driving, sum_tt_q16
 
     def close(self):
         self.ss.close()
@@ -274,8 +271,8 @@ def side_record(env, Z, cpz_total, steps, what, **kw):
     """a secondary workload measured like the headline (settle, then `steps` timed steps): ms per resample and car-steps/s"""
     job = Job(env, Z, cpz_total, **kw)
     job.settle(3)
-    dt, _, counts = job.timed(steps)
-    parking, _ = job.check(counts)
+    dt, counts = job.timed(steps)
+    parking, _, _ = job.check(counts)
     ms = dt / steps * 1e3
     rec = {"what": what, "zones": Z, "cars": job.C, "cars_per_gpu": job.count, "steps": steps, "ms_per_step": ms,
            "value": job.C * T * steps / dt, "unit": "car-steps/s", "bucket_region_x_mean": job.s.get_info(2),
@@ -437,6 +434,15 @@ def melbourne_record(env):
     return out
 
 
+def dump_outputs(path, parking, driving, sum_tt_q16):
+    """the count tensor of the last timed step, float64 (every count is an integer far below 2^53: exact)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "parking.npy"), np.ascontiguousarray(parking, dtype=np.float64))
+    np.save(os.path.join(path, "driving.npy"), np.ascontiguousarray(driving, dtype=np.float64))
+    np.save(os.path.join(path, "sum_tt_q16.npy"), np.array([sum_tt_q16], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -456,6 +462,9 @@ def main():
     ap.add_argument("--no-side", action="store_true", help="skip the secondary records (table_build, per_dataset, skewed, strong, configs3)")
     ap.add_argument("--skip-side", default="", help="comma-separated side records to leave out (profiling passes: melbourne, per_rank_emulated, per_dataset, skewed, table_build)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the placing kernel's own timing, "
+                                                        "full_pipeline, two_resamples_in_flight, the side records and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the count tensor of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     import torch
@@ -502,10 +511,12 @@ def main():
     # day is sampled): the library hands the pair to the launch itself (hipExtLaunchKernelGGL: begin and end of the dispatch),
     # which sits ~1 us above rocprofv3's kernel duration; hipEventRecord on either side of a launch sat ~3 us above it.
     s.set_profile(True, stride=49, kernel=0)
-    dt, blocks, counts = job.timed(args.steps, min_window_s=0.2)
+    dt, counts = job.timed(args.steps)
     sampler_ms_all = s.last_kernel_ms()
     s.set_profile(False)
-    parking, driving = job.check(counts)
+    parking, driving, sum_tt_q16 = job.check(counts)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, parking, driving, sum_tt_q16)
     form = s.get_info(4) if kernel_used in (0, 5) else 0     # 0 two launches per hour, 1 one, 3 placing first, 6 all hours in one launch
     fused = form in (1, 3)
     # the timed launches in launch order: the k-th is sampler launch 49 k of the timed region, i.e. hour (49 k) mod 24 of its step; the
@@ -515,7 +526,7 @@ def main():
 
     # the other hourly kernel of the step, timed the same way outside the headline's timed region (none when the hour is ONE launch)
     place_ms = []
-    if kernel_used in (0, 5) and form == 0:
+    if args.full and kernel_used in (0, 5) and form == 0:
         s.set_profile(True, stride=7, kernel=1)
         job.run_steps(max(8, min(args.steps, 40)))
         place_ms = s.last_kernel_ms()
@@ -523,23 +534,25 @@ def main():
 
     # secondary figure: the whole main.jl:88-95 sequence, initializestates -> 23-hour
     # IVP -> 24-hour resample, 47 car-steps per car; outside the headline's timed region
-    barrier()
-    t0 = time.perf_counter()
-    reps = 3
-    for _ in range(reps):
-        ss.init_states(C, cpz)
-        with torch.cuda.stream(ss.stream):
-            s.solve_ivp_async(SIM_SEED)
-        ss.resample_allreduce(SIM_SEED, travel=job.travel)
-    ss.synchronize()
-    barrier()
-    dt_full = (time.perf_counter() - t0) / reps
+    dt_full = None
+    if args.full:
+        barrier()
+        t0 = time.perf_counter()
+        reps = 3
+        for _ in range(reps):
+            ss.init_states(C, cpz)
+            with torch.cuda.stream(ss.stream):
+                s.solve_ivp_async(SIM_SEED)
+            ss.resample_allreduce(SIM_SEED, travel=job.travel)
+        ss.synchronize()
+        barrier()
+        dt_full = (time.perf_counter() - t0) / reps
 
     # secondary figure: two independent resamples of the same fleet side by side (a second context on its own stream; what a
     # parameter sweep or a run over several seeds does).  The hours of ONE resample are a serial chain of an issue-bound sampler
     # launch and a latency-bound placing launch; two chains interleave on the chip.  Outside the headline's timed region.
     pair_ms = None
-    if world == 1 and kernel_used in (0, 5) and not args.no_pair and not args.melbourne:
+    if args.full and world == 1 and kernel_used in (0, 5) and not args.no_pair and not args.melbourne:
         st2 = torch.cuda.Stream(device=local_rank)
         s2 = cpm.Sampler(Z, T, local_rank, stream=st2)
         s2.set_kernel(args.kernel)
@@ -563,7 +576,7 @@ def main():
         s2.close()
 
     side = {}
-    if not args.no_side and not args.skew and not args.melbourne and Z == 4096 and args.cars_per_zone == 1000:
+    if args.full and not args.no_side and not args.skew and not args.melbourne and Z == 4096 and args.cars_per_zone == 1000:
         if world == 1:
             skip = set(x for x in args.skip_side.split(",") if x)
             traffic0, _ = pmc_traffic(Z, count, args.skew)
@@ -633,8 +646,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
-            "timed_region_s": sum(blocks), "timed_blocks": len(blocks),   # blocks of EXACTLY `steps` steps, repeated until >= 0.2 s; value = the median block
-            "timed_block_ms_min_max": [min(blocks) / args.steps * 1e3, max(blocks) / args.steps * 1e3],
+            "timed_region_s": dt,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -671,9 +683,10 @@ def main():
                          "f64_equivalent": {"algorithmic_bytes_per_launch": f64_bytes,
                                             "achieved": f64_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0,
                                             "frac": (f64_bytes / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if avg_ms > 0 else 0.0}},
-            "full_pipeline": {"value": C * (2 * T - 1) / dt_full, "unit": "car-steps/s", "ms": dt_full * 1e3,
-                              "what": "initializestates + 23-hour IVP + 24-hour resample (main.jl:88-95), 47 car-steps per car"},
         }
+        if dt_full is not None:
+            out["full_pipeline"] = {"value": C * (2 * T - 1) / dt_full, "unit": "car-steps/s", "ms": dt_full * 1e3,
+                                    "what": "initializestates + 23-hour IVP + 24-hour resample (main.jl:88-95), 47 car-steps per car"}
         out.update(side)
         if pair_ms is not None:
             out["two_resamples_in_flight"] = {
@@ -681,7 +694,7 @@ def main():
                         "is one resample at a time)", "ms_per_pair": pair_ms, "ms_per_resample": pair_ms / 2,
                 "value": 2 * car_steps / (pair_ms * 1e-3), "unit": "car-steps/s",
                 "whole_resample_frac": 2 * T * alg_bytes / (pair_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        if world == 1 and not args.no_cpu_baseline and not args.skew:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.skew:
             out["cpu_baseline"] = cpu_baseline(s, Z, min(count, 65536), args.cpu_seconds, args.melbourne)
         if invalid_reasons:  # not the product library, or its counts unchecked: never a measurement of the product
             out = {"invalid": True, "reason": "set in the environment: " + ", ".join(invalid_reasons), "not_a_measurement": {k: v for k, v in out.items() if k != "value"}}

@@ -1,8 +1,9 @@
 """Guards julia/CarParkingMapsAMD.jl, which no Julia has ever parsed (there is no Julia runtime in the build image nor on the GPU
 box): every `ccall((:cpm_..., libcpm), Ret, (types...), args...)` in it is checked mechanically against the prototype of the same
 symbol in include/cpm.h -- symbol exists, arity, every argument's C type, the return type -- and the four overriding definitions
-keep the positional signatures main.jl calls them with (main.jl:82,85,91,95 of the reference, transcribed below; read from the
-reference itself too when it is present)."""
+keep the positional signatures main.jl calls them with (main.jl:82,85,91,95 of the reference, transcribed below and pinned by
+tests/golden/main_jl_calls.json, the argument lists as the reference's main.jl writes them)."""
+import json
 import os
 import re
 
@@ -132,12 +133,10 @@ def test_the_four_overrides_keep_main_jls_positional_signatures():
         assert inside, name
         names = [re.sub(r"::.*", "", a).strip() for a in _split_top(inside.group(1))]
         assert names == args, (name, names)
-    ref = "/root/reference/main.jl"          # present in the build container only
-    if os.path.exists(ref):
-        text = open(ref).read()
-        for name, args in MAIN_JL_CALLS.items():
-            m = re.search(rf"=\s*{name}\(([^)]*)\)", text)
-            assert m and [a.strip() for a in m.group(1).split(",")] == args, name
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "main_jl_calls.json")))["calls"]
+    assert set(ref) == set(MAIN_JL_CALLS)
+    for name, args in MAIN_JL_CALLS.items():
+        assert ref[name]["args"] == args, name
 
 
 def test_the_parser_catches_a_drifted_signature():
