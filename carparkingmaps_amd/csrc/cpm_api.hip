@@ -144,7 +144,13 @@ struct cpm_ctx {
     // finish_ivp() before anything reads or replaces the state or the tables.
     bool ivp_pending = false;
     uint64_t ivp_seed = 0;
+    int ivp_form = -1;                  // the hour form of the pending IVP attempt (GroupedWork::last_form behind its grouped_run)
     long long *h_ivp_status = nullptr;  // pinned [2], likewise
+    // what produced the results of the most recent step (CPM_INFO_LAST_KERNEL / _LAST_FORM), and the step attempts the library ran,
+    // discarded and ran again so far (CPM_INFO_STEPS_REPEATED)
+    int last_kernel = 0;
+    int last_form = -1;
+    int64_t steps_repeated = 0;
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -623,6 +629,8 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         c->zg.set_parts(static_cast<uint32_t>(c->h_status[1]), static_cast<uint32_t>(c->h_status[1] >> 32));
     }
     const int kernel = pick_kernel(c);
+    c->last_kernel = kernel;  // (the family this call enqueues; the grouped path's form is recorded behind its run)
+    c->last_form = kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
     if (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED)  // (the grouped path zeroes the count tensor with its other counters, in one launch)
         HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * nwords, c->stream));
     if (c->n == 0) return CPM_OK;
@@ -648,6 +656,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         }
         int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, travel, d_counts, c->cu_count,
                                       [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error);
+        if (rc == CPM_OK) c->last_form = c->zg.last_form;
         if (rc == CPM_OK && c->h_status && !c->status_pending) {
             c->h_status[1] = 0;
             if (hipMemcpyAsync(c->h_status, d_counts + nwords - 1, sizeof(long long), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
@@ -686,7 +695,10 @@ int32_t ivp_exact(cpm_ctx *c, uint64_t seed)
         int32_t rc_cdf = ensure_full_cdf(c);
         if (rc_cdf != CPM_OK) return rc_cdf;
     }
-    if (pick_kernel(c) != CPM_KERNEL_CAR && cpm::exact_path_fits(static_cast<int>(c->Z))) {
+    const bool exact = pick_kernel(c) != CPM_KERNEL_CAR && cpm::exact_path_fits(static_cast<int>(c->Z));
+    c->last_kernel = exact ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
+    c->last_form = -1;
+    if (exact) {
         return cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
                               c->d_zone0, seed, false, nullptr, c->d_counts, c->cu_count, [](int) {}, [](int) {}, g_last_error, true, c->d_zone0);
     }
@@ -706,6 +718,7 @@ int32_t ivp_grouped(cpm_ctx *c, uint64_t seed)
     int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, false, c->d_counts, c->cu_count,
                                   [](int) {}, [](int) {}, g_last_error, true, c->d_ztmp);
     if (rc != CPM_OK) return rc;
+    c->ivp_form = c->zg.last_form;
     c->h_ivp_status[1] = 0;
     HIP_TRY(hipMemcpyAsync(c->h_ivp_status, c->d_counts + 2 * c->T * c->Z + 1, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(c->h_ivp_status + 1, c->zg.maxn, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -720,24 +733,26 @@ int32_t finish_ivp(cpm_ctx *c)
     c->ivp_pending = false;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->zg.set_parts(static_cast<uint32_t>(c->h_ivp_status[1]), static_cast<uint32_t>(c->h_ivp_status[1] >> 32));
-    if (c->h_ivp_status[0] == 0) {
+    auto commit = [&]() -> int32_t {
         std::swap(c->d_zone0, c->d_ztmp);
+        c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
+        c->last_form = c->ivp_form;
         HIP_TRY(cpm::grouped_commit_ivp(c->zg, c->stream));
         return CPM_OK;
-    }
-    // A bucket or a run outgrew its region: d_zone0 is untouched.  Run the IVP again with twice the regions while the problem
-    // still fits, else on the exact layout (and stay there).
+    };
+    if (c->h_ivp_status[0] == 0) return commit();
+    // A bucket or a run outgrew its region (or a block of a one-launch form gave up waiting): d_zone0 is untouched.  Run the IVP
+    // again with twice the regions while the problem still fits (two launches per hour after a bail-out), else on the exact layout
+    // (and stay there).  Every discarded attempt counts as a repeat.
     while (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && absorb_status(c, c->h_ivp_status[0])) {
+        ++c->steps_repeated;
         int32_t rc = ivp_grouped(c, c->ivp_seed);
         if (rc != CPM_OK) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->zg.set_parts(static_cast<uint32_t>(c->h_ivp_status[1]), static_cast<uint32_t>(c->h_ivp_status[1] >> 32));
-        if (c->h_ivp_status[0] == 0) {
-            std::swap(c->d_zone0, c->d_ztmp);
-            HIP_TRY(cpm::grouped_commit_ivp(c->zg, c->stream));
-            return CPM_OK;
-        }
+        if (c->h_ivp_status[0] == 0) return commit();
     }
+    ++c->steps_repeated;
     if (c->kernel == CPM_KERNEL_AUTO) c->grouped_overflowed = true;
     c->zx.buckets0_valid = false;
     c->zg.buckets0_valid = false;
@@ -750,7 +765,11 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
     if (!c->have_state) return fail(CPM_ERR_STATE, "solve_ivp: no car state");
     int32_t rc = finish_ivp(c);
     if (rc != CPM_OK) return rc;
-    if (c->n == 0) return CPM_OK;
+    if (c->n == 0) {  // (nothing to run: the record names the family all the same)
+        c->last_kernel = pick_kernel(c);
+        c->last_form = c->last_kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
+        return CPM_OK;
+    }
     if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && grouped_fits(c, c->zg.cap_mult)) {
         rc = ivp_grouped(c, seed);
         if (rc != CPM_OK) return rc;
@@ -934,18 +953,32 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
     case CPM_INFO_PARTS:
         *value_out = c->zg.parts;
         return CPM_OK;
-    case CPM_INFO_FUSED:
+    case CPM_INFO_FUSED: {
+        // (the conditions grouped_run decides on: the day launch needs two applied hours and bucket regions below the counters' XCD
+        //  bits; with one hour a run has no hour to fuse but in the placing-first form)
+        const bool day = c->zg.fused_day && c->T >= 3 && cpm::grouped_cap(c->n, static_cast<int>(c->Z), c->zg.cap_mult) < (1u << cpm::kCntXccShift);
         *value_out = (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && c->zg.fused_ok && c->zg.parts <= 1 &&
                       cpm::fused_shape_ok(static_cast<int>(c->Z), c->Zq, c->pk_G, c->sparse_tables) &&
                       (!c->zg.fused_auto || cpm::fused_pays(static_cast<int>(c->Z), c->Zq, c->pk_G, c->cu_count, c->sparse_tables, (c->n + c->Z - 1) / std::max<int64_t>(c->Z, 1))))
-                         ? (c->zg.fused_day ? 6 : (c->zg.fused_pf ? 3 : 1))
+                         ? (day ? 6 : (c->zg.fused_pf ? 3 : (c->T >= 2 ? 1 : 0)))
                          : 0;
         return CPM_OK;
+    }
     case CPM_INFO_SPARSE_TABLES:
         *value_out = c->sparse_tables ? cpm::pack_row_words(c->Zq, c->pk_G, 1) : 0;
         return CPM_OK;
     case CPM_INFO_FUSED_BAILOUTS:
         *value_out = c->fused_bailouts;
+        return CPM_OK;
+    case CPM_INFO_LAST_KERNEL:
+    case CPM_INFO_LAST_FORM:
+    case CPM_INFO_STEPS_REPEATED:
+        if (c->ivp_pending) {  // a record of committed steps: an IVP still in flight is committed (or repeated) first
+            HIP_TRY(hipSetDevice(c->device));
+            int32_t rc_ivp = finish_ivp(c);
+            if (rc_ivp != CPM_OK) return rc_ivp;
+        }
+        *value_out = what == CPM_INFO_LAST_KERNEL ? c->last_kernel : what == CPM_INFO_LAST_FORM ? c->last_form : c->steps_repeated;
         return CPM_OK;
     default:
         return fail(CPM_ERR_ARG, "unknown info %d", what);
@@ -1534,12 +1567,15 @@ int32_t cpm_resample(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking
         return CPM_OK;
     };
     if (rc == CPM_OK) rc = fetch();
-    // a bucket or a run outgrew its region: again with twice the regions while the problem still fits ...
+    // a bucket or a run outgrew its region (or a block of a one-launch form gave up waiting): again with twice the regions while the
+    // problem still fits (two launches per hour after a bail-out) ...  (each discarded attempt: CPM_INFO_STEPS_REPEATED)
     while (rc == CPM_OK && c->h_counts[nwords - 1] != 0 && pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && absorb_status(c, c->h_counts[nwords - 1])) {
+        ++c->steps_repeated;
         rc = resample_enqueue(c, seed, flags, c->d_counts);
         if (rc == CPM_OK) rc = fetch();
     }
     if (rc == CPM_OK && c->h_counts[nwords - 1] != 0) {  // ... else on a layout that cannot overflow
+        ++c->steps_repeated;
         if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED) c->grouped_overflowed = true;
         c->kernel = cpm::exact_path_fits(static_cast<int>(c->Z)) ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
         rc = resample_enqueue(c, seed, flags, c->d_counts);

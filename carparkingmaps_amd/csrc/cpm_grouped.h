@@ -2730,6 +2730,8 @@ struct GroupedWork {
     int parts = 1;                                               // workgroups per heavy zone: 1 + blocks of the heavy kernel (set_parts)
     int hgrid = 0;                                               // zones the heavy launch covers
     const uint32_t *ivp_ids = nullptr, *ivp_cnt = nullptr;       // final buckets of the last IVP (grouped_commit_ivp)
+    int last_form = -1;                                          // form the applied hours of the last run took (CPM_INFO_LAST_FORM coding: 0 two
+                                                                 // launches, 1 one, 3 placing first, 6 all in one launch), from grouped_run's decision
 
     // destination groups of a run: general (any zones per group) for sparse row packs, power-of-two for dense ones (grouped_gdiv_of)
     void set_groups(bool general)
@@ -3004,6 +3006,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         pend_D = pend_cntg = nullptr;
     };
     int t_first = 0;
+    w.last_form = day_n >= 2 ? 6 : 0;  // (raised below by the first hour that runs a one-launch form)
     if (day_n >= 2) {
         prof_begin(CPM_PROFILE_SAMPLER);
         grouped_launch_day(w.day_hours, day_n, Z, tb.Zq, G, tb.smap, static_cast<int>(w.zpg), nchunk, w.day_mix, mean, stream);
@@ -3047,6 +3050,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         const bool after_day = day_n >= 2 && t == t_first;  // (the hour behind a day launch: its placing rides in front, whatever the context's own form)
         const bool pf = shape && (w.fused_pf || after_day);  // (also the last hour, in its plain form: the placing of the hour before it rides in front)
         const bool fuse = grouped && !last_hour && shape && !pf;
+        if (w.last_form == 0 && (pf || fuse)) w.last_form = pf ? 3 : 1;
         if (!pf) flush_pending();
         a.pD = pend_D;
         a.pcntg = pend_cntg;

@@ -66,7 +66,7 @@ class Sampler:
         (tests), 3 the placing-first form (the previous hour's placing blocks in front of the hour's samplers), 4 = 3 with samplers
         that give up at once (tests); 6 all hours of a run in ONE launch (k_grouped_day: the placing blocks of an hour among the next
         hour's sampler workgroups, which draw for their stayers first), 8 = 6 with the placing blocks in front, 7 = 6 with blocks that
-        give up at once (tests), 9 = 6 where it pays; lag: chunks of sampler workgroups in front of a chunk's placing blocks (mode 1)."""
+        give up at once (tests); lag: chunks of sampler workgroups in front of a chunk's placing blocks (mode 1)."""
         _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_FUSED, int(mode)))
         if lag is not None:
             _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_FUSED_LAG, int(lag)))
@@ -78,12 +78,23 @@ class Sampler:
         _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_ZONE_ORDER, int(on)))
 
     def get_info(self, what):
-        """cpm_get_info: 1 = kernel family AUTO resolves to now, 2 = bucket-region size in multiples of the mean bucket, 3 = workgroups per
-        heavy zone, 4 = form of the hour (0 two launches, 1 one, 3 placing first, 6 all hours in one launch), 5 = steps that bailed out of a
-        one-launch form, 6 = words of a sparse row pack (0: dense tables)."""
+        """cpm_get_info (keys: _lib.CPM_INFO_*).  What the context would run next: 1 = kernel family AUTO resolves to now, 2 =
+        bucket-region size in multiples of the mean bucket, 3 = workgroups per heavy zone, 4 = form of the hour (0 two launches, 1 one,
+        3 placing first, 6 all hours in one launch), 5 = steps that bailed out of a one-launch form, 6 = words of a sparse row pack (0:
+        dense tables).  What its most recent step ran: 7 = the kernel family that produced its results (0 before any step), 8 = the
+        form its grouped hours took (coded as 4; -1 when the family is not the grouped one), 9 = step attempts the library discarded
+        and ran again so far."""
         v = C.c_int64(0)
         _lib.check(self._L.cpm_get_info(self._h, int(what), C.byref(v)))
         return int(v.value)
+
+    def last_step(self):
+        """The record of the most recent step: {kernel, form, repeats (cumulative), cap_mult, parts, bailouts (cumulative)}.
+        Not a plain getter: an IVP that solve_ivp_async left in flight is committed first (the call waits for the stream and may
+        repeat that IVP, which then shows in `repeats`), so it must not be called while the stream is being captured."""
+        return dict(kernel=self.get_info(_lib.CPM_INFO_LAST_KERNEL), form=self.get_info(_lib.CPM_INFO_LAST_FORM),
+                    repeats=self.get_info(_lib.CPM_INFO_STEPS_REPEATED), cap_mult=self.get_info(_lib.CPM_INFO_CAP_MULT),
+                    parts=self.get_info(_lib.CPM_INFO_PARTS), bailouts=self.get_info(_lib.CPM_INFO_FUSED_BAILOUTS))
 
     def set_profile(self, on=True, stride=1, kernel=0):
         """hipEvents around every `stride`-th hourly launch of `kernel` (0 sampler, 1 place, 2 travel); on=False: off."""

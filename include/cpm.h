@@ -120,7 +120,18 @@ int32_t cpm_set_option(cpm_ctx *ctx, int32_t option, int64_t value);
 #define CPM_INFO_FUSED_BAILOUTS 5 /* steps so far that came back with status bit 2 (a block of a one-launch form gave up waiting: the context then keeps to two launches per hour) */
 #define CPM_INFO_FUSED 4   /* 1 (3: in its placing-first form, 6: all hours in one launch) when the next grouped step runs the fused hour (one launch per hour), 0 when it takes two launches per hour: switched
                             * off (CPM_OPT_FUSED), heavy buckets seen (CPM_INFO_PARTS > 1), rows / groups outside the fused instantiations, or
-                            * a placing block once gave up waiting */
+                            * a placing block once gave up waiting.  A prediction; what ran is CPM_INFO_LAST_FORM.  It does not know the next
+                            * step's kind: a travel resample whose runs of all hours do not fit their 24 GiB budget runs 6 hour by hour (1), and
+                            * an IVP at T = 1 runs no hour at all (0) */
+/* what the context DID: a record of its most recent step (an IVP or a resample; reading one of these commits an IVP that
+ * cpm_solve_ivp_async left in flight) */
+#define CPM_INFO_LAST_KERNEL 7     /* the kernel family (CPM_KERNEL_CAR / _ZONE_LDS / _ZONE_GROUPED) whose launches produced the results of the
+                                    * most recent step; 0 before any.  A blocking cpm_resample: the attempt whose counts it returned (CAR for the
+                                    * state / transition matrices); an IVP: the attempt that was committed; cpm_resample_dev: what it enqueued */
+#define CPM_INFO_LAST_FORM 8       /* when CPM_INFO_LAST_KERNEL is CPM_KERNEL_ZONE_GROUPED: the form its applied hours ran in, coded as
+                                    * CPM_INFO_FUSED (0 two launches per hour, 1 one, 3 placing first, 6 all hours in one launch); -1 otherwise */
+#define CPM_INFO_STEPS_REPEATED 9  /* step attempts the blocking calls ran, discarded and ran again so far (regions grown, a one-launch form
+                                    * that bailed out repeated with two launches, a demotion to a layout that cannot overflow); 0 on a new context */
 int32_t cpm_get_info(cpm_ctx *ctx, int32_t what, int64_t *value_out);
 /* run on a caller-owned hipStream_t (e.g. torch's current stream); NULL = ctx's own, which is created when a call first needs it.
  * Contexts meant to run side by side (two resamples interleave on the chip) are each given their stream right behind

@@ -86,6 +86,12 @@ int main(int argc, char **argv)
     CHECK(cpm_resample(h, seed, 0u, parking2, driving2, NULL, state, trans));
     int64_t info_kernel = -1;
     CHECK(cpm_get_info(h, CPM_INFO_KERNEL, &info_kernel));
+    /* the record of the last step (the compat call: the per-car kernel) by the header's names; an unknown key is an argument error */
+    int64_t last_kernel = -1, last_form = -2, steps_repeated = -1, unknown = 0;
+    CHECK(cpm_get_info(h, CPM_INFO_LAST_KERNEL, &last_kernel));
+    CHECK(cpm_get_info(h, CPM_INFO_LAST_FORM, &last_form));
+    CHECK(cpm_get_info(h, CPM_INFO_STEPS_REPEATED, &steps_repeated));
+    int32_t unknown_status = cpm_get_info(h, CPM_INFO_STEPS_REPEATED + 1, &unknown);
     /* error convention: a status, a message, no abort */
     int32_t bad = cpm_set_state(h, NULL);
     printf("Z %" PRId64 " C %" PRId64 " kernel %" PRId64 " null_state_status %d\n", Z, C, info_kernel, (int)bad);
@@ -98,6 +104,8 @@ int main(int argc, char **argv)
     int64_t hour_sum = 0;
     for (int64_t z = 0; z < Z; ++z) hour_sum += parking[z + Z * (T - 1)];
     printf("hour24_cars %" PRId64 "\n", hour_sum);
+    printf("last_kernel %" PRId64 " last_form %" PRId64 " steps_repeated %" PRId64 " unknown_info_status %d\n", last_kernel, last_form,
+           steps_repeated, (int)unknown_status);
     CHECK(cpm_destroy(h));
     free(p_drive); free(p_dest); free(zones); free(initial_state); free(parking); free(driving); free(state); free(trans); free(parking2); free(driving2);
     return 0;

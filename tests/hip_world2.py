@@ -27,11 +27,13 @@ ss.s.synth_tables(table_seed)
 first, count = ss.init_states(C, cpz)
 ss.s.solve_ivp_async(sim_seed)
 out = {"backend": dist.get_backend(), "world": dist.get_world_size(), "count": count, "steps": []}
+status = []                                             # this rank's status word of every step (before the reduce)
 for k in range(2):
     with torch.cuda.stream(ss.stream):
         ss.s.resample_dev(sim_seed + k, ss.counts.data_ptr(), travel=False)
         host = ss.counts.cpu()
     own_cars = int(host[:Z].sum())                      # this rank's cars at hour 1
+    status.append(int(host[-1]))
     dist.all_reduce(host)                               # the path's one exchange: integer sum of [parking | driving | time | status]
     pk, dr, tt = split_counts(host, Z, T)
     out["steps"].append({"parking": hashlib.sha256(pk.tobytes(order="F")).hexdigest(), "driving": hashlib.sha256(dr.tobytes(order="F")).hexdigest(),
@@ -39,6 +41,10 @@ for k in range(2):
 counts = [None] * world
 dist.all_gather_object(counts, count)
 out["counts"] = counts
+ranks = [None] * world                                  # the family that produced every rank's counts, and its status words
+dist.all_gather_object(ranks, (ss.s.last_step()["kernel"], status))
+out["last_kernel"] = [k for k, _ in ranks]
+out["status"] = [st for _, st in ranks]
 ss.close()
 dist.barrier()
 dist.destroy_process_group()

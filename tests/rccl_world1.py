@@ -24,7 +24,7 @@ ss = ShardedSampler(Z, T)                       # rank / world size from the pro
 ss.s.synth_tables(table_seed)
 ss.init_states(C, cpz)
 ss.s.solve_ivp_async(sim_seed)
-out = {"backend": dist.get_backend(), "world": dist.get_world_size(), "steps": []}
+out = {"backend": dist.get_backend(), "world": dist.get_world_size(), "steps": [], "status": []}
 tickets = []
 for k in range(4):                              # pipelined: a step's all-reduce runs beside the next step's kernels
     buf, ticket = ss.resample_allreduce_async(sim_seed + (k & 1))
@@ -34,14 +34,18 @@ for k in range(4):                              # pipelined: a step's all-reduce
         ss.wait(t)
         with torch.cuda.stream(ss.stream):
             host = b.to("cpu")
+        out["status"].append(int(host[-1]))            # (the status word after the reduce: split_counts raises on a set one)
         pk, dr, tt = split_counts(host, Z, T)
         out["steps"].append({"k": kk, "parking": hashlib.sha256(pk.tobytes(order="F")).hexdigest(), "driving": hashlib.sha256(dr.tobytes(order="F")).hexdigest(),
                              "cars_per_hour_ok": bool((pk.sum(axis=0) == C).all())})
 ss.synchronize()
 counts = ss.resample_allreduce(sim_seed)        # the blocking form
 with torch.cuda.stream(ss.stream):
-    pk, dr, tt = split_counts(counts.to("cpu"), Z, T)
+    host = counts.to("cpu")
+out["status"].append(int(host[-1]))
+pk, dr, tt = split_counts(host, Z, T)
 out["sync"] = {"parking": hashlib.sha256(pk.tobytes(order="F")).hexdigest(), "driving": hashlib.sha256(dr.tobytes(order="F")).hexdigest()}
+out["last_kernel"] = ss.s.last_step()["kernel"]  # the family that produced the last step's counts
 ss.close()
 dist.destroy_process_group()
 print("RESULT " + json.dumps(out), flush=True)

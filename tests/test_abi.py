@@ -129,6 +129,10 @@ def test_c_harness_call_sequence_equals_the_ctypes_path(cpm, tmp_path):
     assert int(got["parking"], 16) == _fnv(r["parking"].ravel(order="F")) and int(got["driving"], 16) == _fnv(r["driving"].ravel(order="F"))
     assert int(got["tt"]) == 0 and int(got["compat_counts_equal"]) == 1 and int(got["hour24_cars"]) == C
     assert int(got["state"], 16) == _fnv(r2["state"].ravel(order="F")) and int(got["trans"], 16) == _fnv(r2["trans"].ravel(order="F"))
+    # CPM_INFO_LAST_KERNEL / _LAST_FORM / _STEPS_REPEATED through the header's names: the compat resample ran the per-car kernel
+    # (no hour form), nothing was repeated; a key past them is still CPM_ERR_ARG
+    assert int(got["last_kernel"]) == cpm.CPM_KERNEL_CAR and int(got["last_form"]) == -1 and int(got["steps_repeated"]) == 0
+    assert int(got["unknown_info_status"]) == -1
 
 
 def test_every_lds_dma_sampler_waits_for_its_pack_before_the_barrier(cpm, tmp_path):

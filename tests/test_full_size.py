@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import SIM_SEED, TABLE_SEED
+from product_form import GROUPED, pinned
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -36,9 +37,15 @@ def test_s8k_rank_shards_of_the_8_gpu_configuration(cpm):
         for name, sh in sorted(c["shards"].items(), key=lambda kv: -kv[1]["car_stride"]):
             s.init_states(C, cpz, sh["car_first"], sh["car_count"], car_stride=sh["car_stride"])
             assert s.get_info(1) == cpm.CPM_KERNEL_ZONE_GROUPED, name           # what AUTO resolves to for a rank's shard
-            init = s.solve_ivp(c["sim_seed"])
+            # (interleaved: every bucket starts at its mean size, nothing is repeated; contiguous: the first such shard's IVP outgrows
+            #  the regions in its first hour and is repeated with them doubled -- every repeat is a doubling, checked below)
+            interleaved = sh["car_stride"] > 1
+            with pinned(s, 0, family=GROUPED, repeats=0 if interleaved else None):
+                init = s.solve_ivp(c["sim_seed"])
             assert _sha(init) == sh["initial_state_sha256"], name
-            r = s.resample(c["sim_seed"])
+            with pinned(s, 0, family=GROUPED):
+                r = s.resample(c["sim_seed"])
+            assert s.get_info(cpm.CPM_INFO_CAP_MULT) == 4 << s.get_info(cpm.CPM_INFO_STEPS_REPEATED), name
             assert (r["parking"].sum(axis=0) == sh["car_count"]).all(), name     # every hour holds the whole shard
             assert _sha(r["parking"].ravel(order="F")) == sh["parking_sha256"], name
             assert _sha(r["driving"].ravel(order="F")) == sh["driving_sha256"], name
@@ -68,11 +75,14 @@ def test_melbourne_shaped_full_fleet_with_travel_times(cpm, O):
         del p_dest
         ref = O.fast_run(p_drive, cdf, C, SIM_SEED, np.arange(C, dtype=np.int64) // cpz + 1, datamatrix=dm, dist=dist)
         s.init_states(C, cpz)
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
-        r = s.resample(SIM_SEED, travel=True)
+        with pinned(s, 0, family=GROUPED):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, 0, family=GROUPED):              # the form CPM_INFO_FUSED predicts (one launch per hour on 256 CUs)
+            r = s.resample(SIM_SEED, travel=True)
         s.set_fused(3)                                  # the placing-first form of the hour at full size: the same counts
         assert s.get_info(4) == 3
-        r3 = s.resample(SIM_SEED, travel=True)
+        with pinned(s, 0, family=GROUPED, fused=3):
+            r3 = s.resample(SIM_SEED, travel=True)
         assert s.get_info(4) == 3                       # (no sampler workgroup gave up or found its arrivals on another XCD)
     assert np.array_equal(r3["parking"], ref["parking"]) and np.array_equal(r3["driving"], ref["driving"]) and r3["sum_tt_q16"] == ref["sum_tt_q16"]
     assert np.array_equal(r["parking"], ref["parking"])
@@ -103,7 +113,13 @@ def test_model_selection_grid_of_256_points_at_melbourne_size(cpm, O):
         s.init_states(C, cpz)
         init = s.solve_ivp(SIM_SEED)                                   # once; every point restarts from it
         ev = ms.Evaluator(s, C, SIM_SEED, measured_act, measured_park, travel=True)
+        repeats0 = s.get_info(cpm.CPM_INFO_STEPS_REPEATED)
         per_rank = [ms.grid_sweep(ev, grid, rank=r, world_size=world, gather=False, checksums=True) for r in range(world)]
+        # the grouped path produced the counts and the library repeated no step; a point the pipelined sweep evaluated again
+        # (its asynchronous step overflowed) shows as grown regions
+        assert s.get_info(cpm.CPM_INFO_LAST_KERNEL) == GROUPED
+        assert s.get_info(cpm.CPM_INFO_STEPS_REPEATED) == repeats0
+        assert (ev.fallbacks > 0) == (s.get_info(cpm.CPM_INFO_CAP_MULT) > 4), (ev.fallbacks, s.get_info(cpm.CPM_INFO_CAP_MULT))
         results = []
         for i in range(len(grid)):
             owners = [r for r in range(world) if per_rank[r][i] is not None]

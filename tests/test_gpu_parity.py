@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import SIM_SEED, TABLE_SEED
+from product_form import CAR, GROUPED, ZONE_LDS, at_least, auto_family, pinned
 
 pytestmark = pytest.mark.gpu
 
@@ -62,14 +63,17 @@ def test_ivp_and_counts_bit_exact(cpm, O, kernel, Z, cpz):
         s.set_p_dest(p_dest)
         s.init_states(C, cpz)
         assert np.array_equal(s.get_state(), _zone0(C, cpz))
-        init = s.solve_ivp(SIM_SEED)
+        with pinned(s, kernel):
+            init = s.solve_ivp(SIM_SEED)
         assert np.array_equal(init, ref["zone0"])
-        r = s.resample(SIM_SEED)
+        with pinned(s, kernel):
+            r = s.resample(SIM_SEED)
         assert np.array_equal(r["parking"], ref["parking"])
         assert np.array_equal(r["driving"], ref["driving"])
         assert (r["parking"].sum(axis=0) == C).all()
         # the resample leaves the initial state untouched: a second call gives the same counts
-        r2 = s.resample(SIM_SEED)
+        with pinned(s, kernel):
+            r2 = s.resample(SIM_SEED)
         assert np.array_equal(r2["parking"], ref["parking"]) and np.array_equal(r2["driving"], ref["driving"])
         # densities: same count / C in f64 on both sides -> well inside the 1e-6 relative bound
         dens = r["parking"] / C
@@ -95,8 +99,10 @@ def test_compat_matrices_equal_the_faithful_oracle(cpm, O):
         s.set_p_dest(p_dest)
         s.set_datamatrix(dm, dist)
         s.init_states(C, cpz)
-        assert np.array_equal(s.solve_ivp(SIM_SEED), init)
-        r = s.resample(SIM_SEED, travel=True, want_state=True, want_trans=True)
+        with pinned(s, 0):                                   # the IVP: what AUTO picks
+            assert np.array_equal(s.solve_ivp(SIM_SEED), init)
+        with pinned(s, 0, family=CAR):                       # the matrices: the per-car kernel keeps every car's hours
+            r = s.resample(SIM_SEED, travel=True, want_state=True, want_trans=True)
     assert np.array_equal(r["state"], st)
     assert np.array_equal(r["trans"][:, :, 0], tr[:, :, 0])
     assert np.array_equal(r["trans"][:, :, 1], tr[:, :, 1])
@@ -124,8 +130,10 @@ def test_travel_time_sum_bit_exact(cpm, O, kernel):
         s.set_p_dest(p_dest)
         s.set_datamatrix(dm, dist)
         s.init_states(C, cpz)
-        s.solve_ivp(SIM_SEED, want=False)
-        r = s.resample(SIM_SEED, travel=True)
+        with pinned(s, kernel):
+            s.solve_ivp(SIM_SEED, want=False)
+        with pinned(s, kernel):
+            r = s.resample(SIM_SEED, travel=True)
     assert np.array_equal(r["parking"], ref["parking"])
     assert np.array_equal(r["driving"], ref["driving"])
     assert r["sum_tt_q16"] == ref["sum_tt_q16"]
@@ -147,8 +155,10 @@ def test_travel_time_sum_for_every_block_size_of_the_travel_kernel(cpm, O, cpz):
         s.set_p_dest(p_dest)
         s.set_datamatrix(dm, dist)
         s.init_states(C, cpz)
-        s.solve_ivp(SIM_SEED, want=False)
-        r = s.resample(SIM_SEED, travel=True)
+        with pinned(s, 5):
+            s.solve_ivp(SIM_SEED, want=False)
+        with pinned(s, 5):
+            r = s.resample(SIM_SEED, travel=True)
         assert s.get_info(1) == cpm.CPM_KERNEL_ZONE_GROUPED
     assert np.array_equal(r["parking"], ref["parking"])
     assert np.array_equal(r["driving"], ref["driving"])
@@ -171,8 +181,10 @@ def test_travel_times_when_a_row_of_the_travel_table_does_not_fit_lds(cpm, O):
         s.set_p_dest(p_dest)
         s.set_datamatrix(dm, dist)
         s.init_states(C, cpz)
-        s.solve_ivp(SIM_SEED, want=False)
-        r = s.resample(SIM_SEED, travel=True)
+        with pinned(s, 5):
+            s.solve_ivp(SIM_SEED, want=False)
+        with pinned(s, 5):
+            r = s.resample(SIM_SEED, travel=True)
         assert s.get_info(1) == cpm.CPM_KERNEL_ZONE_GROUPED
     assert np.array_equal(r["parking"], ref["parking"])
     assert np.array_equal(r["driving"], ref["driving"])
@@ -183,7 +195,11 @@ def test_travel_times_when_a_row_of_the_travel_table_does_not_fit_lds(cpm, O):
 def test_edge_rows(cpm, O, kernel):
     """Zero rows (dest = origin, still counted as driving: Appendix A-8), p_drive 0 / 1 / NaN zones
     (A-3, A-6), rows that sum to less than one (fall-through, deviation D1), sparse rows with
-    leading / trailing zero-probability zones (A-9)."""
+    leading / trailing zero-probability zones (A-9).  Zone 4's zero row sends every one of its drivers back to zone 4: ONE run of
+    the grouped path, up to 372 drivers in an hour of the resample (the IVP's stay within 288).  A run holds a quarter of a bucket
+    region (grouped_scap): 288 entries at the 1,024-slot floor that 4x, 8x and 16x the mean of 40 cars all land on, 352 at 32x,
+    672 at 64x -- so on the grouped path the IVP runs clean and the resample is repeated four times, the regions doubled up to 64x.
+    (Three of the four repeats run on regions of the same size: the doubling does not skip what the floor swallows.)"""
     Z, T, cpz = 48, 24, 40
     C = Z * cpz
     p_drive, p_dest = _tables(O, Z, T)
@@ -208,8 +224,11 @@ def test_edge_rows(cpm, O, kernel):
         s.set_p_drive(p_drive)
         s.set_p_dest(p_dest)
         s.init_states(C, cpz)
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
-        r = s.resample(SIM_SEED)
+        grouped = kernel in (0, 5)
+        with pinned(s, kernel, cap_mult=4):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, kernel, repeats=4 if grouped else 0, cap_mult=64 if grouped else 4):
+            r = s.resample(SIM_SEED)
     assert np.array_equal(r["parking"], ref["parking"])
     assert np.array_equal(r["driving"], ref["driving"])
     assert r["driving"][2].sum() == 0       # NaN zone never drives
@@ -263,8 +282,10 @@ def test_shards_sum_to_the_single_run(cpm, O, kernel):
             for rank in range(world):
                 b, n = shard_range(C, rank, world)
                 s.init_states(C, cpz, b, n)
-                s.solve_ivp(SIM_SEED, want=False)
-                r = s.resample(SIM_SEED)
+                with pinned(s, kernel):
+                    s.solve_ivp(SIM_SEED, want=False)
+                with pinned(s, kernel):
+                    r = s.resample(SIM_SEED)
                 pk += r["parking"]
                 dr += r["driving"]
             s.init_states(C, cpz, C, 0)  # empty shard
@@ -343,7 +364,8 @@ def test_headline_config_full_size(cpm, O):
     """BASELINE.json configs[2] at full size (Z = 4,096, 1,000 cars/zone, C = 4,096,000): tables built
     on the device by cpm_synth_tables, IVP + resample on the device, against the oracle's fast twin
     on oracle-built tables -- post-IVP state and both count tensors bit-exact -- plus the
-    size-independent properties (every hour holds all C cars; repeatable; shards add up)."""
+    size-independent properties (every hour holds all C cars; repeatable; shards add up).  The counts are pinned to the form
+    bench.py times: the grouped path's one-launch hour (on 256 CUs), bucket regions at 4x the mean, no step repeated, no bail-out."""
     from carparkingmaps_amd.distributed import shard_range
     Z, T, cpz = 4096, 24, 1000
     C = Z * cpz
@@ -357,16 +379,21 @@ def test_headline_config_full_size(cpm, O):
         s.synth_tables(TABLE_SEED)
         assert np.array_equal(s.get_p_drive(), p_drive)
         s.init_states(C, cpz)
-        init = s.solve_ivp(SIM_SEED)
+        with pinned(s, 0, form=1, cap_mult=4, parts=1) as ivp:
+            init = s.solve_ivp(SIM_SEED)
+        assert ivp["kernel"] == GROUPED
         assert np.array_equal(init, ref["zone0"])
-        r = s.resample(SIM_SEED)
+        with pinned(s, 0, form=1, cap_mult=4, parts=1) as step:
+            r = s.resample(SIM_SEED)
+        assert step["kernel"] == GROUPED and step["repeats"] == 0 and step["bailouts"] == 0
         assert np.array_equal(r["parking"], ref["parking"])
         assert np.array_equal(r["driving"], ref["driving"])
         assert (r["parking"].sum(axis=0) == C).all()
         np.testing.assert_allclose(r["parking"] / C, ref["parking"] / C, rtol=1e-6, atol=0)
         for kernel in (1, 2):  # the other kernels agree at full size too
             _set_kernel(s, kernel)
-            r2 = s.resample(SIM_SEED)
+            with pinned(s, kernel):
+                r2 = s.resample(SIM_SEED)
             assert np.array_equal(r2["parking"], ref["parking"]) and np.array_equal(r2["driving"], ref["driving"])
         s.set_kernel(0)
         # two shards of the same fleet add up to the whole (Philox keyed by the global car id)
@@ -375,7 +402,8 @@ def test_headline_config_full_size(cpm, O):
             b, n = shard_range(C, rank, 2)
             s.init_states(C, cpz, b, n)
             s.set_state(init[b:b + n])
-            pk += s.resample(SIM_SEED)["parking"]
+            with pinned(s, 0):
+                pk += s.resample(SIM_SEED)["parking"]
         assert np.array_equal(pk, ref["parking"])
 
 
@@ -397,9 +425,13 @@ def test_melbourne_shaped_config(cpm, O, cpz):
         assert np.array_equal(p_dest, O.createpdestin(dm, Z, T, 2))
         ref = O.fast_run(p_drive, O.build_cdf(p_dest), C, SIM_SEED, _zone0(C, cpz), datamatrix=dm, dist=dist)
         s.init_states(C, cpz)
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        assert s.get_info(cpm.CPM_INFO_SPARSE_TABLES) > 0   # sparse row packs: destination groups of any size
+        with pinned(s, 0, form=0):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
         assert s.get_info(1) == 5                          # AUTO runs the grouped path at both fleet sizes
-        r = s.resample(SIM_SEED, travel=True)
+        with pinned(s, 0, form=0) as step:                 # the two-launch sparse sampler produced the counts (256 CUs: one launch pays from 256 cars/zone)
+            r = s.resample(SIM_SEED, travel=True)
+        assert step["kernel"] == GROUPED
     assert np.array_equal(r["parking"], ref["parking"])
     assert np.array_equal(r["driving"], ref["driving"])
     assert r["sum_tt_q16"] == ref["sum_tt_q16"]
@@ -453,6 +485,7 @@ def test_rccl_allreduce_on_the_sampler_stream(cpm):
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     out = json.loads([l for l in proc.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
     assert out["backend"] == "nccl" and out["world"] == 1
+    assert out["last_kernel"] == cpm.CPM_KERNEL_ZONE_GROUPED and out["status"] == [0] * len(out["status"]) and out["status"], out
     want = {}
     with cpm.Sampler(Z, T) as s:
         s.synth_tables(TABLE_SEED)
@@ -473,7 +506,8 @@ def test_fused_hour_equals_two_launches_per_hour(cpm, O, Z, cpz, T):
     """The grouped path's hour as ONE launch (sampler workgroups + the placing blocks of their drivers, handed over inside the
     launch) against two launches per hour and against the oracle: counts, post-IVP state, travel-time sum.  Also the bail-out:
     with placing blocks that give up waiting at once every fused step comes back flagged, the blocking calls repeat it with two
-    launches, and the context stays there."""
+    launches, and the context stays there.  Every step is pinned to the form it names: the forced mode's form with no step
+    repeated, or -- the bail-out modes -- two launches per hour, at least one repeat and one bail-out counted."""
     C = Z * cpz
     dm, dist = O.synth_datamatrix(Z, T, TABLE_SEED, density=0.3)
     with cpm.Sampler(Z, T) as s:
@@ -489,18 +523,29 @@ def test_fused_hour_equals_two_launches_per_hour(cpm, O, Z, cpz, T):
             s.set_fused(mode, lag)
             s.init_states(C, cpz)
             assert s.get_info(4) == {0: 0, 1: 1, 2: 1, 3: 3, 4: 3, 6: 6, 7: 6, 8: 6}[mode]
-            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"]), (mode, lag)
-            r = s.resample(SIM_SEED, travel=True)
+            bail = mode in (2, 4, 7)
+            # (a bail-out mode: every one-launch attempt gives up and is repeated with two launches per hour, which then stay)
+            pin = dict(fused=mode, form=0, repeats=None, bailouts=None) if bail else dict(fused=mode)
+            repeats0, bailouts0 = s.get_info(cpm.CPM_INFO_STEPS_REPEATED), s.get_info(cpm.CPM_INFO_FUSED_BAILOUTS)
+            with pinned(s, 5, **pin):
+                assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"]), (mode, lag)
+            with pinned(s, 5, **pin):
+                r = s.resample(SIM_SEED, travel=True)
             assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"]), (mode, lag)
             assert r["sum_tt_q16"] == ref["sum_tt_q16"], (mode, lag)
-            r = s.resample(SIM_SEED)                             # (without travel times the last hour runs in its plain form)
+            with pinned(s, 5, **pin):
+                r = s.resample(SIM_SEED)                         # (without travel times the last hour runs in its plain form)
             assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"]), (mode, lag)
             s.set_zone_order(False)                              # (the one-launch hour in zone order instead of largest-first: a hint, the same counts)
-            r = s.resample(SIM_SEED)
+            with pinned(s, 5, **pin):
+                r = s.resample(SIM_SEED)
             assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"]), (mode, lag)
             s.set_zone_order(True)
             assert s.get_info(4) == {0: 0, 1: 1, 2: 0, 3: 3, 4: 0, 6: 6, 7: 0, 8: 6}[mode]   # after a bail-out the context keeps to two launches
             assert s.get_info(2) == 4                            # ... and did not mistake it for an overflow
+            if bail:                                             # ... and the repeat behind the bail-out was counted
+                assert s.get_info(cpm.CPM_INFO_STEPS_REPEATED) - repeats0 >= 1, (mode, lag)
+                assert s.get_info(cpm.CPM_INFO_FUSED_BAILOUTS) - bailouts0 == 1, (mode, lag)
 
 
 @pytest.mark.parametrize("Z,want", [(1536, 0), (3072, 1), (4096, 1), (6144, 0)])
@@ -517,7 +562,10 @@ def test_one_launch_per_hour_only_where_it_pays(cpm, Z, want):
         s.set_fused(1)
         assert s.get_info(4) == 1
         s.set_fused(5)
-        r = s.resample(SIM_SEED)
+        with pinned(s, 0, form=want) as step:
+            r = s.resample(SIM_SEED)
+        if cpm.device_info(0)["cu_count"] == 256:
+            assert step["form"] == want
         assert (r["parking"].sum(axis=0) == Z * cpz).all()
 
 
@@ -546,6 +594,9 @@ def test_two_hip_ranks_on_one_gpu_sum_to_the_single_run(cpm, deal):
         assert p.returncode == 0, so_[-2000:] + se_[-4000:]
     out = json.loads([l for l in outs[0][0].splitlines() if l.startswith("RESULT ")][-1][7:])
     assert out["backend"] == "gloo" and out["world"] == world and sum(out["counts"]) == C and min(out["counts"]) > 0
+    # every rank's counts came from the grouped path with a clean status word (nothing for the caller to repeat)
+    assert out["last_kernel"] == [cpm.CPM_KERNEL_ZONE_GROUPED] * world, out["last_kernel"]
+    assert out["status"] == [[0] * len(out["steps"])] * world, out["status"]
     with cpm.Sampler(Z, T) as s:
         s.synth_tables(TABLE_SEED)
         s.init_states(C, cpz)
@@ -560,8 +611,10 @@ def test_two_hip_ranks_on_one_gpu_sum_to_the_single_run(cpm, deal):
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_extreme_skew_everyone_to_one_zone(cpm, O, kernel):
     """Every row is a point mass on zone 3: after one hour the whole fleet sits in one bucket
-    (one workgroup walks 200k cars; the fused kernel's 16-bit rank overflows and the blocking API
-    falls back by itself).  Counts stay bit-exact."""
+    (one workgroup walks 200k cars; its drivers outgrow the zone's run even at the largest bucket regions) and the blocking API
+    falls back by itself: the grouped attempts are repeated with regions doubled up to 64x the mean, then on the exact layout,
+    which produces the counts -- also for an explicit CPM_KERNEL_ZONE_GROUPED (CPM_INFO_LAST_KERNEL shows it).  Counts stay
+    bit-exact."""
     Z, T, cpz = 64, 24, 3200
     C = Z * cpz
     p_drive = O.synth_p_drive(Z, T, TABLE_SEED)
@@ -573,8 +626,14 @@ def test_extreme_skew_everyone_to_one_zone(cpm, O, kernel):
         s.set_p_drive(p_drive)
         s.set_p_dest(p_dest)
         s.init_states(C, cpz)
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
-        r = s.resample(SIM_SEED)
+        grouped = kernel in (0, 5)
+        with pinned(s, kernel, family=ZONE_LDS if grouped else None, repeats=at_least(1) if grouped else 0,
+                    cap_mult=64 if grouped else 4):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        # AUTO stays on the exact layout; an explicit kernel 5 tries its (grown) regions again, overflows, and is served by kernel 2
+        with pinned(s, kernel, family=ZONE_LDS if grouped else None, repeats=1 if kernel == 5 else 0):
+            r = s.resample(SIM_SEED)
+        assert s.get_info(cpm.CPM_INFO_KERNEL) == {0: ZONE_LDS}.get(kernel, kernel)
     assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
     assert r["parking"][2, 5] > 0.9 * C
 
@@ -597,21 +656,25 @@ def test_fixed_stride_overflow_is_reported_and_auto_demotes_itself(cpm, O):
         counts = torch.zeros(s.counts_words(), dtype=torch.int64, device="cuda:0")
         for kernel in (5,):
             _set_kernel(s, kernel)
-            s.resample_dev(SIM_SEED, counts.data_ptr())
+            with pinned(s, kernel):                              # (the async form reports what it enqueued)
+                s.resample_dev(SIM_SEED, counts.data_ptr())
             s.sync()
             assert int(counts[-1].item()) != 0
             with pytest.raises(RuntimeError):
                 split_counts(counts, Z, T)
         s.set_kernel(2)
-        s.resample_dev(SIM_SEED, counts.data_ptr())
+        with pinned(s, 2):
+            s.resample_dev(SIM_SEED, counts.data_ptr())
         s.sync()
         pk, _, _ = split_counts(counts, Z, T)
         assert (pk.sum(axis=0) == C).all() and pk[2, 1] == C
         # AUTO: first async step is flagged, the blocking call corrects itself, later async steps are clean
         s.set_kernel(0)
-        r = s.resample(SIM_SEED)
+        with pinned(s, 0, family=ZONE_LDS, repeats=at_least(1)):  # grouped attempts discarded, the exact layout's counts returned
+            r = s.resample(SIM_SEED)
         assert (r["parking"].sum(axis=0) == C).all() and r["parking"][2, 1] == C
-        s.resample_dev(SIM_SEED, counts.data_ptr())
+        with pinned(s, 0, family=ZONE_LDS):
+            s.resample_dev(SIM_SEED, counts.data_ptr())
         s.sync()
         assert int(counts[-1].item()) == 0
         pk2, _, _ = split_counts(counts, Z, T)
@@ -621,7 +684,9 @@ def test_fixed_stride_overflow_is_reported_and_auto_demotes_itself(cpm, O):
 def test_run_overflow_of_the_grouped_layout_falls_back(cpm, O):
     """Every car of a zone drives into ONE destination group (a permutation of the groups, so no bucket outgrows its
     region): the zone's fixed-size run of that group (scap = a quarter of the bucket region) overflows as soon as the
-    zone holds more than scap cars.  Async form: status word; blocking form: exact layout, bit-exact counts."""
+    zone holds more than scap cars.  Async form: status word.  Blocking forms: the IVP repeats its overflowed attempt with the
+    regions doubled once; the resample that follows takes the async step's status word (one more doubling) and runs clean on the
+    grouped layout -- bit-exact counts, no demotion to the exact layout."""
     import torch
     Z, T, cpz = 64, 24, 3200
     C = Z * cpz
@@ -639,11 +704,14 @@ def test_run_overflow_of_the_grouped_layout_falls_back(cpm, O):
         s.set_p_dest(p_dest)
         s.init_states(C, cpz)
         counts = torch.zeros(s.counts_words(), dtype=torch.int64, device="cuda:0")
-        s.resample_dev(SIM_SEED, counts.data_ptr())
+        with pinned(s, 5):
+            s.resample_dev(SIM_SEED, counts.data_ptr())
         s.sync()
         assert int(counts[-1].item()) != 0
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
-        r = s.resample(SIM_SEED)
+        with pinned(s, 5, repeats=1, cap_mult=8):               # the blocking IVP repeats its overflowed attempt by itself
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, 5, cap_mult=16):                          # (regions grown for the async step's status word: no repeat)
+            r = s.resample(SIM_SEED)
     assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
 
 
@@ -657,8 +725,11 @@ def test_few_cars_per_zone_uses_the_car_kernel_and_matches(cpm, O):
         s.set_p_drive(p_drive)
         s.set_p_dest(p_dest)
         s.init_states(C, cpz)
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
-        r = s.resample(SIM_SEED)
+        assert auto_family(s) == CAR
+        with pinned(s, 0):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, 0):
+            r = s.resample(SIM_SEED)
     assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
 
 
@@ -769,7 +840,8 @@ def test_refresh_tables_and_lazy_cdf_rows(cpm, O):
                 assert np.array_equal(s.get_cdf_row(o, t), cdf[t - 1, o - 1])
             for kernel in (0, 1, 2, 5):
                 s.set_kernel(kernel)
-                r = s.resample(SIM_SEED)
+                with pinned(s, kernel):
+                    r = s.resample(SIM_SEED)
                 assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"]), (full, kernel)
         assert np.array_equal(r0["parking"], ref["parking"])
 
@@ -927,8 +999,10 @@ def test_grouped_path_with_long_rows(cpm, O, Z, T, cpz):
         s.set_p_drive(p_drive)
         s.set_p_dest(p_dest)
         s.init_states(C, cpz)
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
-        r = s.resample(SIM_SEED)
+        with pinned(s, 5, cap_mult=4):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, 5, cap_mult=4):
+            r = s.resample(SIM_SEED)
         assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
         # the grouped layout really ran (no overflow demotion): the async form reports a clean status
         import torch
@@ -956,12 +1030,15 @@ def test_overflow_is_absorbed_by_growing_the_bucket_regions(cpm, O):
         s.set_p_dest(p_dest)
         s.init_states(C, cpz)
         assert s.get_info(1) == 5 and s.get_info(2) == 4
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
-        r = s.resample(SIM_SEED)
+        with pinned(s, 0, repeats=1, cap_mult=8):               # the overflowed IVP attempt: grown once and repeated
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, 0, cap_mult=8):
+            r = s.resample(SIM_SEED)
         assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
         assert s.get_info(1) == 5 and s.get_info(2) == 8       # grew once, still the grouped layout
         counts = torch.zeros(s.counts_words(), dtype=torch.int64, device="cuda:0")
-        s.resample_dev(SIM_SEED, counts.data_ptr())
+        with pinned(s, 0, cap_mult=8):
+            s.resample_dev(SIM_SEED, counts.data_ptr())
         s.sync()
         assert int(counts[-1].item()) == 0
         from carparkingmaps_amd.distributed import split_counts
@@ -972,8 +1049,9 @@ def test_overflow_is_absorbed_by_growing_the_bucket_regions(cpm, O):
 def test_heavy_buckets_are_split_over_several_workgroups(cpm, O):
     """Skewed destination popularity (the oracle's / the library's Zipf-Mandelbrot tables, bit-identical): a few zones hold many times
     the mean.  The first grouped step walks such a bucket with one workgroup and reports its size; from then on the context launches
-    the heavy kernel with several blocks per zone (CPM_INFO_PARTS > 1).  Counts stay bit-exact on both sides of the switch, for the
-    IVP and for the resample, with and without travel times."""
+    the heavy kernel with several blocks per zone (CPM_INFO_PARTS > 1).  The largest buckets (~17 workgroups' slots) also outgrow the
+    bucket regions in the first IVP, which is repeated with them doubled three times (32x the mean); nothing is repeated after that.
+    Counts stay bit-exact on both sides of the switch, for the IVP and for the resample, with and without travel times."""
     Z, T, cpz, q = 192, 24, 1000, 4
     C = Z * cpz
     p_drive = O.synth_p_drive(Z, T, TABLE_SEED)
@@ -989,19 +1067,23 @@ def test_heavy_buckets_are_split_over_several_workgroups(cpm, O):
         s.set_kernel(5)
         s.init_states(C, cpz)
         assert s.get_info(3) == 1
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, 5, repeats=3, cap_mult=32, parts=at_least(2)):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
         parts_after_ivp = s.get_info(3)
         assert parts_after_ivp > 1                               # the IVP saw the heavy buckets
         for k in range(3):
-            r = s.resample(SIM_SEED, travel=(k == 1))
+            with pinned(s, 5, cap_mult=32, parts=at_least(2)):  # heavy buckets split over workgroups are no overflow: nothing repeated
+                r = s.resample(SIM_SEED, travel=(k == 1))
             assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"]), k
             if k == 1:
                 assert r["sum_tt_q16"] == ref["sum_tt_q16"]
             assert s.get_info(3) >= int(np.ceil(ref["parking"].max() / 1024)) - 1
         # and from a fresh context whose very first step is already split (parts carried over by the IVP above are not needed)
         s.init_states(C, cpz)
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
-        r = s.resample(SIM_SEED)
+        with pinned(s, 5, cap_mult=32):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, 5, cap_mult=32, parts=at_least(2)):
+            r = s.resample(SIM_SEED)
         assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
 
 
@@ -1026,12 +1108,13 @@ def test_async_ivp_is_committed_on_the_tables_it_was_enqueued_with(cpm, O):
             s.set_p_dest(p_dest)
             s.init_states(C, cpz)
             assert s.get_info(2) == 4
-            s.solve_ivp_async(SIM_SEED)
-            if swap in ("p_dest", "both"):
-                s.set_p_dest(flat_dest)
-            if swap in ("p_drive", "both"):
-                s.set_p_drive(flat_drive)
-            assert np.array_equal(s.get_state(), ref["zone0"]), swap
+            with pinned(s, 0, repeats=1, cap_mult=8):
+                s.solve_ivp_async(SIM_SEED)
+                if swap in ("p_dest", "both"):
+                    s.set_p_dest(flat_dest)
+                if swap in ("p_drive", "both"):
+                    s.set_p_drive(flat_drive)
+                assert np.array_equal(s.get_state(), ref["zone0"]), swap
             assert s.get_info(2) == 8            # the first attempt did overflow and was repeated with grown regions
 
 
@@ -1089,9 +1172,11 @@ def test_contiguous_shard_of_an_8_gpu_run_starts_skewed(cpm, O):
         s.set_p_dest(p_dest)
         s.init_states(C, cpz, 0, count)
         assert s.get_info(1) == 5 and s.get_info(2) == 4
-        assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        with pinned(s, 0, repeats=1, cap_mult=8):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
         assert s.get_info(1) == 5 and s.get_info(2) == 8            # grew, did not fall back
-        r = s.resample(SIM_SEED)
+        with pinned(s, 0, cap_mult=8):
+            r = s.resample(SIM_SEED)
         assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
         assert (r["parking"].sum(axis=0) == count).all()
 
@@ -1099,7 +1184,9 @@ def test_contiguous_shard_of_an_8_gpu_run_starts_skewed(cpm, O):
 @pytest.mark.parametrize("seed", range(24))
 def test_randomized_small_configurations(cpm, O, seed):
     """Random small problems through the grouped path and AUTO: odd zone counts, T from 1 to 24, one car to hundreds per zone,
-    sparse rows, all-zero rows, single-destination rows, unreachable zones, p_drive of 0 / 1 / NaN.  Bit-exact against the oracle."""
+    sparse rows, all-zero rows, single-destination rows, unreachable zones, p_drive of 0 / 1 / NaN.  Bit-exact against the oracle,
+    and produced by the kernel named for every seed: kernel 5 by the grouped path (grown regions only as counted repeats, one per
+    doubling), AUTO by the family its rule picks."""
     rng = np.random.default_rng(1000 + seed)
     Z = int(rng.integers(2, 150))
     T = int(rng.choice([1, 2, 5, 24]))
@@ -1125,15 +1212,23 @@ def test_randomized_small_configurations(cpm, O, seed):
             if tot > 0:
                 p_dest[o, :, t] = w[o, :, t] / tot
     ref = O.fast_run(p_drive, O.build_cdf(p_dest), C, SIM_SEED + seed, _zone0(C, cpz))
+    forms = []
     for kernel in (5, 0):
         with cpm.Sampler(Z, T) as s:
             s.set_kernel(kernel)
             s.set_p_drive(p_drive)
             s.set_p_dest(p_dest)
             s.init_states(C, cpz)
-            assert np.array_equal(s.solve_ivp(SIM_SEED + seed), ref["zone0"]), (kernel, Z, T, cpz)
-            r = s.resample(SIM_SEED + seed)
+            with pinned(s, kernel, repeats=None) as ivp:
+                assert np.array_equal(s.solve_ivp(SIM_SEED + seed), ref["zone0"]), (kernel, Z, T, cpz)
+            with pinned(s, kernel, repeats=None) as step:
+                r = s.resample(SIM_SEED + seed)
             assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"]), (kernel, Z, T, cpz)
+            # every repeat is a doubling of the bucket regions (no bail-out, no demotion: the families are pinned above)
+            cap, repeats = s.get_info(cpm.CPM_INFO_CAP_MULT), s.get_info(cpm.CPM_INFO_STEPS_REPEATED)
+            assert cap == 4 << repeats, (kernel, Z, T, cpz, cap, repeats)
+            forms.append(f"kernel {kernel}: ivp {ivp['kernel']}/{ivp['form']} resample {step['kernel']}/{step['form']} repeats {repeats}")
+    print(f"seed {seed} Z={Z} T={T} cpz={cpz}: " + "; ".join(forms))
 
 
 def test_sparse_dataset_tables_equal_the_dense_ones(cpm, O):
@@ -1142,7 +1237,10 @@ def test_sparse_dataset_tables_equal_the_dense_ones(cpm, O):
     (src/createpdrive.jl:10-33, src/createpdestin.jl:10-46) and its run on them: the tables a caller gets back, the f64 CDF rows built
     on demand, the categorical draw on, below and above every breakpoint (ties walk the row's cells), the post-IVP state, counts and
     travel-time sum -- for the Int exponent of main.jl:38 and a Float64 one, with an origin without data, a (mean 0, std > 0) cell
-    and Z not a multiple of 32."""
+    and Z not a multiple of 32.  One context serves every (e_dest, kernel) pass, and its bucket regions only ever grow: the first
+    travel resample (e_dest = 2, AUTO) meets a run of one destination group longer than the 288 entries of regions at the
+    1,024-slot floor (4x, 8x and 16x the mean of 60 cars) and is repeated three times, up to 32x (480 entries); every other step,
+    the IVPs included, runs on the regions as they are, without a repeat."""
     Z, T, cpz = 700, 24, 60
     C = Z * cpz
     dm, dist = O.synth_datamatrix(Z, T, TABLE_SEED, density=0.06)
@@ -1179,14 +1277,18 @@ def test_sparse_dataset_tables_equal_the_dense_ones(cpm, O):
             for kernel in (0, 2, 5):
                 s.set_kernel(kernel)
                 s.init_states(C, cpz)
-                assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"]), (e_dest, kernel)
-                r = s.resample(SIM_SEED, travel=True)
+                first = e_dest == 2 and kernel == 0
+                with pinned(s, kernel, cap_mult=4 if first else 32):
+                    assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"]), (e_dest, kernel)
+                with pinned(s, kernel, repeats=3 if first else 0, cap_mult=32):
+                    r = s.resample(SIM_SEED, travel=True)
                 assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"]), (e_dest, kernel)
                 assert r["sum_tt_q16"] == ref["sum_tt_q16"], (e_dest, kernel)
             s.set_kernel(0)
             s.refresh_tables()
             assert s.get_info(6) > 0
-            r = s.resample(SIM_SEED)
+            with pinned(s, 0, cap_mult=32):
+                r = s.resample(SIM_SEED)
             assert np.array_equal(r["parking"], ref["parking"])
         # a new datamatrix behind installed sparse tables: they stay whole (a tie walks the TABLE's cells, not the new dataset's)
         dm2, dist2 = O.synth_datamatrix(Z, T, TABLE_SEED + 1, density=0.06)
@@ -1197,3 +1299,57 @@ def test_sparse_dataset_tables_equal_the_dense_ones(cpm, O):
         t53 = np.floor(np.minimum(cdf, 1.0 - 2.0 ** -53) * 2.0 ** 53).astype(np.uint64)
         got, n_exact = s.debug_categorical(100, 12, t53)
         assert np.array_equal(got, _ref_categorical(cdf, t53)) and n_exact > 0
+
+
+def test_the_form_pin_catches_a_silent_repeat_and_a_demotion(cpm, O):
+    """tests/product_form.py's pin against the two repairs the blocking calls make without telling the caller, both reached by the
+    ordinary status-word route: a one-launch hour whose placing blocks give up waiting at once (CPM_OPT_FUSED = 2, the library's
+    bail-out mode for tests) is repeated with two launches per hour, and an explicit CPM_KERNEL_ZONE_GROUPED whose regions cannot
+    hold the everyone-to-zone-3 fleet is demoted to the exact layout.  The counts equal the oracle's both times; a pin that
+    expected the named form must fail all the same."""
+    Z, T, cpz = 130, 6, 1100
+    C = Z * cpz
+    dm, dist = O.synth_datamatrix(Z, T, TABLE_SEED, density=0.3)
+    with cpm.Sampler(Z, T) as s:
+        s.set_datamatrix(dm, dist)
+        p_drive = s.build_p_drive(0.1, 0.9, 0.5)
+        p_dest = s.build_p_dest(2)
+        ref = O.fast_run(p_drive, O.build_cdf(p_dest), C, SIM_SEED, _zone0(C, cpz))
+        s.set_kernel(5)
+        s.set_fused(0)
+        s.init_states(C, cpz)
+        with pinned(s, 5, fused=0):
+            assert np.array_equal(s.solve_ivp(SIM_SEED), ref["zone0"])
+        s.set_fused(2)
+        with pytest.raises(AssertionError, match="hour form 0"):
+            with pinned(s, 5, fused=1) as step:
+                r = s.resample(SIM_SEED)
+        assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
+        assert step["kernel"] == GROUPED and step["form"] == 0 and step["step_repeats"] >= 1 and step["step_bailouts"] == 1, step
+        with pytest.raises(AssertionError, match="repeated attempts"):   # (the repeat alone is caught too)
+            with pinned(s, 5, fused=1, form=0, bailouts=None):
+                s.set_fused(2)
+                r = s.resample(SIM_SEED)
+        assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
+
+    Z, T, cpz = 64, 24, 3200
+    C = Z * cpz
+    p_drive = O.synth_p_drive(Z, T, TABLE_SEED)
+    p_dest = np.zeros((Z, Z, T), order="F")
+    p_dest[:, 2, :] = 1.0
+    ref = O.fast_run(p_drive, O.build_cdf(p_dest), C, SIM_SEED, _zone0(C, cpz))
+    with cpm.Sampler(Z, T) as s:
+        s.set_kernel(5)
+        s.set_p_drive(p_drive)
+        s.set_p_dest(p_dest)
+        s.init_states(C, cpz)
+        with pytest.raises(AssertionError, match="family 2 produced the results, expected 5"):
+            with pinned(s, 5) as ivp:
+                init = s.solve_ivp(SIM_SEED)
+        assert np.array_equal(init, ref["zone0"])
+        with pytest.raises(AssertionError, match="family 2 produced the results, expected 5"):
+            with pinned(s, 5) as step:
+                r = s.resample(SIM_SEED)
+        assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
+        assert s.get_info(cpm.CPM_INFO_KERNEL) == GROUPED                   # the prediction still names the grouped path ...
+        assert ivp["step_repeats"] >= 1 and step["step_repeats"] == 1, (ivp, step)   # ... the record shows the repair

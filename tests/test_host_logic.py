@@ -185,3 +185,60 @@ def test_geojson_duplicate_zone_ids_keep_the_old_tail(cpm):
     assert lons[:4] == [145.5, 145.5, 145.6, 145.6] and lats[:4] == [-38.5, -38.5, -38.6, -38.6]
     assert lons[4:] == [p[0] for p in long_ring for _ in (0, 1)][4:]
     assert zones[2][0] == [145.5, 145.5, 145.6, 145.6]
+
+
+class _ScriptedSampler:
+    """Stands in for a Sampler in front of tests/product_form.py: cpm_get_info answers from a dict, and `step` applies what a
+    library step would have recorded."""
+
+    def __init__(self, Z, cars, fused_prediction=1):
+        self.Z, self.car_count = Z, cars
+        self.info = {1: 5, 2: 4, 3: 1, 4: fused_prediction, 5: 0, 6: 0, 7: 0, 8: -1, 9: 0}
+
+    def get_info(self, what):
+        return self.info[what]
+
+    def last_step(self):
+        i = self.info
+        return dict(kernel=i[7], form=i[8], repeats=i[9], cap_mult=i[2], parts=i[3], bailouts=i[5])
+
+    def step(self, kernel, form, repeats=0, bailouts=0, cap_mult=None):
+        self.info[7], self.info[8] = kernel, form
+        self.info[9] += repeats
+        self.info[5] += bailouts
+        if cap_mult is not None:
+            self.info[2] = cap_mult
+
+
+def test_form_pin_fails_on_every_silent_repair():
+    """The pin passes on the step it names and fails on each repair the blocking calls can make behind the counts' back."""
+    from product_form import at_least, auto_family, pinned
+    s = _ScriptedSampler(Z=100, cars=100 * 64)
+    with pinned(s, 5, cap_mult=4):
+        s.step(5, 1)                                  # the named form, predicted one launch per hour
+    with pytest.raises(AssertionError, match="family 2 produced the results, expected 5"):
+        with pinned(s, 5):
+            s.step(2, -1, repeats=1)                  # demoted to the exact layout
+    with pytest.raises(AssertionError, match="hour form 0, CPM_INFO_FUSED predicted 1"):
+        with pinned(s, 5):
+            s.step(5, 0, repeats=1, bailouts=1)       # a bail-out repeated with two launches per hour
+    with pytest.raises(AssertionError, match="repeated attempts"):
+        with pinned(s, 5):
+            s.step(5, 1, repeats=1, cap_mult=8)       # grown and repeated
+    with pytest.raises(AssertionError, match="CAP_MULT 8"):
+        with pinned(s, 5, repeats=1, cap_mult=4):
+            s.step(5, 1, repeats=1)
+    with pinned(s, 5, repeats=at_least(1), cap_mult=at_least(8)):
+        s.step(5, 1, repeats=2, cap_mult=16)
+    with pytest.raises(AssertionError, match="fused mode 3 expects 3"):
+        with pinned(s, 5, fused=3):
+            s.step(5, 1)                              # a forced mode must run its own form, whatever was predicted
+    with pytest.raises(AssertionError, match="hour form 1 reported for family 1"):
+        with pinned(s, 1):
+            s.step(1, 1)
+    # AUTO: the library's rule restated -- fewer than 32 of the context's cars per zone -> the per-car kernel, else grouped
+    assert auto_family(_ScriptedSampler(Z=100, cars=3199)) == 1 and auto_family(_ScriptedSampler(Z=100, cars=3200)) == 5
+    few = _ScriptedSampler(Z=100, cars=500)
+    with pytest.raises(AssertionError, match="family 5 produced the results, expected 1"):
+        with pinned(few, 0):
+            few.step(5, 0)
