@@ -23,6 +23,9 @@ SYMBOLS = [
     "cpm_init_states_strided", "cpm_synth_tables_skewed", "cpm_synth_datamatrix", "cpm_refresh_tables",
 ]
 
+# every symbol include/cpm_batch.h declares (checked by tests/test_batch_host.py); kept apart: SYMBOLS is cpm.h's list
+BATCH_SYMBOLS = ["cpm_set_p_drive_batch", "cpm_build_p_drive_batch", "cpm_get_p_drive_batch", "cpm_resample_batch", "cpm_resample_batch_dev"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -31,6 +34,11 @@ CPM_OPT_KERNEL, CPM_OPT_PROFILE, CPM_OPT_PROFILE_KERNEL, CPM_OPT_FUSED, CPM_OPT_
 CPM_INFO_KERNEL, CPM_INFO_CAP_MULT, CPM_INFO_PARTS, CPM_INFO_FUSED, CPM_INFO_FUSED_BAILOUTS, CPM_INFO_SPARSE_TABLES = 1, 2, 3, 4, 5, 6
 # ... and what its most recent step ran
 CPM_INFO_LAST_KERNEL, CPM_INFO_LAST_FORM, CPM_INFO_STEPS_REPEATED = 7, 8, 9
+# include/cpm_batch.h: the installed batch tables' fleets, the fleets the batched kernels produced in the most recent batch step, and the
+# CPM_INFO_LAST_FORM of such a step
+CPM_MAX_BATCH = 64
+CPM_INFO_BATCH, CPM_INFO_LAST_BATCH_FLEETS = 16, 17
+CPM_FORM_BATCH = 10
 
 _lib = None
 
@@ -45,6 +53,7 @@ def build(force=False):
     """Compile libcpm_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")) or f == "Makefile"]
     srcs.append(os.path.join(_HERE, "..", "include", "cpm.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_batch.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -111,7 +120,12 @@ def load():
     L.cpm_get_distance.argtypes = [vp, vp]
     L.cpm_set_distance.argtypes = [vp, vp]
     L.cpm_get_info.argtypes = [vp, i32, C.POINTER(i64)]
-    for name in SYMBOLS:
+    L.cpm_set_p_drive_batch.argtypes = [vp, i32, vp]
+    L.cpm_build_p_drive_batch.argtypes = [vp, i32, vp, vp, vp]
+    L.cpm_get_p_drive_batch.argtypes = [vp, vp]
+    L.cpm_resample_batch.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.cpm_resample_batch_dev.argtypes = [vp, vp, u32, vp]
+    for name in SYMBOLS + BATCH_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

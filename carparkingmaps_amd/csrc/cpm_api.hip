@@ -16,6 +16,7 @@
 #include "cpm_tables.h"
 #include "cpm_exact.h"
 #include "cpm_grouped.h"
+#include "cpm_batch.h"
 #include "cpm_dataset.h"
 #include "cpm_ingest.h"
 
@@ -151,6 +152,21 @@ struct cpm_ctx {
     int last_kernel = 0;
     int last_form = -1;
     int64_t steps_repeated = 0;
+    int last_batch_fleets = 0;          // CPM_INFO_LAST_BATCH_FLEETS: 0 after every step that is not a batch step
+    // batch tables and workspace (include/cpm_batch.h, cpm_batch.h)
+    int batch_B = 0, batch_alloc = 0;
+    double *d_pdrive_b = nullptr;       // [B][T][Z] the fleets' p_drive tables
+    long long *d_thr_b = nullptr;       // [B][T][Z] their Bernoulli thresholds
+    cpm::BatchWork zb;
+    int64_t *d_bcounts = nullptr;       // [B][2*T*Z + 2] the blocking batch call's count tensors, and their pinned twin
+    int64_t *h_bcounts = nullptr;
+    int bcounts_cap = 0;
+    // the asynchronous batch step's status words, ORed into one word and copied to pinned memory behind the step; looked at, without
+    // waiting, when the next batch step is enqueued (as status_ev / h_status for the single path)
+    unsigned long long *d_bstatus = nullptr;
+    unsigned long long *h_bstatus = nullptr;
+    hipEvent_t bstatus_ev = nullptr;
+    bool bstatus_pending = false;
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -612,6 +628,28 @@ bool absorb_status(cpm_ctx *c, long long st)
     return bailed || grown;
 }
 
+// The travel tables of the grouped path's travel kernel, once per datamatrix: the travel rows of its compact rows (cpm_dataset.h) ...
+int32_t ensure_travel_tables(cpm_ctx *c)
+{
+    if (!c->tt_valid) {
+        int32_t rc_ds = ensure_dataset(c);
+        if (rc_ds != CPM_OK) return rc_ds;
+    }
+    if (!c->tt_valid) {  // ... or, datasets those do not take: sparse rows for LDS, or -- rows too large -- the dense table
+        int32_t rc_tts = build_sparse_travel_rows(c);
+        if (rc_tts != CPM_OK) return rc_tts;
+        if (!c->tts_valid) {
+            const size_t cells = static_cast<size_t>(c->Z) * c->Z * c->T;
+            if (!c->d_tt) HIP_TRY(hipMalloc(&c->d_tt, sizeof(double2) * cells));
+            hipLaunchKernelGGL(cpm::k_build_travel_table, dim3(nblk(c->Z, cpm::kTtTile), nblk(c->Z, cpm::kTtTile), static_cast<unsigned>(c->T)),
+                               dim3(cpm::kTtTile * 8), 0, c->stream, c->d_dm, c->d_tt, static_cast<int>(c->Z), static_cast<int>(c->T));
+            HIP_TRY(hipGetLastError());
+        }
+        c->tt_valid = true;
+    }
+    return CPM_OK;
+}
+
 int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts)
 {
     if (!c->have_pdrive || !c->have_cdf) return fail(CPM_ERR_STATE, "resample: p_drive / p_dest not set");
@@ -630,6 +668,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     }
     const int kernel = pick_kernel(c);
     c->last_kernel = kernel;  // (the family this call enqueues; the grouped path's form is recorded behind its run)
+    c->last_batch_fleets = 0;
     c->last_form = kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
     if (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED)  // (the grouped path zeroes the count tensor with its other counters, in one launch)
         HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * nwords, c->stream));
@@ -638,21 +677,9 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     if (kernel == CPM_KERNEL_ZONE_GROUPED) {
         if (!grouped_fits(c, c->zg.cap_mult))
             return fail(CPM_ERR_ARG, "CPM_KERNEL_ZONE_GROUPED does not fit this problem (use CPM_KERNEL_ZONE_LDS or CPM_KERNEL_CAR)");
-        if (travel && !c->tt_valid) {  // the travel rows of the current datamatrix, once: with its compact rows (cpm_dataset.h) ...
-            int32_t rc_ds = ensure_dataset(c);
-            if (rc_ds != CPM_OK) return rc_ds;
-        }
-        if (travel && !c->tt_valid) {  // ... or, datasets those do not take: sparse rows for LDS, or -- rows too large -- the dense table
-            int32_t rc_tts = build_sparse_travel_rows(c);
-            if (rc_tts != CPM_OK) return rc_tts;
-            if (!c->tts_valid) {
-                const size_t cells = static_cast<size_t>(c->Z) * c->Z * c->T;
-                if (!c->d_tt) HIP_TRY(hipMalloc(&c->d_tt, sizeof(double2) * cells));
-                hipLaunchKernelGGL(cpm::k_build_travel_table, dim3(nblk(c->Z, cpm::kTtTile), nblk(c->Z, cpm::kTtTile), static_cast<unsigned>(c->T)),
-                                   dim3(cpm::kTtTile * 8), 0, c->stream, c->d_dm, c->d_tt, static_cast<int>(c->Z), static_cast<int>(c->T));
-                HIP_TRY(hipGetLastError());
-            }
-            c->tt_valid = true;
+        if (travel) {
+            int32_t rc_tt = ensure_travel_tables(c);
+            if (rc_tt != CPM_OK) return rc_tt;
         }
         int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, travel, d_counts, c->cu_count,
                                       [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error);
@@ -697,6 +724,7 @@ int32_t ivp_exact(cpm_ctx *c, uint64_t seed)
     }
     const bool exact = pick_kernel(c) != CPM_KERNEL_CAR && cpm::exact_path_fits(static_cast<int>(c->Z));
     c->last_kernel = exact ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
+    c->last_batch_fleets = 0;
     c->last_form = -1;
     if (exact) {
         return cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
@@ -715,6 +743,7 @@ int32_t ivp_exact(cpm_ctx *c, uint64_t seed)
 int32_t ivp_grouped(cpm_ctx *c, uint64_t seed)
 {
     c->zx.buckets0_valid = false;  // the current state's grouped buckets may be cached (zg); everything else is stale once the IVP is committed
+    c->zb.buckets0_valid = false;
     int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, false, c->d_counts, c->cu_count,
                                   [](int) {}, [](int) {}, g_last_error, true, c->d_ztmp);
     if (rc != CPM_OK) return rc;
@@ -737,6 +766,7 @@ int32_t finish_ivp(cpm_ctx *c)
         std::swap(c->d_zone0, c->d_ztmp);
         c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
         c->last_form = c->ivp_form;
+        c->last_batch_fleets = 0;
         HIP_TRY(cpm::grouped_commit_ivp(c->zg, c->stream));
         return CPM_OK;
     };
@@ -756,6 +786,7 @@ int32_t finish_ivp(cpm_ctx *c)
     if (c->kernel == CPM_KERNEL_AUTO) c->grouped_overflowed = true;
     c->zx.buckets0_valid = false;
     c->zg.buckets0_valid = false;
+    c->zb.buckets0_valid = false;
     return ivp_exact(c, c->ivp_seed);
 }
 
@@ -768,6 +799,7 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
     if (c->n == 0) {  // (nothing to run: the record names the family all the same)
         c->last_kernel = pick_kernel(c);
         c->last_form = c->last_kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
+        c->last_batch_fleets = 0;
         return CPM_OK;
     }
     if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && grouped_fits(c, c->zg.cap_mult)) {
@@ -779,7 +811,159 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
     }
     c->zx.buckets0_valid = false;
     c->zg.buckets0_valid = false;
+    c->zb.buckets0_valid = false;
     return ivp_exact(c, seed);
+}
+
+// The blocking resample: the count tensor of a valid step in c->h_counts (c->d_counts, status word included).  Leaves c->kernel
+// changed when it had to fall back to a layout that cannot overflow: the caller restores it.
+int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags)
+{
+    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts);
+    const size_t zt = static_cast<size_t>(c->Z * c->T), nwords = 2 * zt + 2;
+    auto fetch = [&]() -> int32_t {  // the count tensor, Σ time and the status word: one copy into pinned memory, one wait
+        HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, sizeof(int64_t) * nwords, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->status_pending) c->zg.set_parts(static_cast<uint32_t>(c->h_status[1]), static_cast<uint32_t>(c->h_status[1] >> 32));  // (how the next grouped step is launched)
+        c->status_pending = false;  // this step's status word is dealt with here: resample_enqueue must not grow the regions for it again
+        return CPM_OK;
+    };
+    if (rc == CPM_OK) rc = fetch();
+    // a bucket or a run outgrew its region (or a block of a one-launch form gave up waiting): again with twice the regions while the
+    // problem still fits (two launches per hour after a bail-out) ...  (each discarded attempt: CPM_INFO_STEPS_REPEATED)
+    while (rc == CPM_OK && c->h_counts[nwords - 1] != 0 && pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && absorb_status(c, c->h_counts[nwords - 1])) {
+        ++c->steps_repeated;
+        rc = resample_enqueue(c, seed, flags, c->d_counts);
+        if (rc == CPM_OK) rc = fetch();
+    }
+    if (rc == CPM_OK && c->h_counts[nwords - 1] != 0) {  // ... else on a layout that cannot overflow
+        ++c->steps_repeated;
+        if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED) c->grouped_overflowed = true;
+        c->kernel = cpm::exact_path_fits(static_cast<int>(c->Z)) ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
+        rc = resample_enqueue(c, seed, flags, c->d_counts);
+        if (rc == CPM_OK) rc = fetch();
+    }
+    return rc;
+}
+
+// mean_sum of createpdrive (src/createpdrive.jl:10-21), once per datamatrix / distance matrix: from the dataset's compact rows, or the
+// Z x Z x T pass over the datamatrix
+int32_t ensure_pdrive_mean(cpm_ctx *c)
+{
+    if (!c->d_pdrive_mean) HIP_TRY(hipMalloc(&c->d_pdrive_mean, sizeof(double) * c->Z * c->T));
+    if (c->pdrive_mean_valid) return CPM_OK;
+    int32_t rc_ds = ensure_dataset(c);
+    if (rc_ds != CPM_OK) return rc_ds;
+    if (c->ds_ok) {
+        hipLaunchKernelGGL(cpm::k_ds_pdrive, dim3(cpm::ds_grid(c->T * c->Z)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_ds_cells, c->d_ds_cnt,
+                           cpm::kDsCap, c->T * c->Z, static_cast<int>(c->Z), c->d_dist, c->d_pdrive_mean);
+    } else {
+        dim3 grid(nblk(c->Z, 64), static_cast<unsigned>(c->T));
+        hipLaunchKernelGGL(cpm::k_pdrive_mean, grid, dim3(64), 0, c->stream, c->d_dm, c->d_dist, c->d_pdrive_mean, static_cast<int>(c->Z));
+    }
+    HIP_TRY(hipGetLastError());
+    c->pdrive_mean_valid = true;
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ batch (include/cpm_batch.h)
+int32_t ensure_batch_tables(cpm_ctx *c, int B)
+{
+    if (c->batch_alloc >= B && c->d_pdrive_b) return CPM_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the tables in use by steps in flight are replaced)
+    dfree(c->d_pdrive_b);
+    dfree(c->d_thr_b);
+    c->batch_alloc = 0;
+    c->batch_B = 0;
+    const size_t cells = static_cast<size_t>(B) * c->T * c->Z;
+    HIP_TRY(hipMalloc(&c->d_pdrive_b, sizeof(double) * cells));
+    HIP_TRY(hipMalloc(&c->d_thr_b, sizeof(long long) * cells));
+    c->batch_alloc = B;
+    return CPM_OK;
+}
+
+// A fleet's table in place of the context's own p_drive for the single-fleet step; the context's table, its flag and its kernel
+// choice are back when the object goes, on every path.
+struct FleetTable {
+    cpm_ctx *c;
+    double *pdrive;
+    long long *thr;
+    bool have;
+    int kernel;
+    explicit FleetTable(cpm_ctx *c_) : c(c_), pdrive(c_->d_pdrive), thr(c_->d_thr), have(c_->have_pdrive), kernel(c_->kernel) {}
+    void use(int b)
+    {
+        const size_t off = static_cast<size_t>(b) * c->T * c->Z;
+        c->d_pdrive = c->d_pdrive_b + off;
+        c->d_thr = c->d_thr_b + off;
+        c->have_pdrive = true;
+        c->kernel = kernel;
+    }
+    ~FleetTable()
+    {
+        c->d_pdrive = pdrive;
+        c->d_thr = thr;
+        c->have_pdrive = have;
+        c->kernel = kernel;
+    }
+};
+
+int32_t batch_ready(cpm_ctx *c, const uint64_t *seeds, uint32_t flags)
+{
+    if (!seeds) return fail(CPM_ERR_ARG, "resample_batch: null seeds");
+    if (c->batch_B < 1) return fail(CPM_ERR_STATE, "resample_batch: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
+    if (!c->have_cdf) return fail(CPM_ERR_STATE, "resample_batch: p_dest not set");
+    if (!c->have_state) return fail(CPM_ERR_STATE, "resample_batch: no car state (cpm_init_states / cpm_set_state)");
+    if ((flags & CPM_FLAG_TRAVEL) && !c->have_dm()) return fail(CPM_ERR_STATE, "CPM_FLAG_TRAVEL needs cpm_set_datamatrix");
+    return finish_ivp(c);
+}
+
+// After an overflow of the batch's regions: twice the regions while the problem still fits (grow_grouped's rule, for the batch's own
+// cap_mult); the next run re-buckets the state.  false: no room to grow.
+bool grow_batch(cpm_ctx *c)
+{
+    const int next = c->zb.cap_mult * 2;
+    if (next > cpm::kMaxCapMult || !cpm::grouped_path_fits(c->n, static_cast<int>(c->Z), next)) return false;
+    c->zb.cap_mult = next;
+    c->zb.buckets0_valid = false;
+    return true;
+}
+
+// what the last asynchronous batch step's status words ask of the batch, once that step has drained (no wait): a bucket or a run of a
+// fleet outgrew its region -> twice the regions for the steps that follow (that step's fleets are the caller's to repeat)
+void absorb_batch_status(cpm_ctx *c)
+{
+    if (!c->bstatus_pending || hipEventQuery(c->bstatus_ev) != hipSuccess) return;
+    c->bstatus_pending = false;
+    if (*c->h_bstatus != 0) (void)grow_batch(c);
+}
+
+// the batched kernels run when the single path would take the grouped family for this problem (asked with a fleet's table in place)
+// and the batch's own regions fit
+bool batch_grouped(const cpm_ctx *c)
+{
+    return c->n > 0 && pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && grouped_fits(c, c->zg.cap_mult) && cpm::grouped_path_fits(c->n, static_cast<int>(c->Z), c->zb.cap_mult);
+}
+
+// fleets k of `tabs` (their tables, seeds, count tensors d_counts + outs[k] * nwords) on the batched kernels, in sub-batches
+int32_t batch_enqueue(cpm_ctx *c, const std::vector<uint64_t> &seeds, const std::vector<int32_t> &tabs, const std::vector<int32_t> &outs, uint32_t flags,
+                      int64_t *d_counts)
+{
+    const bool travel = (flags & CPM_FLAG_TRAVEL) != 0;
+    if (travel) {
+        int32_t rc_tt = ensure_travel_tables(c);
+        if (rc_tt != CPM_OK) return rc_tt;
+    }
+    const int nfl = static_cast<int>(tabs.size());
+    const int sub = cpm::BatchWork::sub_batch(c->n, static_cast<int>(c->Z), static_cast<int>(c->T), c->zb.cap_mult, nfl);
+    const cpm::GroupedTables tb = grouped_tables(c);
+    for (int k0 = 0; k0 < nfl; k0 += sub) {
+        const int nf = std::min(sub, nfl - k0);
+        int32_t rc = cpm::batch_run(c->zb, c->stream, tb, c->n, c->cars, c->d_zone0, c->d_thr_b, seeds.data() + k0, tabs.data() + k0, outs.data() + k0, nf,
+                                    travel, d_counts, c->cu_count, g_last_error);
+        if (rc != CPM_OK) return rc;
+    }
+    return CPM_OK;
 }
 
 }  // namespace
@@ -872,6 +1056,14 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_dm);
     dfree(c->d_dist);
     dfree(c->d_pdrive_mean);
+    dfree(c->d_pdrive_b);
+    dfree(c->d_thr_b);
+    dfree(c->d_bcounts);
+    if (c->h_bcounts) (void)hipHostFree(c->h_bcounts);
+    dfree(c->d_bstatus);
+    if (c->h_bstatus) (void)hipHostFree(c->h_bstatus);
+    if (c->bstatus_ev) (void)hipEventDestroy(c->bstatus_ev);
+    c->zb.release();
     dfree(c->d_ds_cells);
     dfree(c->d_ds_cnt);
     dfree(c->d_sp);
@@ -979,6 +1171,17 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
             if (rc_ivp != CPM_OK) return rc_ivp;
         }
         *value_out = what == CPM_INFO_LAST_KERNEL ? c->last_kernel : what == CPM_INFO_LAST_FORM ? c->last_form : c->steps_repeated;
+        return CPM_OK;
+    case CPM_INFO_BATCH:
+        *value_out = c->batch_B;
+        return CPM_OK;
+    case CPM_INFO_LAST_BATCH_FLEETS:
+        if (c->ivp_pending) {
+            HIP_TRY(hipSetDevice(c->device));
+            int32_t rc_ivp = finish_ivp(c);
+            if (rc_ivp != CPM_OK) return rc_ivp;
+        }
+        *value_out = c->last_batch_fleets;
         return CPM_OK;
     default:
         return fail(CPM_ERR_ARG, "unknown info %d", what);
@@ -1261,19 +1464,9 @@ int32_t cpm_build_p_drive(cpm_ctx *c, double p_min, double p_max, double e_drive
     if (!c->have_dm()) return fail(CPM_ERR_STATE, "build_p_drive: datamatrix and distance matrix first (cpm_set_datamatrix, or cpm_createdatamatrix_* + cpm_set_distance_from_centroids)");
     size_t bytes = sizeof(double) * c->Z * c->T;
     if (!c->d_pdrive) HIP_TRY(hipMalloc(&c->d_pdrive, bytes));
-    if (!c->d_pdrive_mean) HIP_TRY(hipMalloc(&c->d_pdrive_mean, bytes));
-    if (!c->pdrive_mean_valid) {  // once per datamatrix / distance matrix: from the dataset's compact rows, or the Z x Z x T pass over the datamatrix
-        int32_t rc_ds = ensure_dataset(c);
-        if (rc_ds != CPM_OK) return rc_ds;
-        if (c->ds_ok) {
-            hipLaunchKernelGGL(cpm::k_ds_pdrive, dim3(cpm::ds_grid(c->T * c->Z)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_ds_cells, c->d_ds_cnt,
-                               cpm::kDsCap, c->T * c->Z, static_cast<int>(c->Z), c->d_dist, c->d_pdrive_mean);
-        } else {
-            dim3 grid(nblk(c->Z, 64), static_cast<unsigned>(c->T));
-            hipLaunchKernelGGL(cpm::k_pdrive_mean, grid, dim3(64), 0, c->stream, c->d_dm, c->d_dist, c->d_pdrive_mean, static_cast<int>(c->Z));
-        }
-        HIP_TRY(hipGetLastError());
-        c->pdrive_mean_valid = true;
+    {
+        int32_t rc_mean = ensure_pdrive_mean(c);
+        if (rc_mean != CPM_OK) return rc_mean;
     }
     if (!c->d_thr) HIP_TRY(hipMalloc(&c->d_thr, sizeof(long long) * static_cast<size_t>(c->Z * c->T)));
     hipLaunchKernelGGL(cpm::k_pdrive_final, dim3(nblk(c->Z, 64), static_cast<unsigned>(c->T)), dim3(64), 0, c->stream, c->d_pdrive_mean,
@@ -1455,6 +1648,7 @@ int32_t cpm_init_states_strided(cpm_ctx *c, int64_t C_total, int64_t cars_per_zo
     c->cars = cpm::CarIndex{car_first, static_cast<uint32_t>(car_stride)};
     c->zx.buckets0_valid = false;
     c->zg.buckets0_valid = false;
+    c->zb.buckets0_valid = false;
     if (car_count > 0) {
         hipLaunchKernelGGL(cpm::k_init_states, dim3(nblk(car_count, 256)), dim3(256), 0, c->stream, c->d_zone0, c->cars, car_count, cars_per_zone);
         HIP_TRY(hipGetLastError());
@@ -1478,6 +1672,7 @@ int32_t cpm_set_state(cpm_ctx *c, const int64_t *zones)
     }
     c->zx.buckets0_valid = false;
     c->zg.buckets0_valid = false;
+    c->zb.buckets0_valid = false;
     if (c->n == 0) return CPM_OK;
     if (!zones) return fail(CPM_ERR_ARG, "null zones");
     int64_t *d_z = nullptr;
@@ -1557,31 +1752,9 @@ int32_t cpm_resample(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking
         if (rc_ivp != CPM_OK) return rc_ivp;
     }
     if (compat) c->kernel = CPM_KERNEL_CAR;  // the per-hour records of every car are kept by this path
-    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts);
-    const size_t zt = static_cast<size_t>(c->Z * c->T), nwords = 2 * zt + 2;
-    auto fetch = [&]() -> int32_t {  // the count tensor, Σ time and the status word: one copy into pinned memory, one wait
-        HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, sizeof(int64_t) * nwords, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->status_pending) c->zg.set_parts(static_cast<uint32_t>(c->h_status[1]), static_cast<uint32_t>(c->h_status[1] >> 32));  // (how the next grouped step is launched)
-        c->status_pending = false;  // this step's status word is dealt with here: resample_enqueue must not grow the regions for it again
-        return CPM_OK;
-    };
-    if (rc == CPM_OK) rc = fetch();
-    // a bucket or a run outgrew its region (or a block of a one-launch form gave up waiting): again with twice the regions while the
-    // problem still fits (two launches per hour after a bail-out) ...  (each discarded attempt: CPM_INFO_STEPS_REPEATED)
-    while (rc == CPM_OK && c->h_counts[nwords - 1] != 0 && pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && absorb_status(c, c->h_counts[nwords - 1])) {
-        ++c->steps_repeated;
-        rc = resample_enqueue(c, seed, flags, c->d_counts);
-        if (rc == CPM_OK) rc = fetch();
-    }
-    if (rc == CPM_OK && c->h_counts[nwords - 1] != 0) {  // ... else on a layout that cannot overflow
-        ++c->steps_repeated;
-        if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED) c->grouped_overflowed = true;
-        c->kernel = cpm::exact_path_fits(static_cast<int>(c->Z)) ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
-        rc = resample_enqueue(c, seed, flags, c->d_counts);
-        if (rc == CPM_OK) rc = fetch();
-    }
+    int32_t rc = resample_blocking(c, seed, flags);
     if (rc != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z * c->T);
     std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
     std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
     if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
@@ -1686,6 +1859,175 @@ int32_t cpm_debug_categorical(cpm_ctx *c, int64_t origin1, int64_t hour1, int64_
     dfree(d_n);
     if (e != hipSuccess) return fail(CPM_ERR_HIP, "debug_categorical: %s", hipGetErrorString(e));
     if (n_exact_out) *n_exact_out = h_n;
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ batch (include/cpm_batch.h)
+
+int32_t cpm_set_p_drive_batch(cpm_ctx *c, int32_t B, const double *p_drives)
+{
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (B < 1 || B > CPM_MAX_BATCH) return fail(CPM_ERR_ARG, "set_p_drive_batch: B = %d outside 1..%d", B, CPM_MAX_BATCH);
+    if (!p_drives) return fail(CPM_ERR_ARG, "set_p_drive_batch: null p_drives");
+    CTX_TRY(c);
+    int32_t rc = ensure_batch_tables(c, B);
+    if (rc != CPM_OK) return rc;
+    const int64_t cells = static_cast<int64_t>(B) * c->T * c->Z;
+    HIP_TRY(hipMemcpyAsync(c->d_pdrive_b, p_drives, sizeof(double) * cells, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(cpm::k_build_thr, dim3(nblk(cells, 256)), dim3(256), 0, c->stream, c->d_pdrive_b, c->d_thr_b, cells);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->batch_B = B;
+    return CPM_OK;
+}
+
+int32_t cpm_build_p_drive_batch(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive)
+{
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (B < 1 || B > CPM_MAX_BATCH) return fail(CPM_ERR_ARG, "build_p_drive_batch: B = %d outside 1..%d", B, CPM_MAX_BATCH);
+    if (!p_min || !p_max || !e_drive) return fail(CPM_ERR_ARG, "build_p_drive_batch: null parameter array");
+    CTX_TRY(c);
+    if (!c->have_dm()) return fail(CPM_ERR_STATE, "build_p_drive_batch: datamatrix and distance matrix first");
+    int32_t rc = ensure_batch_tables(c, B);
+    if (rc == CPM_OK) rc = ensure_pdrive_mean(c);
+    if (rc != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z * c->T);
+    for (int b = 0; b < B; ++b)  // (the kernel of cpm_build_p_drive: the same table bit for bit; the call returns once they are enqueued)
+        hipLaunchKernelGGL(cpm::k_pdrive_final, dim3(nblk(c->Z, 64), static_cast<unsigned>(c->T)), dim3(64), 0, c->stream, c->d_pdrive_mean,
+                           c->d_pdrive_b + b * zt, c->d_thr_b + b * zt, static_cast<int>(c->Z), static_cast<int>(c->T), p_min[b], p_max[b], e_drive[b]);
+    HIP_TRY(hipGetLastError());
+    c->batch_B = B;
+    return CPM_OK;
+}
+
+int32_t cpm_get_p_drive_batch(cpm_ctx *c, double *out)
+{
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!out) return fail(CPM_ERR_ARG, "get_p_drive_batch: null out");
+    CTX_TRY(c);
+    if (c->batch_B < 1) return fail(CPM_ERR_STATE, "get_p_drive_batch: no batch tables");
+    HIP_TRY(hipMemcpyAsync(out, c->d_pdrive_b, sizeof(double) * c->batch_B * c->Z * c->T, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+int32_t cpm_resample_batch(cpm_ctx *c, const uint64_t *seeds, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16)
+{
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "resample_batch: null count outputs");
+    CTX_TRY(c);
+    int32_t rc = batch_ready(c, seeds, flags);
+    if (rc != CPM_OK) return rc;
+    absorb_batch_status(c);
+    const int B = c->batch_B;
+    const size_t zt = static_cast<size_t>(c->Z * c->T), nwords = 2 * zt + 2;
+    FleetTable fleet(c);
+    fleet.use(0);
+    auto single = [&](int b) -> int32_t {  // fleet b through the single-fleet step (its own repeats and fallbacks included)
+        fleet.use(b);
+        int32_t r = resample_blocking(c, seeds[b], flags);
+        if (r != CPM_OK) return r;
+        std::memcpy(parking + b * zt, c->h_counts, sizeof(int64_t) * zt);
+        std::memcpy(driving + b * zt, c->h_counts + zt, sizeof(int64_t) * zt);
+        if (sum_tt_q16) sum_tt_q16[b] = c->h_counts[2 * zt];
+        return CPM_OK;
+    };
+    if (!batch_grouped(c)) {  // the grouped path would not run this problem: every fleet with the context's kernel choice
+        for (int b = 0; b < B && rc == CPM_OK; ++b) rc = single(b);
+        return rc;
+    }
+    if (c->bcounts_cap < B) {
+        dfree(c->d_bcounts);
+        if (c->h_bcounts) (void)hipHostFree(c->h_bcounts);
+        c->h_bcounts = nullptr;
+        c->bcounts_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_bcounts, sizeof(int64_t) * nwords * B));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_bcounts), sizeof(int64_t) * nwords * B));
+        c->bcounts_cap = B;
+    }
+    std::vector<int32_t> todo(B);
+    for (int b = 0; b < B; ++b) todo[b] = b;
+    std::vector<char> by_single(B, 0);
+    int batched = B;
+    for (;;) {
+        std::vector<uint64_t> sd(todo.size());
+        for (size_t k = 0; k < todo.size(); ++k) sd[k] = seeds[todo[k]];
+        rc = batch_enqueue(c, sd, todo, todo, flags, c->d_bcounts);
+        if (rc != CPM_OK) return rc;
+        for (int32_t b : todo)
+            HIP_TRY(hipMemcpyAsync(c->h_bcounts + b * nwords, c->d_bcounts + b * nwords, sizeof(int64_t) * nwords, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        std::vector<int32_t> over;
+        for (int32_t b : todo)
+            if (c->h_bcounts[b * nwords + nwords - 1] != 0) over.push_back(b);
+        if (over.empty()) break;
+        // a bucket or a run of these fleets outgrew its region: again, those fleets only, with twice the batch's regions while the
+        // problem still fits ...  (each discarded attempt: CPM_INFO_STEPS_REPEATED)
+        ++c->steps_repeated;
+        if (grow_batch(c)) {
+            todo = over;
+            continue;
+        }
+        for (int32_t b : over) {  // ... else one at a time through the single-fleet step
+            rc = single(b);
+            if (rc != CPM_OK) return rc;
+            by_single[b] = 1;
+            --batched;
+        }
+        break;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (by_single[b]) continue;
+        const int64_t *h = c->h_bcounts + b * nwords;
+        std::memcpy(parking + b * zt, h, sizeof(int64_t) * zt);
+        std::memcpy(driving + b * zt, h + zt, sizeof(int64_t) * zt);
+        if (sum_tt_q16) sum_tt_q16[b] = h[2 * zt];
+    }
+    c->last_batch_fleets = batched;
+    if (batched > 0) {
+        c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
+        c->last_form = CPM_FORM_BATCH;
+    }
+    return CPM_OK;
+}
+
+int32_t cpm_resample_batch_dev(cpm_ctx *c, const uint64_t *seeds, uint32_t flags, void *d_counts)
+{
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!d_counts) return fail(CPM_ERR_ARG, "resample_batch_dev: null d_counts");
+    CTX_TRY(c);
+    int32_t rc = batch_ready(c, seeds, flags);
+    if (rc != CPM_OK) return rc;
+    absorb_batch_status(c);
+    const int B = c->batch_B;
+    const size_t nwords = static_cast<size_t>(2 * c->T * c->Z + 2);
+    int64_t *counts = static_cast<int64_t *>(d_counts);
+    FleetTable fleet(c);
+    fleet.use(0);
+    if (!batch_grouped(c)) {
+        for (int b = 0; b < B && rc == CPM_OK; ++b) {
+            fleet.use(b);
+            rc = resample_enqueue(c, seeds[b], flags, counts + b * nwords);
+        }
+        return rc;
+    }
+    std::vector<int32_t> all(B);
+    for (int b = 0; b < B; ++b) all[b] = b;
+    rc = batch_enqueue(c, std::vector<uint64_t>(seeds, seeds + B), all, all, flags, counts);
+    if (rc != CPM_OK) return rc;
+    if (!c->bstatus_pending) {  // (one step's status in flight at a time: a later one is looked at when that one has been)
+        if (!c->d_bstatus) HIP_TRY(hipMalloc(&c->d_bstatus, sizeof(unsigned long long)));
+        if (!c->h_bstatus) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_bstatus), sizeof(unsigned long long)));
+        if (!c->bstatus_ev) HIP_TRY(hipEventCreateWithFlags(&c->bstatus_ev, hipEventDisableTiming));
+        hipLaunchKernelGGL(cpm::k_batch_status, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<const unsigned long long *>(counts), nwords, B, c->d_bstatus);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->h_bstatus, c->d_bstatus, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(c->bstatus_ev, c->stream));
+        c->bstatus_pending = true;
+    }
+    c->last_batch_fleets = B;
+    c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
+    c->last_form = CPM_FORM_BATCH;
     return CPM_OK;
 }
 

@@ -900,10 +900,14 @@ __device__ __forceinline__ void hand_off_done(uint32_t *done_chunk, int tid)
 // does not depend on the arrivals' count, so count and ids are requested together.
 // SPARSE: the row packs are sparse packs (cpm_dataset.h); a template parameter, not a.smap read at run time: the dense sampler lives
 // at its SGPR ceiling and the pointer, the flag and the branch cost it seven more scalar spills (v_readlane in its hot paths).
-template <int BLOCK, int CPT, int NQ, bool GROUPED, bool FUSED, bool WAIT = false, bool SPARSE = false>
+// STAGED (the batched sampler, cpm_batch.h): the caller has put the zone's pack into `pack` already -- no LDS-DMA here, and the ids
+// are waited for with vmcnt(0) (nothing of this body is in flight behind them).  The pack is read behind the barrier of the first
+// pass, which follows that wait in every wave.
+template <int BLOCK, int CPT, int NQ, bool GROUPED, bool FUSED, bool WAIT = false, bool SPARSE = false, bool STAGED = false>
 __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const int z, uint32_t *pack, SampleLds &sl, uint32_t *done_chunk,
                                                     const uint32_t *wait_on = nullptr, uint32_t wait_need = 0)
 {
+    static_assert(!(STAGED && (WAIT || FUSED)), "a staged pack is the batched sampler's: two launches per hour");
     uint32_t &s_ndrive = sl.ndrive, &s_nstay = sl.nstay, &s_split = sl.split;
     uint32_t(&gb)[kGroups] = sl.gb;
     uint32_t(&stage)[kGroups * kStage] = sl.stage;
@@ -990,8 +994,12 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
             const uint32_t off = min(s4 + (s4 >= ns4 ? gap4 : 0u), top4);
             asm volatile("global_load_dword %0, %1, %2" : "=v"(id[c]) : "v"(off), "s"(a.ids + b) : "memory");
         }
-        pack_dma<BLOCK, NQ>(pack, a.rp_t + static_cast<size_t>(z) * rw, pieces, tid);
-        wait_ids<CPT + 1, NQ>(id);
+        if constexpr (STAGED) {
+            wait_ids<CPT + 1, 0>(id);
+        } else {
+            pack_dma<BLOCK, NQ>(pack, a.rp_t + static_cast<size_t>(z) * rw, pieces, tid);
+            wait_ids<CPT + 1, NQ>(id);
+        }
     }
     CPM_SSTAMP(1);
     // A bucket beyond CPT * BLOCK cars is walked here BLOCK cars at a time -- unless it is heavy, the heavy kernel follows and has
@@ -1472,7 +1480,7 @@ __device__ __forceinline__ uint32_t place_surplus_entry(const PlaceLds<PB, KRUNS
     return hand_load<FUSED>(&D[(static_cast<size_t>(zc) * kGroups + g) * scap + place_held(KDEEP, FUSED) + (e - pl.lstart[r])]);
 }
 // exclusive scan of the surplus lengths (one per thread), then the histogram of the surplus entries (tbins); returns their number
-template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool PERM = false>
+template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool PERM = false, int TAG = 0>
 __device__ __noinline__ uint32_t place_surplus_count(PlaceLds<PB, KRUNS, ZPG> &pl, const uint32_t *D, int g, int zs0, int zs1, uint32_t scap, uint32_t idbits)
 {
     constexpr int kRuns = (KRUNS / 2) * (PB / 8), kSurplusBatch = 4;
@@ -1500,7 +1508,7 @@ __device__ __noinline__ uint32_t place_surplus_count(PlaceLds<PB, KRUNS, ZPG> &p
     return ltotal;
 }
 // the surplus entries straight to their buckets (tbins: the running position inside each bucket)
-template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool SIGNAL, bool PERM = false>
+template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool SIGNAL, bool PERM = false, int TAG = 0>
 __device__ __noinline__ void place_surplus_out(PlaceLds<PB, KRUNS, ZPG> &pl, const uint32_t *D, int g, int zs0, int zs1, uint32_t scap, uint32_t idbits,
                                                int zg0, int nzl, uint32_t cap, uint32_t *__restrict__ ids_next, uint32_t ltotal)
 {
@@ -1542,7 +1550,9 @@ constexpr uint32_t kFusedSpinLimit = 1u << 15;  // default number of polls: x (o
 // the block in on its destination group's counter (done_out), which the group's sampler workgroups ask for before they read.
 // PERM (k_grouped_hour with its zones dealt largest-first): the runs of the block are those of the zones perm[zs0 ...] -- the
 // sampler workgroups of chunk j by POSITION in the launch.
-template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool SIGNAL = false, bool PERM = false>
+// TAG: the batched placing (cpm_batch.h, TAG 1) calls instances of the out-of-line helpers of its own, so that what the compiler infers
+// from their callers -- e.g. where the run pointers point -- stays that of the hourly kernels.
+template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool SIGNAL = false, bool PERM = false, int TAG = 0>
 __device__ __forceinline__ void grouped_place_body(const int g, const int j, PlaceLds<PB, KRUNS, ZPG> &pl, uint32_t *sorted_ids, const uint32_t *__restrict__ D,
                                                    const uint32_t *__restrict__ cntg, int zpg, int zps, int Z, uint32_t cap, uint32_t scap, uint32_t idbits,
                                                    uint32_t *__restrict__ cnt_a_next, uint32_t *__restrict__ ids_next, unsigned long long *status,
@@ -1723,7 +1733,7 @@ __device__ __forceinline__ void grouped_place_body(const int g, const int j, Pla
     CPM_PSTAMP(3);
     const bool any_long = __builtin_amdgcn_readfirstlane(static_cast<int>(s_any_long)) != 0;  // (block-uniform, in a scalar register)
     uint32_t ltotal = 0;
-    if (any_long) ltotal = place_surplus_count<PB, KRUNS, KDEEP, ZPG, FUSED, PERM>(pl, D, g, zs0, zs1, scap, idbits);
+    if (any_long) ltotal = place_surplus_count<PB, KRUNS, KDEEP, ZPG, FUSED, PERM, TAG>(pl, D, g, zs0, zs1, scap, idbits);
     // The ticket (this block's range inside each bucket of the group) is requested now and needed only when the sorted list is
     // written out: its round trip runs under the block scan of the histogram (the zones' offsets in the sorted list) and the sort.
     const bool zone = tid < nzl;
@@ -1795,7 +1805,7 @@ __device__ __forceinline__ void grouped_place_body(const int g, const int j, Pla
         }
     }
     // ... and the surplus of the long runs straight to their buckets
-    if (any_long) place_surplus_out<PB, KRUNS, KDEEP, ZPG, FUSED, SIGNAL, PERM>(pl, D, g, zs0, zs1, scap, idbits, zg0, nzl, cap, ids_next, ltotal);
+    if (any_long) place_surplus_out<PB, KRUNS, KDEEP, ZPG, FUSED, SIGNAL, PERM, TAG>(pl, D, g, zs0, zs1, scap, idbits, zg0, nzl, cap, ids_next, ltotal);
     CPM_PSTAMP(7);
 #if defined(CPM_DIAGNOSTIC) && !defined(CPM_STAMP_SAMPLER) && !defined(CPM_STAMP_BOTH)
     st_[7] = (st_[7] & ~1ull) | (any_long ? 1ull : 0ull);  // (the tick's lowest bit: did this block take the long-run path)

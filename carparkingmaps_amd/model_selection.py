@@ -93,11 +93,13 @@ class Evaluator:
             self.measured_parking = np.asfortranarray(np.asarray(self.measured_parking, dtype=np.float64))
 
     def _install(self, pt):
-        s = self.sampler
-        s.build_p_drive(pt.p_min, pt.p_max, pt.e_drive, want=False)   # (Z x T work: the Z x Z x T mean is cached by the library)
-        key = (type(pt.e_dest).__name__, float(pt.e_dest))
+        self.sampler.build_p_drive(pt.p_min, pt.p_max, pt.e_drive, want=False)   # (Z x T work: the Z x Z x T mean is cached by the library)
+        self._install_dest(pt.e_dest)
+
+    def _install_dest(self, e_dest):
+        key = e_dest_key(e_dest)
         if key != self._e_dest:              # the CDF and the row packs are rebuilt only when e_dest changes
-            s.build_p_dest(pt.e_dest, want=False)
+            self.sampler.build_p_dest(e_dest, want=False)
             self._e_dest = key
 
     def _objectives(self, pt, parking, driving, sum_tt_q16):
@@ -118,24 +120,34 @@ class Evaluator:
         return self._objectives(pt, r["parking"], r["driving"], r["sum_tt_q16"])
 
     # -- pipelined form: point k+1 runs on the GPU while the host reduces point k (two count tensors, pinned host twins) --
-    def begin(self, pt, slot):
-        """Enqueue the table update, the resample and the copy of its counts to the host for `pt`; returns at once."""
+    def _slot(self, slot, n):
+        """The pipeline's stream, and slot `slot`'s count tensors of at least n words.  A slot grows alone: when it is begun again its
+        last step has been reduced (finish runs behind the begin of the next step), while the other slot's step may still be in flight
+        -- its tensors and its event stay as they are."""
         import torch
         s = self.sampler
         if self._pipe is None:
             if s._stream is None:     # (a Sampler that was given its stream at construction keeps it; see Sampler.__init__)
                 s.set_stream(torch.cuda.Stream(device=s.device))
             stream = s._stream_obj if hasattr(s._stream_obj, "cuda_stream") else torch.cuda.ExternalStream(s._stream, device=s.device)
-            n = s.counts_words()
-            self._pipe = dict(stream=stream,
-                              dev=[torch.zeros(n, dtype=torch.int64, device=f"cuda:{s.device}") for _ in range(2)],
-                              host=[torch.zeros(n, dtype=torch.int64).pin_memory() for _ in range(2)],
-                              done=[torch.cuda.Event() for _ in range(2)])
+            self._pipe = dict(stream=stream, dev=[None, None], host=[None, None], done=[torch.cuda.Event() for _ in range(2)])
         p = self._pipe
+        if p["dev"][slot] is None or p["dev"][slot].numel() < n:
+            p["done"][slot].synchronize()  # (a slot's event has recorded nothing yet, or a step that has been reduced)
+            p["dev"][slot] = torch.zeros(n, dtype=torch.int64, device=f"cuda:{s.device}")
+            p["host"][slot] = torch.zeros(n, dtype=torch.int64).pin_memory()
+        return p
+
+    def begin(self, pt, slot):
+        """Enqueue the table update, the resample and the copy of its counts to the host for `pt`; returns at once."""
+        import torch
+        s = self.sampler
+        n = s.counts_words()
+        p = self._slot(slot, n)
         self._install(pt)
         with torch.cuda.stream(p["stream"]):
             s.resample_dev(self.seed, p["dev"][slot].data_ptr(), travel=self.travel)
-            p["host"][slot].copy_(p["dev"][slot], non_blocking=True)
+            p["host"][slot][:n].copy_(p["dev"][slot][:n], non_blocking=True)
             p["done"][slot].record(p["stream"])
 
     def finish(self, pt, slot):
@@ -157,6 +169,62 @@ class Evaluator:
         parking = both[:zt].reshape((T, Z)).T                 # Julia order (Z, T): views, no second copy
         driving = both[zt:].reshape((T, Z)).T
         return self._objectives(pt, parking, driving, int(flat[2 * zt]))
+
+
+    # -- batched form: the points of one batch share e_dest and run as the fleets of ONE batched resample (include/cpm_batch.h) --
+    def begin_batch(self, pts, slot):
+        """Enqueue the batch tables of `pts` (one e_dest), their batched resample and the copy of their counts to the host."""
+        import torch
+        s = self.sampler
+        n = s.counts_words() * len(pts)
+        p = self._slot(slot, n)        # (sized per slot: a lane's batches need not grow monotonically, nor be of one size)
+        self._install_dest(pts[0].e_dest)
+        s.build_p_drive_batch([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts])
+        with torch.cuda.stream(p["stream"]):
+            s.resample_batch_dev(self.seed, p["dev"][slot].data_ptr(), travel=self.travel)
+            p["host"][slot][:n].copy_(p["dev"][slot][:n], non_blocking=True)
+            p["done"][slot].record(p["stream"])
+
+    def finish_batch(self, pts, slot):
+        """Wait for `begin_batch(pts, slot)` and reduce every fleet's counts; a fleet whose status word is set is evaluated again
+        through the blocking call (and counted in `fallbacks`), as in finish()."""
+        p = self._pipe
+        p["done"][slot].synchronize()
+        Z, T = self.sampler.Z, self.sampler.T
+        zt, nw = Z * T, self.sampler.counts_words()
+        flat = p["host"][slot].numpy()[:nw * len(pts)].reshape(len(pts), nw)
+        bad = flat[:, 2 * zt + 1] != 0
+        counts = flat[:, :2 * zt].copy()                      # (the pinned twin is reused two batches later)
+        outs = []
+        for b, pt in enumerate(pts):
+            if bad[b]:
+                self.fallbacks += 1
+                out = self.evaluate(pt)
+                out["fallback"] = True
+            else:
+                parking = counts[b, :zt].reshape((T, Z)).T
+                driving = counts[b, zt:].reshape((T, Z)).T
+                out = self._objectives(pt, parking, driving, int(flat[b, 2 * zt]))
+            outs.append(out)
+        return outs
+
+
+def e_dest_key(e_dest):
+    """What tells two e_dest values apart for the tables: Julia's Float64^Int and Float64^Float64 differ (main.jl:38)."""
+    return (type(e_dest).__name__, float(e_dest))
+
+
+def batch_cuts(grid, order, batch):
+    """`order` (indices into `grid`, already ordered by e_dest) cut into runs of at most `batch` CONSECUTIVE points that share one
+    e_dest: the fleets of one batched resample each."""
+    cuts, key = [], None
+    for i in order:
+        k = e_dest_key(grid[i].e_dest)
+        if not cuts or k != key or len(cuts[-1]) >= batch:
+            cuts.append([])
+        cuts[-1].append(i)
+        key = k
+    return cuts
 
 
 # ------------------------------------------------------------------ the reference's three searches
@@ -234,7 +302,7 @@ def points_of_rank(n_points, rank, world_size, order=None):
     return order[begin:begin + base + (1 if rank < rem else 0)]
 
 
-def grid_sweep(evaluator, grid, rank=0, world_size=1, gather=True, checksums=False):
+def grid_sweep(evaluator, grid, rank=0, world_size=1, gather=True, checksums=False, batch=None):
     """Evaluate this rank's share of `grid`; returns a list (on every rank when gather) of dicts with the
     per-point scalars, ordered like `grid` (checksums: also CRC-32 of both count tensors, for the tests).
 
@@ -242,7 +310,10 @@ def grid_sweep(evaluator, grid, rank=0, world_size=1, gather=True, checksums=Fal
     rank's slice is cut into as many contiguous pieces and the pieces advance in turn, so that a point of every context is on
     the GPU at any time.  A resample is a serial chain of an issue-bound sampler launch and a latency-bound placing launch
     per hour; two independent chains interleave on the chip (measured at S4k: 1.41 ms for two resamples side by side
-    against 2 x 0.92 one after the other, profiles/round2_notes.md) -- the hours of ONE resample cannot."""
+    against 2 x 0.92 one after the other, profiles/round2_notes.md) -- the hours of ONE resample cannot.
+
+    batch=B: each lane's slice is cut into batches of at most B consecutive points that share e_dest (batch_cuts); a batch is ONE
+    batched resample of B fleets (Evaluator.begin_batch / finish_batch, pipelined like begin / finish).  Same results, point for point."""
     lanes = list(evaluator) if isinstance(evaluator, (list, tuple)) else [evaluator]
     C = lanes[0].C
     by_e_dest = sorted(range(len(grid)), key=lambda i: (float(grid[i].e_dest), type(grid[i].e_dest).__name__, i))
@@ -269,7 +340,25 @@ def grid_sweep(evaluator, grid, rank=0, world_size=1, gather=True, checksums=Fal
                 except StopIteration:
                     gens.remove(g)
 
-    for i, r in results():
+    def lane_batches(ev, pts):  # batch k+1 is enqueued before batch k is reduced; every step yields the list of results it reduced
+        prev = None
+        for k, cut in enumerate(batch_cuts(grid, pts, int(batch))):
+            ev.begin_batch([grid[i] for i in cut], k & 1)
+            yield list(zip(prev[0], ev.finish_batch([grid[i] for i in prev[0]], prev[1]))) if prev is not None else []
+            prev = (cut, k & 1)
+        if prev is not None:
+            yield list(zip(prev[0], ev.finish_batch([grid[i] for i in prev[0]], prev[1])))
+
+    def results_batched():
+        gens = [lane_batches(ev, points_of_rank(len(mine), l, len(lanes), mine)) for l, ev in enumerate(lanes)]
+        while gens:
+            for g in list(gens):
+                try:
+                    yield from next(g)
+                except StopIteration:
+                    gens.remove(g)
+
+    for i, r in (results() if batch is None else results_batched()):
         local[i] = {k: v for k, v in r.items() if np.isscalar(v)}
         local[i]["fallback"] = bool(r.get("fallback", False))   # evaluated twice: its asynchronous step had overflowed
         local[i]["driving_total"] = int(r["driving"].sum())

@@ -89,12 +89,14 @@ class Sampler:
         return int(v.value)
 
     def last_step(self):
-        """The record of the most recent step: {kernel, form, repeats (cumulative), cap_mult, parts, bailouts (cumulative)}.
+        """The record of the most recent step: {kernel, form, repeats (cumulative), cap_mult, parts, bailouts (cumulative), batch_fleets
+        (fleets of a batch step that the batched kernels produced; 0 after any other step)}.
         Not a plain getter: an IVP that solve_ivp_async left in flight is committed first (the call waits for the stream and may
         repeat that IVP, which then shows in `repeats`), so it must not be called while the stream is being captured."""
         return dict(kernel=self.get_info(_lib.CPM_INFO_LAST_KERNEL), form=self.get_info(_lib.CPM_INFO_LAST_FORM),
                     repeats=self.get_info(_lib.CPM_INFO_STEPS_REPEATED), cap_mult=self.get_info(_lib.CPM_INFO_CAP_MULT),
-                    parts=self.get_info(_lib.CPM_INFO_PARTS), bailouts=self.get_info(_lib.CPM_INFO_FUSED_BAILOUTS))
+                    parts=self.get_info(_lib.CPM_INFO_PARTS), bailouts=self.get_info(_lib.CPM_INFO_FUSED_BAILOUTS),
+                    batch_fleets=self.get_info(_lib.CPM_INFO_LAST_BATCH_FLEETS))
 
     def set_profile(self, on=True, stride=1, kernel=0):
         """hipEvents around every `stride`-th hourly launch of `kernel` (0 sampler, 1 place, 2 travel); on=False: off."""
@@ -243,6 +245,60 @@ class Sampler:
 
     def counts_words(self):
         return 2 * self.T * self.Z + 2
+
+    # -- batches (include/cpm_batch.h): B fleets, each with its own p_drive and seed, from this context's state and p_destin --
+    def set_p_drive_batch(self, p_drives):
+        """p_drives: (Z, T, B), B <= 64 (Julia p_drives[:,:,b]); replaces the batch tables.  The context's own p_drive is untouched."""
+        a = np.asfortranarray(p_drives, dtype=np.float64)
+        if a.ndim != 3 or a.shape[:2] != (self.Z, self.T):
+            raise ValueError(f"expected shape ({self.Z}, {self.T}, B), got {a.shape}")
+        _lib.check(self._L.cpm_set_p_drive_batch(self._h, int(a.shape[2]), _vp(a)))
+
+    def build_p_drive_batch(self, p_min, p_max, e_drive, want=False):
+        """createpdrive once per fleet: fleet b = (p_min[b], p_max[b], e_drive[b]).  want: also return the (Z, T, B) tables."""
+        cols = [np.ascontiguousarray(np.atleast_1d(v), dtype=np.float64) for v in (p_min, p_max, e_drive)]
+        B = cols[0].shape[0]
+        if any(c.shape != (B,) for c in cols):
+            raise ValueError("p_min, p_max and e_drive must be sequences of one length")
+        _lib.check(self._L.cpm_build_p_drive_batch(self._h, int(B), *(_vp(c) for c in cols)))
+        return self.get_p_drive_batch() if want else None
+
+    def get_p_drive_batch(self):
+        out = np.zeros((self.Z, self.T, self.get_info(_lib.CPM_INFO_BATCH)), dtype=np.float64, order="F")
+        _lib.check(self._L.cpm_get_p_drive_batch(self._h, _vp(out)))
+        return out
+
+    def _batch_seeds(self, seeds):
+        B = self.get_info(_lib.CPM_INFO_BATCH)
+        sd = np.asarray(seeds, dtype=np.uint64).reshape(-1)
+        if sd.shape[0] == 1:
+            sd = np.full(B, sd[0], dtype=np.uint64)
+        if sd.shape[0] != B:
+            raise ValueError(f"{sd.shape[0]} seeds for {B} fleets")
+        return np.ascontiguousarray(sd), B
+
+    def resample_batch(self, seeds, travel=False):
+        """Every fleet of the installed batch tables, blocking.  seeds: one for all fleets (common random numbers) or B.  Returns
+        dict(parking, driving: (Z, T, B) int64 F-order; sum_tt_q16: (B,) int64) -- fleet b bit for bit resample(seeds[b]) with
+        p_drive[:, :, b] installed."""
+        sd, B = self._batch_seeds(seeds)
+        parking = np.zeros((self.Z, self.T, B), dtype=np.int64, order="F")
+        driving = np.zeros((self.Z, self.T, B), dtype=np.int64, order="F")
+        tt = np.zeros(B, dtype=np.int64)
+        flags = _lib.CPM_FLAG_TRAVEL if travel else 0
+        _lib.check(self._L.cpm_resample_batch(self._h, _vp(sd), flags, _vp(parking), _vp(driving), _vp(tt)))
+        return dict(parking=parking, driving=driving, sum_tt_q16=tt)
+
+    def resample_batch_dev(self, seeds, d_counts_ptr, travel=False):
+        """Enqueue on the context's stream; d_counts_ptr = device address of int64[B][2*T*Z+2], each fleet laid out like
+        resample_dev's tensor with its own status word (!= 0: that fleet's counts are invalid, repeat it)."""
+        sd, _ = self._batch_seeds(seeds)
+        flags = _lib.CPM_FLAG_TRAVEL if travel else 0
+        _lib.check(self._L.cpm_resample_batch_dev(self._h, _vp(sd), flags, C.c_void_p(int(d_counts_ptr))))
+
+    def batch_counts_words(self):
+        """int64 words of resample_batch_dev's tensor: B x counts_words()."""
+        return self.get_info(_lib.CPM_INFO_BATCH) * self.counts_words()
 
     def last_kernel_ms(self):
         buf = (C.c_float * 8192)()

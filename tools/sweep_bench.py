@@ -21,6 +21,7 @@ ap.add_argument("--cpz", type=int, default=1000)
 ap.add_argument("--points", type=int, default=32, help="(kept for old command lines; the share of one rank of --world is what is timed)")
 ap.add_argument("--world", type=int, default=8)
 ap.add_argument("--lanes", type=int, default=2, help="sampler contexts of the rank (grid points in flight on the GPU at a time)")
+ap.add_argument("--batch", type=int, default=None, help="B: each lane runs its points as batched resamples of up to B fleets (include/cpm_batch.h)")
 args = ap.parse_args()
 Z, T, cpz = args.zones, 24, args.cpz
 C = Z * cpz
@@ -45,13 +46,13 @@ for lane in range(args.lanes):
 grid = ms.make_grid()                                # the 256 points of BASELINE.json configs[4]
 for n in sorted({1, args.lanes}):
     ev = lanes[:n]
-    ms.grid_sweep(ev, grid[:2 * n])
+    ms.grid_sweep(ev, grid[:2 * n], batch=args.batch)
     for rank in (0, args.world - 1):                 # what one rank of the 8-GPU job does: its block of the grid, ordered by e_dest
         for again in (False, True):                  # (again: the lanes already hold the rank's e_dest tables -- the steady state of a longer grid)
             t0 = time.perf_counter()
-            res = [r for r in ms.grid_sweep(ev, grid, rank=rank, world_size=args.world, gather=False) if r is not None]
+            res = [r for r in ms.grid_sweep(ev, grid, rank=rank, world_size=args.world, gather=False, batch=args.batch) if r is not None]
             dt = time.perf_counter() - t0
-            print(f"{n} lane(s), rank {rank} of {args.world}{' (tables resident)' if again else ''}: {len(res)} grid points in {dt:.3f} s = "
+            print(f"{n} lane(s){f', batches of {args.batch}' if args.batch else ''}, rank {rank} of {args.world}{' (tables resident)' if again else ''}: {len(res)} grid points in {dt:.3f} s = "
                   f"{1e3 * dt / len(res):.2f} ms/point ({len(res) * C * T / dt:.3e} car-steps/s incl. table rebuilds, travel times, counts to "
                   f"the host and the objectives); e_dest values {sorted({r['e_dest'] for r in res})}", flush=True)
 print("sample:", {k: (round(v, 4) if isinstance(v, float) else v) for k, v in res[0].items()})
