@@ -30,6 +30,8 @@ CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
 CPM_OPT_KERNEL, CPM_OPT_PROFILE, CPM_OPT_PROFILE_KERNEL, CPM_OPT_FUSED, CPM_OPT_FUSED_LAG, CPM_OPT_ZONE_ORDER = 1, 2, 3, 4, 5, 6
+CPM_OPT_SPARSE_UPLOAD = 7  # set_p_dest: sparse row packs for an uploaded p_destin that qualifies (include/cpm.h)
+CPM_PROFILE_SAMPLER, CPM_PROFILE_PLACE, CPM_PROFILE_TRAVEL, CPM_PROFILE_UPLOAD = 0, 1, 2, 3
 # cpm_get_info keys (include/cpm.h): what the context would run next ...
 CPM_INFO_KERNEL, CPM_INFO_CAP_MULT, CPM_INFO_PARTS, CPM_INFO_FUSED, CPM_INFO_FUSED_BAILOUTS, CPM_INFO_SPARSE_TABLES = 1, 2, 3, 4, 5, 6
 # ... and what its most recent step ran

@@ -18,6 +18,7 @@
 #include "cpm_grouped.h"
 #include "cpm_batch.h"
 #include "cpm_dataset.h"
+#include "cpm_upload.h"
 #include "cpm_ingest.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -110,6 +111,10 @@ struct cpm_ctx {
     uint32_t *d_scnt = nullptr;         // [T*Z] cells per row
     bool sparse_tables = false;         // the installed p_destin tables are of that kind: d_p holds p_destin only when p_dense_valid
     bool p_dense_valid = false;
+    bool tables_uploaded = false;       // ... or from an uploaded p_destin (cpm_upload.h, CPM_OPT_SPARSE_UPLOAD): the three arrays are all they come from
+    bool sparse_upload = false;         // CPM_OPT_SPARSE_UPLOAD: cpm_set_p_dest tries the sparse route
+    uint32_t *d_up_stats = nullptr;     // {longest row, a row outgrew kDsCap} of k_up_compact, and their pinned twin
+    uint32_t *h_up_stats = nullptr;
     double tab_e_dest = 2.0;            // the exponent they were built with (cpm_refresh_tables)
     int tab_e_int = 1;
     size_t hi_words_alloc = 0;          // words d_hi was allocated for
@@ -282,6 +287,7 @@ int32_t build_rows(cpm_ctx *c, bool with_cdf)
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     if (!c->d_ckpt) HIP_TRY(hipMalloc(&c->d_ckpt, sizeof(double) * static_cast<size_t>(rows) * cpm::ckpt_count(static_cast<int>(c->Z))));
     c->sparse_tables = false;  // (dense packs of the table in d_p)
+    c->tables_uploaded = false;
     c->p_dense_valid = true;
     c->Zq = cpm::pack_zq(static_cast<int>(c->Z));
     c->pk_G = cpm::pack_guide_bits(static_cast<int>(c->Z));
@@ -549,6 +555,7 @@ int32_t build_p_dest_sparse(cpm_ctx *c, double e_dest, int32_t e_is_integer, boo
                        rows, static_cast<int>(c->Z), e_dest, e_is_integer, nc, zq_c, g_c, c->d_hi, c->d_last, c->d_sp, c->d_sj, c->d_scnt, c->d_err);
     HIP_TRY(hipGetLastError());
     c->sparse_tables = true;
+    c->tables_uploaded = false;
     c->p_dense_valid = false;
     c->Zq = zq_c;
     c->pk_G = g_c;
@@ -557,6 +564,69 @@ int32_t build_p_dest_sparse(cpm_ctx *c, double e_dest, int32_t e_is_integer, boo
     c->tab_e_int = e_is_integer;
     rc = check_err_flag(c, "p_dest holds NaN or negative entries (reference: BoundsError, Appendix A-7)", CPM_ERR_TABLE);
     if (rc != CPM_OK) return rc;
+    c->have_cdf = true;
+    c->zx.tables_dirty = true;
+    *done = true;
+    return CPM_OK;
+}
+
+// The sparse packs of an uploaded table from its compact rows in d_sp / d_sj / d_scnt (k_up_pack): what cpm_set_p_dest ends in on the
+// sparse route and what cpm_refresh_tables re-runs.  nc = the longest row.  Enqueued on the context's stream.
+int32_t pack_uploaded_rows(cpm_ctx *c, int nc)
+{
+    const int64_t rows = c->T * c->Z;
+    const int zq_c = cpm::pack_zq(nc), g_c = cpm::pack_guide_bits(nc);
+    if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
+    int32_t rc = ensure_hi(c, static_cast<size_t>(rows) * cpm::pack_row_words(zq_c, g_c, 1));
+    if (rc != CPM_OK) return rc;
+    prof_begin(c, CPM_PROFILE_UPLOAD);
+    cpm::launch(cpm::k_up_pack, dim3(cpm::ds_grid(rows)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_sp, c->d_sj, c->d_scnt, cpm::kDsCap, rows, nc,
+                zq_c, g_c, c->d_hi, c->d_last);
+    prof_end(c, CPM_PROFILE_UPLOAD);
+    HIP_TRY(hipGetLastError());
+    c->Zq = zq_c;
+    c->pk_G = g_c;
+    c->pk_Zc = nc;
+    return CPM_OK;
+}
+
+// cpm_set_p_dest with CPM_OPT_SPARSE_UPLOAD: the array just copied into d_p -> compact rows (k_up_compact) -> sparse packs, under the
+// dataset route's own rule (ensure_dataset): a row pack fits LDS, no row holds more than kDsCap non-zero entries, and the sparse pack
+// of the longest row is at most 60 % of the dense one.  *done = false: the table does not qualify and the caller builds dense packs.
+// The dense copy stays valid in d_p: the f64-row kernels, cpm_get_cdf_row and ties' readers see the bytes that were uploaded.
+int32_t upload_p_dest_sparse(cpm_ctx *c, bool *done)
+{
+    *done = false;
+    if (!cpm::pack_row_fits(static_cast<int>(c->Z))) return CPM_OK;
+    const int64_t rows = c->T * c->Z;
+    if (!c->d_sp) HIP_TRY(hipMalloc(&c->d_sp, sizeof(double) * static_cast<size_t>(rows) * cpm::kDsCap));
+    if (!c->d_sj) HIP_TRY(hipMalloc(&c->d_sj, sizeof(uint32_t) * static_cast<size_t>(rows) * cpm::kDsCap));
+    if (!c->d_scnt) HIP_TRY(hipMalloc(&c->d_scnt, sizeof(uint32_t) * static_cast<size_t>(rows)));
+    if (!c->d_up_stats) HIP_TRY(hipMalloc(&c->d_up_stats, 2 * sizeof(uint32_t)));
+    if (!c->h_up_stats) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_up_stats), 2 * sizeof(uint32_t)));
+    c->sparse_tables = false;  // (the compact rows of whatever table was installed are gone from here on)
+    c->tables_uploaded = false;
+    HIP_TRY(hipMemsetAsync(c->d_up_stats, 0, 2 * sizeof(uint32_t), c->stream));
+    prof_begin(c, CPM_PROFILE_UPLOAD);
+    cpm::launch(cpm::k_up_compact, dim3(nblk(c->Z, 64), static_cast<unsigned>(c->T)), dim3(64), 0, c->stream, c->d_p, c->d_sp, c->d_sj, c->d_scnt,
+                static_cast<int>(c->Z), cpm::kDsCap, c->d_up_stats, c->d_err);
+    prof_end(c, CPM_PROFILE_UPLOAD);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_up_stats, c->d_up_stats, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    int32_t rc = check_err_flag(c, "p_dest holds NaN or negative entries (reference: BoundsError, Appendix A-7)", CPM_ERR_TABLE);  // (synchronises)
+    if (rc != CPM_OK) return rc;
+    const int nc = static_cast<int>(std::max<uint32_t>(c->h_up_stats[0], 1u));
+    const int dense_words = cpm::pack_row_words(cpm::pack_zq(static_cast<int>(c->Z)), cpm::pack_guide_bits(static_cast<int>(c->Z)));
+    if (c->h_up_stats[1] != 0 || nc > static_cast<int>(cpm::kDsCap) ||
+        10 * cpm::pack_row_words(cpm::pack_zq(nc), cpm::pack_guide_bits(nc), 1) > 6 * dense_words)
+        return CPM_OK;  // dense packs: build_rows
+    c->cdf_full = false;
+    rc = pack_uploaded_rows(c, nc);
+    if (rc != CPM_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->sparse_tables = true;
+    c->tables_uploaded = true;
+    c->p_dense_valid = true;
     c->have_cdf = true;
     c->zx.tables_dirty = true;
     *done = true;
@@ -1069,6 +1139,8 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_sp);
     dfree(c->d_sj);
     dfree(c->d_scnt);
+    dfree(c->d_up_stats);
+    if (c->h_up_stats) (void)hipHostFree(c->h_up_stats);
     if (c->h_ds_stats) (void)hipHostFree(c->h_ds_stats);
     dfree(c->d_tt);
     dfree(c->d_tts_words);
@@ -1117,8 +1189,12 @@ int32_t cpm_set_option(cpm_ctx *c, int32_t option, int64_t value)
         if (value < 0 || value > 2) return fail(CPM_ERR_ARG, "zone order %lld (0 zone order, 1 largest-first, 2 largest-first on sparse row packs)", (long long)value);
         c->zg.use_perm = static_cast<int>(value);
         return CPM_OK;
+    case CPM_OPT_SPARSE_UPLOAD:
+        if (value != 0 && value != 1) return fail(CPM_ERR_ARG, "sparse upload %lld (0 dense row packs, 1 sparse where the table qualifies)", (long long)value);
+        c->sparse_upload = value != 0;  // (read when a table is installed: the installed one stays as it is)
+        return CPM_OK;
     case CPM_OPT_PROFILE_KERNEL:
-        if (value < CPM_PROFILE_SAMPLER || value > CPM_PROFILE_TRAVEL) return fail(CPM_ERR_ARG, "profile kernel %lld", (long long)value);
+        if (value < CPM_PROFILE_SAMPLER || value > CPM_PROFILE_UPLOAD) return fail(CPM_ERR_ARG, "profile kernel %lld", (long long)value);
         c->prof_what = static_cast<int>(value);
         return CPM_OK;
     case CPM_OPT_PROFILE:
@@ -1243,6 +1319,11 @@ int32_t cpm_set_p_dest(cpm_ctx *c, const double *p_dest)
     if (!c->d_p) HIP_TRY(hipMalloc(&c->d_p, bytes));
     c->have_cdf = false;
     HIP_TRY(hipMemcpyAsync(c->d_p, p_dest, bytes, hipMemcpyHostToDevice, c->stream));
+    if (c->sparse_upload) {  // sparse row packs where the table qualifies (cpm_upload.h)
+        bool done = false;
+        int32_t rc_sp = upload_p_dest_sparse(c, &done);
+        if (rc_sp != CPM_OK || done) return rc_sp;
+    }
     return build_rows(c, false);  // (synchronises: the validation flag is read back)
 }
 
@@ -1613,6 +1694,13 @@ int32_t cpm_refresh_tables(cpm_ctx *c, int32_t with_f64_cdf)
         if (rc_ivp != CPM_OK) return rc_ivp;
     }
     if (!c->have_cdf) return fail(CPM_ERR_STATE, "refresh_tables: p_dest not set");
+    if (c->sparse_tables && c->tables_uploaded) {  // (an uploaded table's packs come from the cells the table owns: no dataset has a say)
+        int32_t rc_up = pack_uploaded_rows(c, c->pk_Zc);
+        if (rc_up != CPM_OK) return rc_up;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->zx.tables_dirty = true;
+        return with_f64_cdf ? ensure_full_cdf(c) : CPM_OK;
+    }
     if (c->sparse_tables) {  // (the tables of a compact dataset: its rows are what they are rebuilt from)
         if (!c->ds_valid || !c->ds_ok) return fail(CPM_ERR_STATE, "refresh_tables: the datamatrix these tables were built from has been replaced");
         bool done = false;

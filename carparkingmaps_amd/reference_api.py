@@ -10,6 +10,11 @@ Like the reference, the functions read the script-level hyper-parameters implici
 (main.jl:37-42): they live in `params` below.  Two additions the
 reference does not have: `params.seed` (the reference draws from an unseeded global RNG)
 and `params.device`.
+
+A `p_dest` these functions upload (one that is not the array `createpdestin` just returned) gets the
+library's default, dense row packs.  `Sampler.set_sparse_upload()` (CPM_OPT_SPARSE_UPLOAD, include/cpm.h)
+on the context gives such a table the sparse packs of a device-built one where it qualifies; the Julia
+shim turns it on, this module leaves the default alone.  The counts are the same either way.
 """
 import json
 import os

@@ -77,11 +77,18 @@ class Sampler:
         off for dense ones (2-4 % slower at 4,096 zones)."""
         _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_ZONE_ORDER, int(on)))
 
+    def set_sparse_upload(self, on=True):
+        """set_p_dest gives an uploaded p_destin the sparse row packs build_p_dest gives a sparse datamatrix's tables, when the table
+        qualifies (no row with more than 512 non-zero entries, the sparse pack at most 60 % of the dense one: include/cpm.h,
+        CPM_OPT_SPARSE_UPLOAD); otherwise, and when off (the library's default), dense packs.  Read when a table is installed; the
+        counts do not depend on it.  get_info(6) tells which form the installed table took."""
+        _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_SPARSE_UPLOAD, 1 if on else 0))
+
     def get_info(self, what):
         """cpm_get_info (keys: _lib.CPM_INFO_*).  What the context would run next: 1 = kernel family AUTO resolves to now, 2 =
         bucket-region size in multiples of the mean bucket, 3 = workgroups per heavy zone, 4 = form of the hour (0 two launches, 1 one,
         3 placing first, 6 all hours in one launch), 5 = steps that bailed out of a one-launch form, 6 = words of a sparse row pack (0:
-        dense tables).  What its most recent step ran: 7 = the kernel family that produced its results (0 before any step), 8 = the
+        dense tables; > 0 after build_p_dest on a sparse datamatrix or after set_p_dest under set_sparse_upload on a table that qualifies).  What its most recent step ran: 7 = the kernel family that produced its results (0 before any step), 8 = the
         form its grouped hours took (coded as 4; -1 when the family is not the grouped one), 9 = step attempts the library discarded
         and ran again so far."""
         v = C.c_int64(0)
@@ -99,7 +106,8 @@ class Sampler:
                     batch_fleets=self.get_info(_lib.CPM_INFO_LAST_BATCH_FLEETS))
 
     def set_profile(self, on=True, stride=1, kernel=0):
-        """hipEvents around every `stride`-th hourly launch of `kernel` (0 sampler, 1 place, 2 travel); on=False: off."""
+        """hipEvents around every `stride`-th hourly launch of `kernel` (0 sampler, 1 place, 2 travel; 3: the two kernels of a
+        sparse upload, per set_p_dest); on=False: off."""
         _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_PROFILE_KERNEL, int(kernel)))
         _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_PROFILE, int(stride) if on else 0))
 

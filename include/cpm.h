@@ -88,10 +88,17 @@ extern "C" {
                                    profiles/round4_notes.md): Melbourne-shaped tables, Z = 2,357 x 1,000 cars per zone 0.686 -> 0.587 ms per resample
                                    (1.5 rounds of workgroups: the hour ended on whatever large bucket came last), x 500 0.443 -> 0.412; dense
                                    4,096 zones 2-4 % SLOWER (zone order is also memory order of the packs and of the runs) */
+#define CPM_OPT_SPARSE_UPLOAD 7 /* 1: cpm_set_p_dest gives an uploaded p_destin SPARSE row packs (csrc/cpm_upload.h: the form cpm_build_p_dest gives the
+                                   tables of a sparse datamatrix -- a fifth of the dense pack's bytes at Uber Movement's density) when the table
+                                   qualifies: a row pack fits LDS, every (hour, origin) row holds at most 512 non-zero entries and the sparse
+                                   pack of the longest row is at most 60 % of the dense one (tables of fewer than ~400 zones never do: their
+                                   dense packs are at the 1 KiB floor already); otherwise, and with 0 (default), the dense packs.  Read when a
+                                   table is installed: the installed one keeps its form.  The counts do not depend on it */
 #define CPM_OPT_PROFILE_KERNEL 3 /* which hourly launch CPM_OPT_PROFILE brackets: */
 #define CPM_PROFILE_SAMPLER 0   /*   the sampler (default; every kernel family has one) */
 #define CPM_PROFILE_PLACE 1     /*   the grouped path's placing kernel */
 #define CPM_PROFILE_TRAVEL 2    /*   the grouped path's travel-time kernel (CPM_FLAG_TRAVEL) */
+#define CPM_PROFILE_UPLOAD 3    /*   not an hourly launch: the two kernels of a sparse upload (CPM_OPT_SPARSE_UPLOAD: compact, pack), per cpm_set_p_dest */
 
 typedef struct cpm_ctx cpm_ctx;
 
@@ -114,9 +121,10 @@ int32_t cpm_set_option(cpm_ctx *ctx, int32_t option, int64_t value);
 #define CPM_INFO_CAP_MULT 2
 #define CPM_INFO_PARTS 3   /* workgroups per zone of the grouped sampler: 1, or more once a bucket above FOUR times a workgroup's slots was seen
                             * (kHeavy in cpm_grouped.h; lighter overflow stays with the overflow rounds of the zone's own workgroup) */
-#define CPM_INFO_SPARSE_TABLES 6  /* 0, or -- the installed p_destin tables were built from a sparse datamatrix's compact rows (csrc/cpm_dataset.h:
-                                   * cpm_build_p_dest on a datamatrix whose longest (origin, hour) row holds at most 512 cells and whose sparse
-                                   * row pack is at most 60 % of the dense one) -- the 32-bit words of one sparse row pack */
+#define CPM_INFO_SPARSE_TABLES 6  /* 0, or -- the installed p_destin tables have sparse row packs -- the 32-bit words of one such pack.  Two routes
+                                   * lead there: cpm_build_p_dest on a sparse datamatrix (csrc/cpm_dataset.h: its longest (origin, hour) row holds
+                                   * at most 512 cells and the sparse row pack is at most 60 % of the dense one), and cpm_set_p_dest with
+                                   * CPM_OPT_SPARSE_UPLOAD on an array that meets the same rule (csrc/cpm_upload.h); 0 after a fallback to dense packs */
 #define CPM_INFO_FUSED_BAILOUTS 5 /* steps so far that came back with status bit 2 (a block of a one-launch form gave up waiting: the context then keeps to two launches per hour) */
 #define CPM_INFO_FUSED 4   /* 1 (3: in its placing-first form, 6: all hours in one launch) when the next grouped step runs the fused hour (one launch per hour), 0 when it takes two launches per hour: switched
                             * off (CPM_OPT_FUSED), heavy buckets seen (CPM_INFO_PARTS > 1), rows / groups outside the fused instantiations, or

@@ -39,10 +39,15 @@ _seed() = isdefined(Main, :CPM_SEED) ? UInt64(Main.CPM_SEED) : UInt64(0x5EEDCA12
 _dev() = isdefined(Main, :CPM_DEVICE) ? Int(Main.CPM_DEVICE) : 0
 _trust() = isdefined(Main, :CPM_TRUST_UNCHANGED) && Main.CPM_TRUST_UNCHANGED === true
 
+const CPM_OPT_SPARSE_UPLOAD = Cint(7)   # include/cpm.h
+
 function context(Z::Integer, T::Integer=_T(), device::Integer=_dev())
     get!(_ctx, (Int(Z), Int(T), Int(device))) do
         h = Ref{Ptr{Cvoid}}(C_NULL)
         _check(ccall((:cpm_create, libcpm), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Cint), h, Z, T, device))
+        # sparse row packs for the p_dest arrays _install hands over (a table the user edited, loaded or built with the reference's own
+        # createpdestin is as sparse as the datamatrix): dense packs where a table does not qualify, the same counts either way
+        _check(ccall((:cpm_set_option, libcpm), Cint, (Ptr{Cvoid}, Cint, Int64), h[], CPM_OPT_SPARSE_UPLOAD, 1))
         Ctx(h[], Int(Z), Int(T), Dict{Symbol,Tuple{UInt,Tuple,UInt64,UInt64}}())
     end
 end
