@@ -26,11 +26,15 @@ SYMBOLS = [
 # every symbol include/cpm_batch.h declares (checked by tests/test_batch_host.py); kept apart: SYMBOLS is cpm.h's list
 BATCH_SYMBOLS = ["cpm_set_p_drive_batch", "cpm_build_p_drive_batch", "cpm_get_p_drive_batch", "cpm_resample_batch", "cpm_resample_batch_dev"]
 
+# every symbol include/cpm_flows.h declares (checked by tests/test_flows.py); kept apart like the batch list
+FLOWS_SYMBOLS = ["cpm_resample_flows", "cpm_resample_flows_dev"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
 CPM_OPT_KERNEL, CPM_OPT_PROFILE, CPM_OPT_PROFILE_KERNEL, CPM_OPT_FUSED, CPM_OPT_FUSED_LAG, CPM_OPT_ZONE_ORDER = 1, 2, 3, 4, 5, 6
 CPM_OPT_SPARSE_UPLOAD = 7  # set_p_dest: sparse row packs for an uploaded p_destin that qualifies (include/cpm.h)
+CPM_OPT_FLOWS_KEPT = 16  # include/cpm_flows.h: the OD kernel once per resample over the kept runs of all hours (1) or once per hour (0, default)
 CPM_PROFILE_SAMPLER, CPM_PROFILE_PLACE, CPM_PROFILE_TRAVEL, CPM_PROFILE_UPLOAD = 0, 1, 2, 3
 # cpm_get_info keys (include/cpm.h): what the context would run next ...
 CPM_INFO_KERNEL, CPM_INFO_CAP_MULT, CPM_INFO_PARTS, CPM_INFO_FUSED, CPM_INFO_FUSED_BAILOUTS, CPM_INFO_SPARSE_TABLES = 1, 2, 3, 4, 5, 6
@@ -56,6 +60,7 @@ def build(force=False):
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")) or f == "Makefile"]
     srcs.append(os.path.join(_HERE, "..", "include", "cpm.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_batch.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_flows.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -127,7 +132,9 @@ def load():
     L.cpm_get_p_drive_batch.argtypes = [vp, vp]
     L.cpm_resample_batch.argtypes = [vp, vp, u32, vp, vp, vp]
     L.cpm_resample_batch_dev.argtypes = [vp, vp, u32, vp]
-    for name in SYMBOLS + BATCH_SYMBOLS:
+    L.cpm_resample_flows.argtypes = [vp, u64, u32, vp, vp, vp, vp]
+    L.cpm_resample_flows_dev.argtypes = [vp, u64, u32, vp, vp]
+    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

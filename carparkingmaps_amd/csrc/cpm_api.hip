@@ -12,7 +12,9 @@
 #include <vector>
 
 #include "../../include/cpm.h"
+#include "../../include/cpm_flows.h"
 #include "cpm_kernels.h"
+#include "cpm_flows.h"
 #include "cpm_tables.h"
 #include "cpm_exact.h"
 #include "cpm_grouped.h"
@@ -129,6 +131,7 @@ struct cpm_ctx {
     uint32_t *d_zone0 = nullptr;  // [n] current zones
     uint32_t *d_ztmp = nullptr;   // [n] ping-pong for the IVP
     uint32_t *d_rec = nullptr;    // [T][n]
+    int32_t *d_flows = nullptr;   // [T][Z][Z] OD trip counts of the blocking cpm_resample_flows (allocated by its first call)
     int64_t rec_cap = 0;
     bool have_state = false;
     // results
@@ -720,7 +723,8 @@ int32_t ensure_travel_tables(cpm_ctx *c)
     return CPM_OK;
 }
 
-int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts)
+// d_flows: nullptr, or DEVICE int32[T][Z][Z] for the OD trip counts of the step (cpm_flows.h), from whatever family produces the counts
+int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, int32_t *d_flows = nullptr)
 {
     if (!c->have_pdrive || !c->have_cdf) return fail(CPM_ERR_STATE, "resample: p_drive / p_dest not set");
     if (!c->have_state) return fail(CPM_ERR_STATE, "resample: no car state (cpm_init_states / cpm_set_state)");
@@ -742,6 +746,8 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     c->last_form = kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
     if (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED)  // (the grouped path zeroes the count tensor with its other counters, in one launch)
         HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * nwords, c->stream));
+    if (d_flows && (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED))  // (k_flows_cars adds to it; k_grouped_flows writes every row itself)
+        HIP_TRY(hipMemsetAsync(d_flows, 0, sizeof(int32_t) * static_cast<size_t>(c->T) * c->Z * c->Z, c->stream));
     if (c->n == 0) return CPM_OK;
     unsigned long long *tt_sum = reinterpret_cast<unsigned long long *>(d_counts) + 2 * c->T * c->Z;
     if (kernel == CPM_KERNEL_ZONE_GROUPED) {
@@ -752,7 +758,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
             if (rc_tt != CPM_OK) return rc_tt;
         }
         int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, travel, d_counts, c->cu_count,
-                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error);
+                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, d_flows);
         if (rc == CPM_OK) c->last_form = c->zg.last_form;
         if (rc == CPM_OK && c->h_status && !c->status_pending) {
             c->h_status[1] = 0;
@@ -770,7 +776,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     if (kernel == CPM_KERNEL_ZONE_LDS) {
         return cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
                               c->d_zone0, seed, travel, c->d_dm, d_counts, c->cu_count, [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); },
-                              g_last_error);
+                              g_last_error, false, nullptr, d_flows);
     }
     int32_t rc = ensure_rec(c);
     if (rc != CPM_OK) return rc;
@@ -781,6 +787,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         rc = launch_step_car(c, zin, out, t, static_cast<uint32_t>(c->T - 1 + t), seed, travel, tt_sum);
         prof_end(c);
         if (rc != CPM_OK) return rc;
+        if (d_flows) HIP_TRY(cpm::flows_launch_cars(c->stream, zin, nullptr, out, c->n, static_cast<int>(c->Z), d_flows + static_cast<size_t>(t) * c->Z * c->Z));
     }
     return launch_histogram(c, d_counts);
 }
@@ -887,9 +894,9 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
 
 // The blocking resample: the count tensor of a valid step in c->h_counts (c->d_counts, status word included).  Leaves c->kernel
 // changed when it had to fall back to a layout that cannot overflow: the caller restores it.
-int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags)
+int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, int32_t *d_flows = nullptr)
 {
-    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts);
+    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows);
     const size_t zt = static_cast<size_t>(c->Z * c->T), nwords = 2 * zt + 2;
     auto fetch = [&]() -> int32_t {  // the count tensor, Σ time and the status word: one copy into pinned memory, one wait
         HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, sizeof(int64_t) * nwords, hipMemcpyDeviceToHost, c->stream));
@@ -903,14 +910,14 @@ int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags)
     // problem still fits (two launches per hour after a bail-out) ...  (each discarded attempt: CPM_INFO_STEPS_REPEATED)
     while (rc == CPM_OK && c->h_counts[nwords - 1] != 0 && pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && absorb_status(c, c->h_counts[nwords - 1])) {
         ++c->steps_repeated;
-        rc = resample_enqueue(c, seed, flags, c->d_counts);
+        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows);
         if (rc == CPM_OK) rc = fetch();
     }
     if (rc == CPM_OK && c->h_counts[nwords - 1] != 0) {  // ... else on a layout that cannot overflow
         ++c->steps_repeated;
         if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED) c->grouped_overflowed = true;
         c->kernel = cpm::exact_path_fits(static_cast<int>(c->Z)) ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
-        rc = resample_enqueue(c, seed, flags, c->d_counts);
+        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows);
         if (rc == CPM_OK) rc = fetch();
     }
     return rc;
@@ -1149,6 +1156,7 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_zone0);
     dfree(c->d_ztmp);
     dfree(c->d_rec);
+    dfree(c->d_flows);
     dfree(c->d_counts);
     dfree(c->d_err);
     c->zx.release();
@@ -1192,6 +1200,10 @@ int32_t cpm_set_option(cpm_ctx *c, int32_t option, int64_t value)
     case CPM_OPT_SPARSE_UPLOAD:
         if (value != 0 && value != 1) return fail(CPM_ERR_ARG, "sparse upload %lld (0 dense row packs, 1 sparse where the table qualifies)", (long long)value);
         c->sparse_upload = value != 0;  // (read when a table is installed: the installed one stays as it is)
+        return CPM_OK;
+    case CPM_OPT_FLOWS_KEPT:
+        if (value != 0 && value != 1) return fail(CPM_ERR_ARG, "flows form %lld (0 one launch per hour, 1 one launch over the kept runs of all hours)", (long long)value);
+        c->zg.flows_kept = value != 0;
         return CPM_OK;
     case CPM_OPT_PROFILE_KERNEL:
         if (value < CPM_PROFILE_SAMPLER || value > CPM_PROFILE_UPLOAD) return fail(CPM_ERR_ARG, "profile kernel %lld", (long long)value);
@@ -1872,6 +1884,43 @@ int32_t cpm_resample(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking
         dfree(d_cols);
         if (e != hipSuccess) return fail(CPM_ERR_HIP, "compat export: %s", hipGetErrorString(e));
     }
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ OD trip counts (include/cpm_flows.h)
+int32_t cpm_resample_flows_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, void *d_counts, void *d_flows)
+{
+    CTX_TRY(c);
+    if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
+    if (!d_flows) return fail(CPM_ERR_ARG, "null d_flows");
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), static_cast<int32_t *>(d_flows));
+}
+
+int32_t cpm_resample_flows(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, int32_t *flows_out)
+{
+    CTX_TRY(c);
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
+    if (!flows_out) return fail(CPM_ERR_ARG, "null flows_out");
+    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
+        cpm_ctx *c;
+        int saved;
+        ~KernelGuard() { c->kernel = saved; }
+    } kernel_guard{c, c->kernel};
+    {
+        int32_t rc_ivp = finish_ivp(c);
+        if (rc_ivp != CPM_OK) return rc_ivp;
+    }
+    const size_t cells = static_cast<size_t>(c->T) * c->Z * c->Z;
+    if (!c->d_flows) HIP_TRY(hipMalloc(&c->d_flows, sizeof(int32_t) * std::max<size_t>(cells, 1)));
+    int32_t rc = resample_blocking(c, seed, flags, c->d_flows);
+    if (rc != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z * c->T);
+    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
+    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
+    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    // (the flows of the attempt whose counts were fetched: every attempt writes the whole array, and the last one enqueued is the one returned)
+    HIP_TRY(hipMemcpyAsync(flows_out, c->d_flows, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
 }
 

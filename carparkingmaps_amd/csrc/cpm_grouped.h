@@ -36,6 +36,7 @@
 
 #include "../../include/cpm.h"
 #include "cpm_kernels.h"
+#include "cpm_flows.h"
 
 namespace cpm {
 
@@ -2740,6 +2741,7 @@ struct GroupedWork {
     int parts = 1;                                               // workgroups per heavy zone: 1 + blocks of the heavy kernel (set_parts)
     int hgrid = 0;                                               // zones the heavy launch covers
     const uint32_t *ivp_ids = nullptr, *ivp_cnt = nullptr;       // final buckets of the last IVP (grouped_commit_ivp)
+    bool flows_kept = false;                                     // OD trip counts (cpm_flows.h) from the kept runs of all hours in one launch (CPM_OPT_FLOWS_KEPT), not hour by hour
     int last_form = -1;                                          // form the applied hours of the last run took (CPM_INFO_LAST_FORM coding: 0 two
                                                                  // launches, 1 one, 3 placing first, 6 all in one launch), from grouped_run's decision
 
@@ -2895,8 +2897,9 @@ __global__ __launch_bounds__(256) void k_grouped_zero(unsigned long long *__rest
 template <typename F1, typename F2>
 int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb, int64_t n, CarIndex cars, const uint32_t *d_zone0,
                     uint64_t seed, bool travel, int64_t *d_counts, int cu_count, F1 prof_begin, F2 prof_end, std::string &err, bool ivp = false,
-                    uint32_t *d_zone0_out = nullptr)
+                    uint32_t *d_zone0_out = nullptr, int32_t *d_flows = nullptr)
 {
+    static_assert(kFlowRuns == kGroups, "k_grouped_flows reads the runs of cpm_grouped.h");
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP;
@@ -2916,7 +2919,11 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     unsigned long long *tt_sum = parking + 2 * static_cast<size_t>(T) * Z;
     unsigned long long *status = tt_sum + 1;
     // travel times: from the runs, by one launch per hour -- or, when the runs of all hours fit, by one launch at the end
-    const bool history = travel && !ivp && w.ensure_history();
+    // OD trip counts (cpm_flows.h, d_flows: int32[T][Z][Z]): from the same runs.  By one launch per hour (the default: measured)
+    // unless the runs are kept anyway (travel times), the context asks for the kept form (flows_kept), or the day launch runs,
+    // which has no hourly boundary to launch behind -- what a travel resample does under the same mode
+    const bool flows = d_flows != nullptr && !ivp;
+    const bool history = (travel || (flows && (w.flows_kept || w.fused_day))) && !ivp && w.ensure_history();
     const int G = tb.G;
     const size_t rw = static_cast<size_t>(pack_row_words(tb.Zq, G, tb.smap));
     const int64_t mean = (n + Z - 1) / Z;
@@ -2925,7 +2932,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     const bool shape = w.fused_ok && w.parts <= 1 && fused_shape_ok(Z, tb.Zq, G, tb.smap) && (!w.fused_auto || fused_pays(Z, tb.Zq, G, cu_count, tb.smap, mean));
     // ... and one launch for ALL hours that are applied (k_grouped_day): the IVP's T - 1, a resample's first T - 1 (hour T is sampled,
     // never applied: the plain form behind the placing of hour T - 1, k_grouped_hour_pf); hourly travel launches need hourly boundaries
-    const int day_n = (shape && w.fused_day && w.cap < (1u << kCntXccShift) && (!travel || history)) ? (ivp ? hours : hours - 1) : 0;
+    const int day_n = (shape && w.fused_day && w.cap < (1u << kCntXccShift) && (!(travel || flows) || history)) ? (ivp ? hours : hours - 1) : 0;
     const int nchunk = (Z + kFusedChunk - 1) / kFusedChunk;
     GroupedDay day{};
     auto hour_base = [&](GroupedArgs &a) {  // what all hours of a run share
@@ -3034,7 +3041,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         // hour T of a resample is sampled, never applied (src/resampling.jl:81-83): counts only -- unless its travel times are wanted,
         // which are computed from the runs
         const bool last_hour = !ivp && t + 1 == T;
-        const bool grouped = !last_hour || travel || w.parts > 1;  // (heavy buckets: the grouped form splits them over workgroups, the plain one walks them)
+        const bool grouped = !last_hour || travel || flows || w.parts > 1;  // (heavy buckets: the grouped form splits them over workgroups, the plain one walks them)
         uint32_t *cnt_next = w.cnt + static_cast<size_t>(t + 1) * 2 * Z;  // stayers; the arrivals Z words behind
         uint32_t *ids_next = (t & 1) ? w.idsB : w.idsA;
         GroupedArgs a;
@@ -3110,9 +3117,17 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
             else launch(k_grouped_travel<false>, dim3(Z, 1), dim3(travel_block(mean, w.parts > 1)), 0, stream, a.D, a.cntg, Z, w.scap, w.idbits, tr);
             prof_end(CPM_PROFILE_TRAVEL);
         }
+        if (flows && !history) {  // (grouped: the hour's drivers are in their runs, placed or pending)
+            const int32_t rc_fl = flows_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, 0, 0, t, 1, d_flows, err);
+            if (rc_fl != CPM_OK) return rc_fl;
+        }
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "grouped zone hour launch");
     }
-    if (history) {  // every hour's drivers are still in their runs: one launch
+    if (flows && history) {  // the kept runs of all hours: one launch, grid (Z, T)
+        const int32_t rc_fl = flows_launch_grouped(stream, w.Dq, w.cntg, Z, w.scap, w.idbits, w.zpg, w.run_words(), w.len_words(), 0, T, d_flows, err);
+        if (rc_fl != CPM_OK) return rc_fl;
+    }
+    if (travel && history) {  // every hour's drivers are still in their runs: one launch
         TravelArgs tr{};
         tr.tt = tb.tt;
         tr.tts_words = tb.tts_words;

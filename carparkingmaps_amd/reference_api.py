@@ -415,10 +415,11 @@ def saveresults(number_zones, state_matrix, transition_matrix, path_to_results, 
 
 
 # ------------------------------------------------------------------------------- fused fast path
-def run_dataset(datamatrix, distance_matrix_km, number_zones, travel=True):
+def run_dataset(datamatrix, distance_matrix_km, number_zones, travel=True, flows=False):
     """main.jl:79-102 for one dataset without materialising the C x T matrices on the host:
     tables -> initializestates -> IVP -> resampling -> counts.  Returns dict(parking_density,
-    traffic_activity, A_drive_increment, parking, driving)."""
+    traffic_activity, A_drive_increment, parking, driving); flows=True adds `flows`, the hourly OD trip counts
+    (Sampler.resample: (T, Z, Z) int32, flows[t, o, d])."""
     s, key = _sampler(number_zones)
     Z, T = int(number_zones), params.T
     C = Z * params.cars_per_zone
@@ -429,9 +430,12 @@ def run_dataset(datamatrix, distance_matrix_km, number_zones, travel=True):
     _loaded[key].pop("p_dest", None)
     s.init_states(C, params.cars_per_zone)
     s.solve_ivp(params.seed, want=False)
-    r = s.resample(params.seed, travel=travel)
+    r = s.resample(params.seed, travel=travel, flows=True) if flows else s.resample(params.seed, travel=travel)
     traffic = r["driving"].astype(np.float64).sum(axis=0)
     with np.errstate(all="ignore"):
         traffic = (traffic - traffic.min()) / (traffic.max() - traffic.min())
-    return dict(parking=r["parking"], driving=r["driving"], parking_density=r["parking"] / C,
-                traffic_activity=traffic, A_drive_increment=(r["sum_tt_q16"] / 65536.0) / (C * T * 3600.0))
+    out = dict(parking=r["parking"], driving=r["driving"], parking_density=r["parking"] / C,
+               traffic_activity=traffic, A_drive_increment=(r["sum_tt_q16"] / 65536.0) / (C * T * 3600.0))
+    if flows:
+        out["flows"] = r["flows"]
+    return out

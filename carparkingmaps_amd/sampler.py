@@ -233,10 +233,21 @@ class Sampler:
     def solve_ivp_async(self, seed):
         _lib.check(self._L.cpm_solve_ivp_async(self._h, int(seed)))
 
-    def resample(self, seed, travel=False, want_state=False, want_trans=False):
-        """Returns dict(parking, driving: (Z,T) int64 F-order; sum_tt_q16: int; state, trans or None)."""
+    def resample(self, seed, travel=False, want_state=False, want_trans=False, flows=False):
+        """Returns dict(parking, driving: (Z,T) int64 F-order; sum_tt_q16: int; state, trans or None).
+        flows=True (include/cpm_flows.h): the dict gains `flows`, the OD trip counts of every hour: (T, Z, Z) int32, C order,
+        flows[t, o, d] = cars that drove from zone o + 1 to zone d + 1 in hour t + 1 (trips inside a zone on the diagonal), from the
+        kernel family that produced the counts.  Not together with want_state / want_trans, which force the per-car kernels."""
         parking = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
         driving = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
+        if flows:
+            if want_state or want_trans:
+                raise ValueError("flows=True cannot be combined with want_state / want_trans")
+            out = self.flows_empty()
+            tt = C.c_int64(0)
+            _lib.check(self._L.cpm_resample_flows(self._h, int(seed), _lib.CPM_FLAG_TRAVEL if travel else 0, _vp(parking), _vp(driving),
+                                                  C.cast(C.byref(tt), C.c_void_p), _vp(out)))
+            return dict(parking=parking, driving=driving, sum_tt_q16=int(tt.value), state=None, trans=None, flows=out)
         state = np.zeros((self.car_count, self.T), dtype=np.int64, order="F") if want_state else None
         trans = np.zeros((self.car_count, self.T, 4), dtype=np.float64, order="F") if want_trans else None
         tt = C.c_int64(0)
@@ -253,6 +264,26 @@ class Sampler:
 
     def counts_words(self):
         return 2 * self.T * self.Z + 2
+
+    # -- OD trip counts (include/cpm_flows.h) --
+    def flows_words(self):
+        """int32 words of the flows tensor: T * Z * Z."""
+        return self.T * self.Z * self.Z
+
+    def flows_empty(self):
+        """The host array resample(flows=True) fills: (T, Z, Z) int32, C order (the library writes every word)."""
+        return np.empty((self.T, self.Z, self.Z), dtype=np.int32, order="C")
+
+    def resample_flows_dev(self, seed, d_counts_ptr, d_flows_ptr, travel=False):
+        """Enqueue on the context's stream; d_counts_ptr as for resample_dev, d_flows_ptr = device address of int32[T*Z*Z]
+        (flows[t][o][d]).  A non-zero status word in the count tensor invalidates the flows as well: repeat the step."""
+        flags = _lib.CPM_FLAG_TRAVEL if travel else 0
+        _lib.check(self._L.cpm_resample_flows_dev(self._h, int(seed), flags, C.c_void_p(int(d_counts_ptr)), C.c_void_p(int(d_flows_ptr))))
+
+    def set_flows_kept(self, on=True):
+        """How the grouped family computes the flows: one launch over the kept runs of all hours (True) or one behind every hour
+        (False, the library's default; measured in DESIGN.md 8).  The flows do not depend on it."""
+        _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_FLOWS_KEPT, 1 if on else 0))
 
     # -- batches (include/cpm_batch.h): B fleets, each with its own p_drive and seed, from this context's state and p_destin --
     def set_p_drive_batch(self, p_drives):
