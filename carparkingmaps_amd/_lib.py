@@ -29,6 +29,9 @@ BATCH_SYMBOLS = ["cpm_set_p_drive_batch", "cpm_build_p_drive_batch", "cpm_get_p_
 # every symbol include/cpm_flows.h declares (checked by tests/test_flows.py); kept apart like the batch list
 FLOWS_SYMBOLS = ["cpm_resample_flows", "cpm_resample_flows_dev"]
 
+# every symbol include/cpm_flows_csr.h declares (checked by tests/test_flows_csr.py); a header and a list of its own, likewise
+FLOWS_CSR_SYMBOLS = ["cpm_resample_flows_csr_dev", "cpm_resample_flows_csr", "cpm_get_flows_csr"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -61,6 +64,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_batch.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_flows.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_flows_csr.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -134,7 +138,10 @@ def load():
     L.cpm_resample_batch_dev.argtypes = [vp, vp, u32, vp]
     L.cpm_resample_flows.argtypes = [vp, u64, u32, vp, vp, vp, vp]
     L.cpm_resample_flows_dev.argtypes = [vp, u64, u32, vp, vp]
-    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS:
+    L.cpm_resample_flows_csr_dev.argtypes = [vp, u64, u32, vp, vp, vp, vp, i64]
+    L.cpm_resample_flows_csr.argtypes = [vp, u64, u32, vp, vp, vp, vp, C.POINTER(i64)]
+    L.cpm_get_flows_csr.argtypes = [vp, vp, vp, i64]
+    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

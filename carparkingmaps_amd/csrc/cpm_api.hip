@@ -13,8 +13,10 @@
 
 #include "../../include/cpm.h"
 #include "../../include/cpm_flows.h"
+#include "../../include/cpm_flows_csr.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
+#include "cpm_flows_csr.h"
 #include "cpm_tables.h"
 #include "cpm_exact.h"
 #include "cpm_grouped.h"
@@ -132,6 +134,13 @@ struct cpm_ctx {
     uint32_t *d_ztmp = nullptr;   // [n] ping-pong for the IVP
     uint32_t *d_rec = nullptr;    // [T][n]
     int32_t *d_flows = nullptr;   // [T][Z][Z] OD trip counts of the blocking cpm_resample_flows (allocated by its first call)
+    // the same counts as compressed sparse rows (include/cpm_flows_csr.h): the blocking call's arrays, allocated by its first call
+    int64_t *d_csr_row_ptr = nullptr;  // [T*Z + 1]
+    int32_t *d_csr_dest = nullptr;     // [csr_cap]
+    int32_t *d_csr_count = nullptr;    // [csr_cap]
+    int64_t csr_cap = 0;
+    int64_t csr_nnz = -1;              // what the last blocking call reported (-1: there was none)
+    int32_t *d_flows_hour = nullptr;   // [Z*Z + 4] one hour's dense block: how the per-car families reach the CSR form
     int64_t rec_cap = 0;
     bool have_state = false;
     // results
@@ -723,9 +732,11 @@ int32_t ensure_travel_tables(cpm_ctx *c)
     return CPM_OK;
 }
 
-// d_flows: nullptr, or DEVICE int32[T][Z][Z] for the OD trip counts of the step (cpm_flows.h), from whatever family produces the counts
-int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, int32_t *d_flows = nullptr)
+// fd: where the OD trip counts of the step go, from whatever family produces the counts: nowhere, DEVICE int32[T][Z][Z] (cpm_flows.h)
+// or DEVICE CSR arrays (cpm_flows_csr.h)
+int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, cpm::FlowsDest fd = cpm::FlowsDest{})
 {
+    int32_t *const d_flows = fd.dense;
     if (!c->have_pdrive || !c->have_cdf) return fail(CPM_ERR_STATE, "resample: p_drive / p_dest not set");
     if (!c->have_state) return fail(CPM_ERR_STATE, "resample: no car state (cpm_init_states / cpm_set_state)");
     {
@@ -748,7 +759,13 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * nwords, c->stream));
     if (d_flows && (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED))  // (k_flows_cars adds to it; k_grouped_flows writes every row itself)
         HIP_TRY(hipMemsetAsync(d_flows, 0, sizeof(int32_t) * static_cast<size_t>(c->T) * c->Z * c->Z, c->stream));
+    if (fd.csr() && c->n == 0)  // (no car, no trip: every row is empty)
+        HIP_TRY(hipMemsetAsync(fd.row_ptr, 0, sizeof(int64_t) * (static_cast<size_t>(c->T) * c->Z + 1), c->stream));
     if (c->n == 0) return CPM_OK;
+    if (fd.csr() && kernel != CPM_KERNEL_ZONE_GROUPED) {  // (k_flows_cars adds to a dense hour block, k_flows_csr_from_dense takes it apart)
+        if (!c->d_flows_hour) HIP_TRY(hipMalloc(&c->d_flows_hour, sizeof(int32_t) * (static_cast<size_t>(c->Z) * c->Z + 4)));
+        fd.hour_block = c->d_flows_hour;
+    }
     unsigned long long *tt_sum = reinterpret_cast<unsigned long long *>(d_counts) + 2 * c->T * c->Z;
     if (kernel == CPM_KERNEL_ZONE_GROUPED) {
         if (!grouped_fits(c, c->zg.cap_mult))
@@ -758,7 +775,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
             if (rc_tt != CPM_OK) return rc_tt;
         }
         int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, travel, d_counts, c->cu_count,
-                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, d_flows);
+                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd);
         if (rc == CPM_OK) c->last_form = c->zg.last_form;
         if (rc == CPM_OK && c->h_status && !c->status_pending) {
             c->h_status[1] = 0;
@@ -776,7 +793,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     if (kernel == CPM_KERNEL_ZONE_LDS) {
         return cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
                               c->d_zone0, seed, travel, c->d_dm, d_counts, c->cu_count, [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); },
-                              g_last_error, false, nullptr, d_flows);
+                              g_last_error, false, nullptr, fd);
     }
     int32_t rc = ensure_rec(c);
     if (rc != CPM_OK) return rc;
@@ -787,7 +804,10 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         rc = launch_step_car(c, zin, out, t, static_cast<uint32_t>(c->T - 1 + t), seed, travel, tt_sum);
         prof_end(c);
         if (rc != CPM_OK) return rc;
-        if (d_flows) HIP_TRY(cpm::flows_launch_cars(c->stream, zin, nullptr, out, c->n, static_cast<int>(c->Z), d_flows + static_cast<size_t>(t) * c->Z * c->Z));
+        if (fd.any()) {
+            rc = cpm::flows_hour_from_cars(c->stream, fd, zin, nullptr, out, c->n, static_cast<int>(c->Z), t, g_last_error);
+            if (rc != CPM_OK) return rc;
+        }
     }
     return launch_histogram(c, d_counts);
 }
@@ -894,7 +914,7 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
 
 // The blocking resample: the count tensor of a valid step in c->h_counts (c->d_counts, status word included).  Leaves c->kernel
 // changed when it had to fall back to a layout that cannot overflow: the caller restores it.
-int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, int32_t *d_flows = nullptr)
+int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsDest d_flows = cpm::FlowsDest{})
 {
     int32_t rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows);
     const size_t zt = static_cast<size_t>(c->Z * c->T), nwords = 2 * zt + 2;
@@ -1157,6 +1177,10 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_ztmp);
     dfree(c->d_rec);
     dfree(c->d_flows);
+    dfree(c->d_csr_row_ptr);
+    dfree(c->d_csr_dest);
+    dfree(c->d_csr_count);
+    dfree(c->d_flows_hour);
     dfree(c->d_counts);
     dfree(c->d_err);
     c->zx.release();
@@ -1893,7 +1917,9 @@ int32_t cpm_resample_flows_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, void *
     CTX_TRY(c);
     if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
     if (!d_flows) return fail(CPM_ERR_ARG, "null d_flows");
-    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), static_cast<int32_t *>(d_flows));
+    cpm::FlowsDest fd;
+    fd.dense = static_cast<int32_t *>(d_flows);
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), fd);
 }
 
 int32_t cpm_resample_flows(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, int32_t *flows_out)
@@ -1912,7 +1938,9 @@ int32_t cpm_resample_flows(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     }
     const size_t cells = static_cast<size_t>(c->T) * c->Z * c->Z;
     if (!c->d_flows) HIP_TRY(hipMalloc(&c->d_flows, sizeof(int32_t) * std::max<size_t>(cells, 1)));
-    int32_t rc = resample_blocking(c, seed, flags, c->d_flows);
+    cpm::FlowsDest fd;
+    fd.dense = c->d_flows;
+    int32_t rc = resample_blocking(c, seed, flags, fd);
     if (rc != CPM_OK) return rc;
     const size_t zt = static_cast<size_t>(c->Z * c->T);
     std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
@@ -1920,6 +1948,95 @@ int32_t cpm_resample_flows(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
     // (the flows of the attempt whose counts were fetched: every attempt writes the whole array, and the last one enqueued is the one returned)
     HIP_TRY(hipMemcpyAsync(flows_out, c->d_flows, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ OD trip counts as compressed sparse rows (include/cpm_flows_csr.h)
+int32_t cpm_resample_flows_csr_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, void *d_counts, void *d_row_ptr, void *d_dest, void *d_count, int64_t cap)
+{
+    CTX_TRY(c);
+    if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
+    if (!d_row_ptr) return fail(CPM_ERR_ARG, "null d_row_ptr");
+    if (cap < 0) return fail(CPM_ERR_ARG, "negative cap");
+    if (cap > 0 && (!d_dest || !d_count)) return fail(CPM_ERR_ARG, "null d_dest / d_count with cap > 0");
+    cpm::FlowsDest fd;
+    fd.row_ptr = static_cast<int64_t *>(d_row_ptr);
+    fd.dest = static_cast<int32_t *>(d_dest);
+    fd.count = static_cast<int32_t *>(d_count);
+    fd.cap = cap;
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), fd);
+}
+
+int32_t cpm_resample_flows_csr(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, int64_t *row_ptr_out,
+                               int64_t *nnz_out)
+{
+    CTX_TRY(c);
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
+    if (!row_ptr_out || !nnz_out) return fail(CPM_ERR_ARG, "null row_ptr_out / nnz_out");
+    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
+        cpm_ctx *c;
+        int saved;
+        ~KernelGuard() { c->kernel = saved; }
+    } kernel_guard{c, c->kernel};
+    {
+        int32_t rc_ivp = finish_ivp(c);
+        if (rc_ivp != CPM_OK) return rc_ivp;
+    }
+    c->csr_nnz = -1;
+    const size_t zt = static_cast<size_t>(c->Z * c->T);
+    if (!c->d_csr_row_ptr) HIP_TRY(hipMalloc(&c->d_csr_row_ptr, sizeof(int64_t) * (zt + 1)));
+    // T * min(n, Z * Z) entries always suffice.  The arrays start at that bound, or at 1 GiB for the two where the bound is larger;
+    // a step that needs more tells by row_ptr[T * Z], which is exact whatever the capacity, and is run again on arrays of that size.
+    auto ensure_entries = [&](int64_t want) -> int32_t {
+        if (want <= c->csr_cap) return CPM_OK;
+        dfree(c->d_csr_dest);
+        dfree(c->d_csr_count);
+        c->d_csr_dest = c->d_csr_count = nullptr;
+        c->csr_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_csr_dest, sizeof(int32_t) * static_cast<size_t>(want)));
+        HIP_TRY(hipMalloc(&c->d_csr_count, sizeof(int32_t) * static_cast<size_t>(want)));
+        c->csr_cap = want;
+        return CPM_OK;
+    };
+    const int64_t bound = static_cast<int64_t>(c->T) * std::min<int64_t>(c->n, static_cast<int64_t>(c->Z) * c->Z);
+    int32_t rc = ensure_entries(std::max<int64_t>(std::min<int64_t>(bound, (int64_t{1} << 30) / 8), 1));
+    if (rc != CPM_OK) return rc;
+    for (int attempt = 0;; ++attempt) {
+        cpm::FlowsDest fd;
+        fd.row_ptr = c->d_csr_row_ptr;
+        fd.dest = c->d_csr_dest;
+        fd.count = c->d_csr_count;
+        fd.cap = c->csr_cap;
+        rc = resample_blocking(c, seed, flags, fd);
+        if (rc != CPM_OK) return rc;
+        // (the rows of the attempt whose counts were fetched: every attempt writes all of row_ptr, and the last one enqueued is the one returned)
+        HIP_TRY(hipMemcpyAsync(row_ptr_out, c->d_csr_row_ptr, sizeof(int64_t) * (zt + 1), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const int64_t nnz = row_ptr_out[zt];
+        if (nnz < 0 || nnz > bound) return fail(CPM_ERR_HIP, "flows (csr): %lld entries reported, at most %lld possible", (long long)nnz, (long long)bound);
+        if (nnz <= c->csr_cap) break;
+        if (attempt > 0) return fail(CPM_ERR_HIP, "flows (csr): %lld entries after a run that reported fewer", (long long)nnz);
+        rc = ensure_entries(nnz);  // (the step is a pure function of seed and state: the repeat needs exactly as many)
+        if (rc != CPM_OK) return rc;
+    }
+    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
+    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
+    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    c->csr_nnz = row_ptr_out[zt];
+    *nnz_out = c->csr_nnz;
+    return CPM_OK;
+}
+
+int32_t cpm_get_flows_csr(cpm_ctx *c, int32_t *dest_out, int32_t *count_out, int64_t nnz)
+{
+    CTX_TRY(c);
+    if (c->csr_nnz < 0) return fail(CPM_ERR_ARG, "cpm_get_flows_csr: no cpm_resample_flows_csr before it");
+    if (nnz != c->csr_nnz) return fail(CPM_ERR_ARG, "cpm_get_flows_csr: nnz %lld, the last cpm_resample_flows_csr reported %lld", (long long)nnz, (long long)c->csr_nnz);
+    if (nnz > 0 && (!dest_out || !count_out)) return fail(CPM_ERR_ARG, "null dest_out / count_out");
+    if (nnz == 0) return CPM_OK;
+    HIP_TRY(hipMemcpyAsync(dest_out, c->d_csr_dest, sizeof(int32_t) * static_cast<size_t>(nnz), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(count_out, c->d_csr_count, sizeof(int32_t) * static_cast<size_t>(nnz), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
 }

@@ -28,6 +28,7 @@
 #include "../../include/cpm.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
+#include "cpm_flows_csr.h"
 
 namespace cpm {
 
@@ -465,7 +466,7 @@ inline void exact_launch_sample(hipStream_t stream, const uint32_t *ids, const u
 template <typename F1, typename F2>
 int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, const double *d_cdf, int Z, int Zp, int T, int64_t n, CarIndex cars,
                   const uint32_t *d_zone0, uint64_t seed, bool travel, const double *d_dm, int64_t *d_counts, int cu_count, F1 prof_begin,
-                  F2 prof_end, std::string &err, bool ivp = false, uint32_t *d_zone0_out = nullptr, int32_t *d_flows = nullptr)
+                  F2 prof_end, std::string &err, bool ivp = false, uint32_t *d_zone0_out = nullptr, FlowsDest fd = FlowsDest{})
 {
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
@@ -514,9 +515,11 @@ int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, cons
             exact_launch_sample<false>(stream, ids, off, w.dest, pd, cdf, Z, Zp, cars, step, seed, parking + static_cast<size_t>(t) * Z,
                                        driving + static_cast<size_t>(t) * Z, d_dm, T, t, tt_sum);
         prof_end(CPM_PROFILE_SAMPLER);
-        // OD trip counts (cpm_flows.h): the hour's records lie bucket by bucket in w.dest (zeroed output: the caller's)
-        if (d_flows && !ivp && (e = flows_launch_cars(stream, nullptr, off, w.dest, n, Z, d_flows + static_cast<size_t>(t) * Z * Z)) != hipSuccess)
-            return hip_fail(e, "flows of the hour");
+        // OD trip counts (cpm_flows.h, cpm_flows_csr.h): the hour's records lie bucket by bucket in w.dest (zeroed dense output: the caller's)
+        if (fd.any() && !ivp) {
+            const int32_t rc_fl = flows_hour_from_cars(stream, fd, nullptr, off, w.dest, n, Z, t, err);
+            if (rc_fl != CPM_OK) return rc_fl;
+        }
         if (ivp || t + 1 < T) {  // resampling: hour T's transition is sampled but never applied (src/resampling.jl:81-83)
             uint32_t *cur = w.cursor + static_cast<size_t>(t) * Z;
             uint32_t *ids_next = (t & 1) ? w.idsB : w.idsA;

@@ -37,6 +37,7 @@
 #include "../../include/cpm.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
+#include "cpm_flows_csr.h"
 
 namespace cpm {
 
@@ -2897,9 +2898,10 @@ __global__ __launch_bounds__(256) void k_grouped_zero(unsigned long long *__rest
 template <typename F1, typename F2>
 int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb, int64_t n, CarIndex cars, const uint32_t *d_zone0,
                     uint64_t seed, bool travel, int64_t *d_counts, int cu_count, F1 prof_begin, F2 prof_end, std::string &err, bool ivp = false,
-                    uint32_t *d_zone0_out = nullptr, int32_t *d_flows = nullptr)
+                    uint32_t *d_zone0_out = nullptr, FlowsDest fd = FlowsDest{})
 {
     static_assert(kFlowRuns == kGroups, "k_grouped_flows reads the runs of cpm_grouped.h");
+    int32_t *const d_flows = fd.dense;
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP;
@@ -2921,8 +2923,9 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     // travel times: from the runs, by one launch per hour -- or, when the runs of all hours fit, by one launch at the end
     // OD trip counts (cpm_flows.h, d_flows: int32[T][Z][Z]): from the same runs.  By one launch per hour (the default: measured)
     // unless the runs are kept anyway (travel times), the context asks for the kept form (flows_kept), or the day launch runs,
-    // which has no hourly boundary to launch behind -- what a travel resample does under the same mode
-    const bool flows = d_flows != nullptr && !ivp;
+    // which has no hourly boundary to launch behind -- what a travel resample does under the same mode.  The CSR form of the same
+    // counts (cpm_flows_csr.h, fd.row_ptr) takes the dense form's place launch for launch.
+    const bool flows = fd.any() && !ivp;
     const bool history = (travel || (flows && (w.flows_kept || w.fused_day))) && !ivp && w.ensure_history();
     const int G = tb.G;
     const size_t rw = static_cast<size_t>(pack_row_words(tb.Zq, G, tb.smap));
@@ -3118,13 +3121,15 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
             prof_end(CPM_PROFILE_TRAVEL);
         }
         if (flows && !history) {  // (grouped: the hour's drivers are in their runs, placed or pending)
-            const int32_t rc_fl = flows_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, 0, 0, t, 1, d_flows, err);
+            const int32_t rc_fl = fd.csr() ? flows_csr_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, 0, 0, t, 1, fd, err)
+                                           : flows_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, 0, 0, t, 1, d_flows, err);
             if (rc_fl != CPM_OK) return rc_fl;
         }
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "grouped zone hour launch");
     }
     if (flows && history) {  // the kept runs of all hours: one launch, grid (Z, T)
-        const int32_t rc_fl = flows_launch_grouped(stream, w.Dq, w.cntg, Z, w.scap, w.idbits, w.zpg, w.run_words(), w.len_words(), 0, T, d_flows, err);
+        const int32_t rc_fl = fd.csr() ? flows_csr_launch_grouped(stream, w.Dq, w.cntg, Z, w.scap, w.idbits, w.zpg, w.run_words(), w.len_words(), 0, T, fd, err)
+                                       : flows_launch_grouped(stream, w.Dq, w.cntg, Z, w.scap, w.idbits, w.zpg, w.run_words(), w.len_words(), 0, T, d_flows, err);
         if (rc_fl != CPM_OK) return rc_fl;
     }
     if (travel && history) {  // every hour's drivers are still in their runs: one launch

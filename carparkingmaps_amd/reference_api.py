@@ -419,7 +419,8 @@ def run_dataset(datamatrix, distance_matrix_km, number_zones, travel=True, flows
     """main.jl:79-102 for one dataset without materialising the C x T matrices on the host:
     tables -> initializestates -> IVP -> resampling -> counts.  Returns dict(parking_density,
     traffic_activity, A_drive_increment, parking, driving); flows=True adds `flows`, the hourly OD trip counts
-    (Sampler.resample: (T, Z, Z) int32, flows[t, o, d])."""
+    (Sampler.resample: (T, Z, Z) int32, flows[t, o, d]); flows="csr" adds `flows_csr` instead, the same counts without the
+    zeros (Sampler.resample: row_ptr, dest, count, shape; save_flows_csv writes them)."""
     s, key = _sampler(number_zones)
     Z, T = int(number_zones), params.T
     C = Z * params.cars_per_zone
@@ -430,12 +431,28 @@ def run_dataset(datamatrix, distance_matrix_km, number_zones, travel=True, flows
     _loaded[key].pop("p_dest", None)
     s.init_states(C, params.cars_per_zone)
     s.solve_ivp(params.seed, want=False)
-    r = s.resample(params.seed, travel=travel, flows=True) if flows else s.resample(params.seed, travel=travel)
+    r = s.resample(params.seed, travel=travel, flows=flows) if flows else s.resample(params.seed, travel=travel)
     traffic = r["driving"].astype(np.float64).sum(axis=0)
     with np.errstate(all="ignore"):
         traffic = (traffic - traffic.min()) / (traffic.max() - traffic.min())
     out = dict(parking=r["parking"], driving=r["driving"], parking_density=r["parking"] / C,
                traffic_activity=traffic, A_drive_increment=(r["sum_tt_q16"] / 65536.0) / (C * T * 3600.0))
-    if flows:
+    if isinstance(flows, str):
+        out["flows_csr"] = r["flows_csr"]
+    elif flows:
         out["flows"] = r["flows"]
     return out
+
+
+def save_flows_csv(path, csr):
+    """The long-format table of the OD trip counts, beside the result CSVs of saveresults: `hour,origin,destination,trips` with the
+    reference's 1-based ids, one line per non-zero cell in CSR order (hour, then origin, then destination).  csr: the `flows_csr`
+    dict of run_dataset(..., flows="csr") / Sampler.resample(flows="csr").  Returns the number of lines written."""
+    T, Z, _ = csr["shape"]
+    row_ptr = np.asarray(csr["row_ptr"], dtype=np.int64)
+    rows = np.repeat(np.arange(T * Z, dtype=np.int64), np.diff(row_ptr))
+    table = np.stack([rows // Z + 1, rows % Z + 1, np.asarray(csr["dest"], dtype=np.int64) + 1, np.asarray(csr["count"], dtype=np.int64)], axis=1)
+    with open(path, "w") as f:
+        f.write("hour,origin,destination,trips\n")
+        np.savetxt(f, table, fmt="%d", delimiter=",")
+    return int(table.shape[0])

@@ -237,9 +237,26 @@ class Sampler:
         """Returns dict(parking, driving: (Z,T) int64 F-order; sum_tt_q16: int; state, trans or None).
         flows=True (include/cpm_flows.h): the dict gains `flows`, the OD trip counts of every hour: (T, Z, Z) int32, C order,
         flows[t, o, d] = cars that drove from zone o + 1 to zone d + 1 in hour t + 1 (trips inside a zone on the diagonal), from the
-        kernel family that produced the counts.  Not together with want_state / want_trans, which force the per-car kernels."""
+        kernel family that produced the counts.  Not together with want_state / want_trans, which force the per-car kernels.
+        flows="csr" (include/cpm_flows_csr.h): the dict gains `flows_csr` instead, the same counts without the zeros:
+        dict(row_ptr (T*Z + 1,) int64, dest (nnz,) int32, count (nnz,) int32, shape=(T, Z, Z)), row t*Z + o, destinations 0-based and
+        ascending within a row (flows_csr_to_dense, flows_csr_hour)."""
         parking = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
         driving = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
+        if isinstance(flows, str):
+            if flows != "csr":
+                raise ValueError(f"flows={flows!r}: expected False, True or \"csr\"")
+            if want_state or want_trans:
+                raise ValueError("flows=\"csr\" cannot be combined with want_state / want_trans")
+            row_ptr = np.empty(self.T * self.Z + 1, dtype=np.int64)
+            tt, nnz = C.c_int64(0), C.c_int64(0)
+            _lib.check(self._L.cpm_resample_flows_csr(self._h, int(seed), _lib.CPM_FLAG_TRAVEL if travel else 0, _vp(parking), _vp(driving),
+                                                      C.cast(C.byref(tt), C.c_void_p), _vp(row_ptr), C.byref(nnz)))
+            dest = np.empty(nnz.value, dtype=np.int32)    # (sized by the first call, fetched by the second: no guess, no retry)
+            count = np.empty(nnz.value, dtype=np.int32)
+            _lib.check(self._L.cpm_get_flows_csr(self._h, _vp(dest), _vp(count), nnz.value))
+            return dict(parking=parking, driving=driving, sum_tt_q16=int(tt.value), state=None, trans=None,
+                        flows_csr=dict(row_ptr=row_ptr, dest=dest, count=count, shape=(self.T, self.Z, self.Z)))
         if flows:
             if want_state or want_trans:
                 raise ValueError("flows=True cannot be combined with want_state / want_trans")
@@ -279,6 +296,16 @@ class Sampler:
         (flows[t][o][d]).  A non-zero status word in the count tensor invalidates the flows as well: repeat the step."""
         flags = _lib.CPM_FLAG_TRAVEL if travel else 0
         _lib.check(self._L.cpm_resample_flows_dev(self._h, int(seed), flags, C.c_void_p(int(d_counts_ptr)), C.c_void_p(int(d_flows_ptr))))
+
+    def resample_flows_csr_dev(self, seed, d_counts_ptr, d_row_ptr, d_dest, d_count, cap, travel=False):
+        """Enqueue on the context's stream (include/cpm_flows_csr.h); d_counts_ptr as for resample_dev, d_row_ptr = device address of
+        int64[T*Z + 1], d_dest / d_count = device addresses of int32[cap] (0 with cap = 0: size only).  row_ptr is always complete:
+        row_ptr[T*Z] is the size the step needs; entries below cap are valid, nothing is stored behind it.  A non-zero status word in
+        the count tensor invalidates all three arrays: repeat the step."""
+        flags = _lib.CPM_FLAG_TRAVEL if travel else 0
+        _lib.check(self._L.cpm_resample_flows_csr_dev(self._h, int(seed), flags, C.c_void_p(int(d_counts_ptr)), C.c_void_p(int(d_row_ptr)),
+                                                      C.c_void_p(int(d_dest)) if d_dest else None, C.c_void_p(int(d_count)) if d_count else None,
+                                                      int(cap)))
 
     def set_flows_kept(self, on=True):
         """How the grouped family computes the flows: one launch over the kept runs of all hours (True) or one behind every hour
@@ -359,6 +386,26 @@ class Sampler:
         b = C.c_int64(0)
         _lib.check(self._L.cpm_algorithmic_bytes_per_hour(self._h, C.byref(b)))
         return int(b.value)
+
+
+def flows_csr_to_dense(csr):
+    """The (T, Z, Z) int32 tensor resample(flows=True) returns, from the dict of resample(flows="csr") (numpy only)."""
+    T, Z, _ = csr["shape"]
+    row_ptr = np.asarray(csr["row_ptr"], dtype=np.int64)
+    out = np.zeros((T * Z, Z), dtype=np.int32)
+    rows = np.repeat(np.arange(T * Z, dtype=np.int64), np.diff(row_ptr))
+    out[rows, np.asarray(csr["dest"], dtype=np.int64)] = csr["count"]
+    return out.reshape(T, Z, Z)
+
+
+def flows_csr_hour(csr, t):
+    """Hour t (0-based) of the dict of resample(flows="csr"): (indptr (Z + 1,) int64 rebased to 0, indices, data), the last two views,
+    ready for scipy.sparse.csr_matrix((data, indices, indptr), shape=(Z, Z)) -- rows are origins, columns destinations."""
+    T, Z, _ = csr["shape"]
+    if not 0 <= t < T:
+        raise IndexError(f"hour {t} of {T}")
+    p = csr["row_ptr"][t * Z:(t + 1) * Z + 1]
+    return p - p[0], csr["dest"][p[0]:p[-1]], csr["count"][p[0]:p[-1]]
 
 
 def parse_uber_csv(path):
