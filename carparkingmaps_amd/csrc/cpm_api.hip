@@ -14,9 +14,11 @@
 #include "../../include/cpm.h"
 #include "../../include/cpm_flows.h"
 #include "../../include/cpm_flows_csr.h"
+#include "../../include/cpm_stays.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
+#include "cpm_stays.h"
 #include "cpm_tables.h"
 #include "cpm_exact.h"
 #include "cpm_grouped.h"
@@ -141,6 +143,11 @@ struct cpm_ctx {
     int64_t csr_cap = 0;
     int64_t csr_nnz = -1;              // what the last blocking call reported (-1: there was none)
     int32_t *d_flows_hour = nullptr;   // [Z*Z + 4] one hour's dense block: how the per-car families reach the CSR form
+    // parking stays (include/cpm_stays.h): the per-car side array of every stays call, and the blocking call's arrays
+    uint32_t *d_stay_last = nullptr;   // [stay_last_cap] since << 24 | zone (csrc/cpm_stays.h)
+    int64_t stay_last_cap = 0;
+    int32_t *d_stays = nullptr;        // [T][Z][T]
+    int32_t *d_stay_parked = nullptr;  // [Z][T]
     int64_t rec_cap = 0;
     bool have_state = false;
     // results
@@ -733,10 +740,13 @@ int32_t ensure_travel_tables(cpm_ctx *c)
 }
 
 // fd: where the OD trip counts of the step go, from whatever family produces the counts: nowhere, DEVICE int32[T][Z][Z] (cpm_flows.h)
-// or DEVICE CSR arrays (cpm_flows_csr.h)
-int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, cpm::FlowsDest fd = cpm::FlowsDest{})
+// or DEVICE CSR arrays (cpm_flows_csr.h).  sd: where its parking stays go (cpm_stays.h): nowhere, or DEVICE int32[T][Z][T] + int32[Z][T]
+// (sd.last is the context's own side array, set here)
+int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, cpm::FlowsDest fd = cpm::FlowsDest{}, cpm::StaysDest sd = cpm::StaysDest{})
 {
     int32_t *const d_flows = fd.dense;
+    if (sd.any() && c->T > cpm::kStaysMaxT) return fail(CPM_ERR_ARG, "stays: T = %lld, the per-car word keeps an hour in 8 bits (T <= %d)", (long long)c->T, cpm::kStaysMaxT);
+    if (sd.any() && c->Z > static_cast<int64_t>(cpm::kStayZoneMask)) return fail(CPM_ERR_ARG, "stays: Z = %lld, the per-car word keeps a zone in 24 bits", (long long)c->Z);
     if (!c->have_pdrive || !c->have_cdf) return fail(CPM_ERR_STATE, "resample: p_drive / p_dest not set");
     if (!c->have_state) return fail(CPM_ERR_STATE, "resample: no car state (cpm_init_states / cpm_set_state)");
     {
@@ -761,7 +771,29 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         HIP_TRY(hipMemsetAsync(d_flows, 0, sizeof(int32_t) * static_cast<size_t>(c->T) * c->Z * c->Z, c->stream));
     if (fd.csr() && c->n == 0)  // (no car, no trip: every row is empty)
         HIP_TRY(hipMemsetAsync(fd.row_ptr, 0, sizeof(int64_t) * (static_cast<size_t>(c->T) * c->Z + 1), c->stream));
+    if (sd.any()) {  // (k_stays_parked adds to `parked` in every family, k_stays_cars to `stays`; k_grouped_stays writes every row itself)
+        HIP_TRY(hipMemsetAsync(sd.parked, 0, sizeof(int32_t) * static_cast<size_t>(c->Z) * c->T, c->stream));
+        if (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED)
+            HIP_TRY(hipMemsetAsync(sd.stays, 0, sizeof(int32_t) * static_cast<size_t>(c->T) * c->Z * c->T, c->stream));
+    }
     if (c->n == 0) return CPM_OK;
+    if (sd.any()) {  // the side array: every car "here since the day began", at the start of every attempt
+        if (c->stay_last_cap < c->n) {
+            dfree(c->d_stay_last);
+            c->d_stay_last = nullptr;
+            c->stay_last_cap = 0;
+            HIP_TRY(hipMalloc(&c->d_stay_last, sizeof(uint32_t) * static_cast<size_t>(c->n)));
+            c->stay_last_cap = c->n;
+        }
+        sd.last = c->d_stay_last;
+        HIP_TRY(hipMemsetAsync(sd.last, 0, sizeof(uint32_t) * static_cast<size_t>(c->n), c->stream));
+    }
+    // the stays still open at the end of the day: behind the last hour of whichever family ran
+    auto parked_pass = [&](int32_t rc_run) -> int32_t {
+        if (rc_run != CPM_OK || !sd.any()) return rc_run;
+        HIP_TRY(cpm::stays_launch_parked(c->stream, c->d_zone0, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), sd));
+        return CPM_OK;
+    };
     if (fd.csr() && kernel != CPM_KERNEL_ZONE_GROUPED) {  // (k_flows_cars adds to a dense hour block, k_flows_csr_from_dense takes it apart)
         if (!c->d_flows_hour) HIP_TRY(hipMalloc(&c->d_flows_hour, sizeof(int32_t) * (static_cast<size_t>(c->Z) * c->Z + 4)));
         fd.hour_block = c->d_flows_hour;
@@ -775,7 +807,8 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
             if (rc_tt != CPM_OK) return rc_tt;
         }
         int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, travel, d_counts, c->cu_count,
-                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd);
+                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd);
+        rc = parked_pass(rc);
         if (rc == CPM_OK) c->last_form = c->zg.last_form;
         if (rc == CPM_OK && c->h_status && !c->status_pending) {
             c->h_status[1] = 0;
@@ -791,9 +824,9 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         if (rc_cdf != CPM_OK) return rc_cdf;
     }
     if (kernel == CPM_KERNEL_ZONE_LDS) {
-        return cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
-                              c->d_zone0, seed, travel, c->d_dm, d_counts, c->cu_count, [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); },
-                              g_last_error, false, nullptr, fd);
+        return parked_pass(cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
+                                          c->d_zone0, seed, travel, c->d_dm, d_counts, c->cu_count, [&](int what) { prof_begin(c, what); },
+                                          [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd));
     }
     int32_t rc = ensure_rec(c);
     if (rc != CPM_OK) return rc;
@@ -808,8 +841,9 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
             rc = cpm::flows_hour_from_cars(c->stream, fd, zin, nullptr, out, c->n, static_cast<int>(c->Z), t, g_last_error);
             if (rc != CPM_OK) return rc;
         }
+        if (sd.any()) HIP_TRY(cpm::stays_launch_cars(c->stream, nullptr, zin, nullptr, out, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), t, sd));
     }
-    return launch_histogram(c, d_counts);
+    return parked_pass(launch_histogram(c, d_counts));
 }
 
 // the IVP on a layout that cannot overflow: exact buckets when the row fits LDS, one thread per car otherwise
@@ -914,9 +948,9 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
 
 // The blocking resample: the count tensor of a valid step in c->h_counts (c->d_counts, status word included).  Leaves c->kernel
 // changed when it had to fall back to a layout that cannot overflow: the caller restores it.
-int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsDest d_flows = cpm::FlowsDest{})
+int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsDest d_flows = cpm::FlowsDest{}, cpm::StaysDest d_stays = cpm::StaysDest{})
 {
-    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows);
+    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays);
     const size_t zt = static_cast<size_t>(c->Z * c->T), nwords = 2 * zt + 2;
     auto fetch = [&]() -> int32_t {  // the count tensor, Σ time and the status word: one copy into pinned memory, one wait
         HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, sizeof(int64_t) * nwords, hipMemcpyDeviceToHost, c->stream));
@@ -930,14 +964,14 @@ int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsD
     // problem still fits (two launches per hour after a bail-out) ...  (each discarded attempt: CPM_INFO_STEPS_REPEATED)
     while (rc == CPM_OK && c->h_counts[nwords - 1] != 0 && pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && absorb_status(c, c->h_counts[nwords - 1])) {
         ++c->steps_repeated;
-        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows);
+        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays);
         if (rc == CPM_OK) rc = fetch();
     }
     if (rc == CPM_OK && c->h_counts[nwords - 1] != 0) {  // ... else on a layout that cannot overflow
         ++c->steps_repeated;
         if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED) c->grouped_overflowed = true;
         c->kernel = cpm::exact_path_fits(static_cast<int>(c->Z)) ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
-        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows);
+        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays);
         if (rc == CPM_OK) rc = fetch();
     }
     return rc;
@@ -1181,6 +1215,9 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_csr_dest);
     dfree(c->d_csr_count);
     dfree(c->d_flows_hour);
+    dfree(c->d_stay_last);
+    dfree(c->d_stays);
+    dfree(c->d_stay_parked);
     dfree(c->d_counts);
     dfree(c->d_err);
     c->zx.release();
@@ -1948,6 +1985,54 @@ int32_t cpm_resample_flows(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
     // (the flows of the attempt whose counts were fetched: every attempt writes the whole array, and the last one enqueued is the one returned)
     HIP_TRY(hipMemcpyAsync(flows_out, c->d_flows, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ parking stays (include/cpm_stays.h)
+int32_t cpm_resample_stays_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, void *d_counts, void *d_stays, void *d_parked)
+{
+    CTX_TRY(c);
+    if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
+    if (!d_stays) return fail(CPM_ERR_ARG, "null d_stays");
+    if (!d_parked) return fail(CPM_ERR_ARG, "null d_parked");
+    cpm::StaysDest sd;
+    sd.stays = static_cast<int32_t *>(d_stays);
+    sd.parked = static_cast<int32_t *>(d_parked);
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), cpm::FlowsDest{}, sd);
+}
+
+int32_t cpm_resample_stays(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, int32_t *stays_out,
+                           int32_t *parked_out)
+{
+    CTX_TRY(c);
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
+    if (!stays_out) return fail(CPM_ERR_ARG, "null stays_out");
+    if (!parked_out) return fail(CPM_ERR_ARG, "null parked_out");
+    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
+        cpm_ctx *c;
+        int saved;
+        ~KernelGuard() { c->kernel = saved; }
+    } kernel_guard{c, c->kernel};
+    {
+        int32_t rc_ivp = finish_ivp(c);
+        if (rc_ivp != CPM_OK) return rc_ivp;
+    }
+    const size_t zt = static_cast<size_t>(c->Z * c->T), cells = zt * static_cast<size_t>(c->T);
+    if (!c->d_stays) HIP_TRY(hipMalloc(&c->d_stays, sizeof(int32_t) * std::max<size_t>(cells, 1)));
+    if (!c->d_stay_parked) HIP_TRY(hipMalloc(&c->d_stay_parked, sizeof(int32_t) * std::max<size_t>(zt, 1)));
+    cpm::StaysDest sd;
+    sd.stays = c->d_stays;
+    sd.parked = c->d_stay_parked;
+    int32_t rc = resample_blocking(c, seed, flags, cpm::FlowsDest{}, sd);
+    if (rc != CPM_OK) return rc;
+    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
+    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
+    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    // (the stays of the attempt whose counts were fetched: every attempt resets the side array and writes both arrays whole, and the
+    //  last one enqueued is the one returned)
+    HIP_TRY(hipMemcpyAsync(stays_out, c->d_stays, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(parked_out, c->d_stay_parked, sizeof(int32_t) * zt, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
 }

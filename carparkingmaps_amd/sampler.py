@@ -233,16 +233,28 @@ class Sampler:
     def solve_ivp_async(self, seed):
         _lib.check(self._L.cpm_solve_ivp_async(self._h, int(seed)))
 
-    def resample(self, seed, travel=False, want_state=False, want_trans=False, flows=False):
+    def resample(self, seed, travel=False, want_state=False, want_trans=False, flows=False, stays=False):
         """Returns dict(parking, driving: (Z,T) int64 F-order; sum_tt_q16: int; state, trans or None).
         flows=True (include/cpm_flows.h): the dict gains `flows`, the OD trip counts of every hour: (T, Z, Z) int32, C order,
         flows[t, o, d] = cars that drove from zone o + 1 to zone d + 1 in hour t + 1 (trips inside a zone on the diagonal), from the
         kernel family that produced the counts.  Not together with want_state / want_trans, which force the per-car kernels.
         flows="csr" (include/cpm_flows_csr.h): the dict gains `flows_csr` instead, the same counts without the zeros:
         dict(row_ptr (T*Z + 1,) int64, dest (nnz,) int32, count (nnz,) int32, shape=(T, Z, Z)), row t*Z + o, destinations 0-based and
-        ascending within a row (flows_csr_to_dense, flows_csr_hour)."""
+        ascending within a row (flows_csr_to_dense, flows_csr_hour).
+        stays=True (include/cpm_stays.h): the dict gains `stays`, (T, Z, T) int32, C order, stays[t, z, L] = cars that drove out of (or
+        within) zone z + 1 in hour t (0-based) after L whole parked hours there (L == t: parked since the day began), and `parked`,
+        (Z, T) int32, parked[z, a] = cars parked in zone z + 1 since hour a that did not drive in the last hour (stay_length_histogram).
+        Not together with flows, want_state or want_trans."""
         parking = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
         driving = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
+        if stays:
+            if flows or want_state or want_trans:
+                raise ValueError("stays=True cannot be combined with flows, want_state or want_trans")
+            out, parked = self.stays_empty(), self.parked_empty()
+            tt = C.c_int64(0)
+            _lib.check(self._L.cpm_resample_stays(self._h, int(seed), _lib.CPM_FLAG_TRAVEL if travel else 0, _vp(parking), _vp(driving),
+                                                  C.cast(C.byref(tt), C.c_void_p), _vp(out), _vp(parked)))
+            return dict(parking=parking, driving=driving, sum_tt_q16=int(tt.value), state=None, trans=None, stays=out, parked=parked)
         if isinstance(flows, str):
             if flows != "csr":
                 raise ValueError(f"flows={flows!r}: expected False, True or \"csr\"")
@@ -311,6 +323,23 @@ class Sampler:
         """How the grouped family computes the flows: one launch over the kept runs of all hours (True) or one behind every hour
         (False, the library's default; measured in DESIGN.md 8).  The flows do not depend on it."""
         _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_FLOWS_KEPT, 1 if on else 0))
+
+    # -- parking stays (include/cpm_stays.h) --
+    def stays_empty(self):
+        """The host array resample(stays=True) fills with the completed stays: (T, Z, T) int32, C order (the library writes every word)."""
+        return np.empty((self.T, self.Z, self.T), dtype=np.int32, order="C")
+
+    def parked_empty(self):
+        """The host array resample(stays=True) fills with the stays still open at the end of the day: (Z, T) int32, C order."""
+        return np.empty((self.Z, self.T), dtype=np.int32, order="C")
+
+    def resample_stays_dev(self, seed, d_counts_ptr, d_stays_ptr, d_parked_ptr, travel=False):
+        """Enqueue on the context's stream; d_counts_ptr as for resample_dev, d_stays_ptr = device address of int32[T*Z*T]
+        (stays[t][z][L]), d_parked_ptr = device address of int32[Z*T] (parked[z][a]).  A non-zero status word in the count tensor
+        invalidates both arrays: repeat the step."""
+        flags = _lib.CPM_FLAG_TRAVEL if travel else 0
+        _lib.check(self._L.cpm_resample_stays_dev(self._h, int(seed), flags, C.c_void_p(int(d_counts_ptr)), C.c_void_p(int(d_stays_ptr)),
+                                                  C.c_void_p(int(d_parked_ptr))))
 
     # -- batches (include/cpm_batch.h): B fleets, each with its own p_drive and seed, from this context's state and p_destin --
     def set_p_drive_batch(self, p_drives):
@@ -406,6 +435,22 @@ def flows_csr_hour(csr, t):
         raise IndexError(f"hour {t} of {T}")
     p = csr["row_ptr"][t * Z:(t + 1) * Z + 1]
     return p - p[0], csr["dest"][p[0]:p[-1]], csr["count"][p[0]:p[-1]]
+
+
+def stay_length_histogram(stays, parked):
+    """Stay lengths of a day over all zones, from the arrays of resample(stays=True) (numpy only): dict of three (T,) int64 arrays.
+    completed[L]: stays of L whole hours with both ends inside the day (L < t); left_censored[L]: stays that began with the day and
+    ended with a drive in hour L (L == t: at least L hours); open[h]: stays still open when the day ends, by hours parked so far
+    (h = T - 1 - a: at least h hours)."""
+    stays = np.asarray(stays)
+    parked = np.asarray(parked)
+    T = stays.shape[0]
+    if stays.ndim != 3 or stays.shape[2] != T or parked.shape != (stays.shape[1], T):
+        raise ValueError(f"stays {stays.shape} / parked {parked.shape}: expected (T, Z, T) and (Z, T)")
+    by_hour = stays.sum(axis=1, dtype=np.int64)  # [t, L]
+    left = np.diagonal(by_hour).copy()
+    completed = np.tril(by_hour, -1).sum(axis=0)
+    return dict(completed=completed, left_censored=left, open=parked.sum(axis=0, dtype=np.int64)[::-1].copy())
 
 
 def parse_uber_csv(path):
