@@ -40,12 +40,14 @@ CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
 CPM_OPT_KERNEL, CPM_OPT_PROFILE, CPM_OPT_PROFILE_KERNEL, CPM_OPT_FUSED, CPM_OPT_FUSED_LAG, CPM_OPT_ZONE_ORDER = 1, 2, 3, 4, 5, 6
 CPM_OPT_SPARSE_UPLOAD = 7  # set_p_dest: sparse row packs for an uploaded p_destin that qualifies (include/cpm.h)
+CPM_OPT_LAST_HOUR = 8  # hour T of a grouped resample: 1 (default) counts only where only its counts are wanted, 0 the plain sampler (include/cpm.h)
 CPM_OPT_FLOWS_KEPT = 16  # include/cpm_flows.h: the OD kernel once per resample over the kept runs of all hours (1) or once per hour (0, default)
 CPM_PROFILE_SAMPLER, CPM_PROFILE_PLACE, CPM_PROFILE_TRAVEL, CPM_PROFILE_UPLOAD = 0, 1, 2, 3
 # cpm_get_info keys (include/cpm.h): what the context would run next ...
 CPM_INFO_KERNEL, CPM_INFO_CAP_MULT, CPM_INFO_PARTS, CPM_INFO_FUSED, CPM_INFO_FUSED_BAILOUTS, CPM_INFO_SPARSE_TABLES = 1, 2, 3, 4, 5, 6
 # ... and what its most recent step ran
 CPM_INFO_LAST_KERNEL, CPM_INFO_LAST_FORM, CPM_INFO_STEPS_REPEATED = 7, 8, 9
+CPM_INFO_LAST_HOUR = 11  # 1: hour T of the most recent step ran the count-only kernel (10 stays unknown: tests/abi_harness.c)
 # include/cpm_batch.h: the installed batch tables' fleets, the fleets the batched kernels produced in the most recent batch step, and the
 # CPM_INFO_LAST_FORM of such a step
 CPM_MAX_BATCH = 64

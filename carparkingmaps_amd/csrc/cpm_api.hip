@@ -177,6 +177,7 @@ struct cpm_ctx {
     int last_form = -1;
     int64_t steps_repeated = 0;
     int last_batch_fleets = 0;          // CPM_INFO_LAST_BATCH_FLEETS: 0 after every step that is not a batch step
+    int last_hour = 0;                  // CPM_INFO_LAST_HOUR: 1 when hour T of the most recent step was a count-only launch (cpm_count.h)
     // batch tables and workspace (include/cpm_batch.h, cpm_batch.h)
     int batch_B = 0, batch_alloc = 0;
     double *d_pdrive_b = nullptr;       // [B][T][Z] the fleets' p_drive tables
@@ -764,6 +765,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     const int kernel = pick_kernel(c);
     c->last_kernel = kernel;  // (the family this call enqueues; the grouped path's form is recorded behind its run)
     c->last_batch_fleets = 0;
+    c->last_hour = 0;
     c->last_form = kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
     if (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED)  // (the grouped path zeroes the count tensor with its other counters, in one launch)
         HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * nwords, c->stream));
@@ -810,6 +812,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
                                       [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd);
         rc = parked_pass(rc);
         if (rc == CPM_OK) c->last_form = c->zg.last_form;
+        if (rc == CPM_OK) c->last_hour = c->zg.last_hour_counted;
         if (rc == CPM_OK && c->h_status && !c->status_pending) {
             c->h_status[1] = 0;
             if (hipMemcpyAsync(c->h_status, d_counts + nwords - 1, sizeof(long long), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
@@ -856,6 +859,7 @@ int32_t ivp_exact(cpm_ctx *c, uint64_t seed)
     const bool exact = pick_kernel(c) != CPM_KERNEL_CAR && cpm::exact_path_fits(static_cast<int>(c->Z));
     c->last_kernel = exact ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
     c->last_batch_fleets = 0;
+    c->last_hour = 0;
     c->last_form = -1;
     if (exact) {
         return cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
@@ -898,6 +902,7 @@ int32_t finish_ivp(cpm_ctx *c)
         c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
         c->last_form = c->ivp_form;
         c->last_batch_fleets = 0;
+        c->last_hour = 0;
         HIP_TRY(cpm::grouped_commit_ivp(c->zg, c->stream));
         return CPM_OK;
     };
@@ -931,6 +936,7 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
         c->last_kernel = pick_kernel(c);
         c->last_form = c->last_kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
         c->last_batch_fleets = 0;
+        c->last_hour = 0;
         return CPM_OK;
     }
     if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && grouped_fits(c, c->zg.cap_mult)) {
@@ -1266,6 +1272,10 @@ int32_t cpm_set_option(cpm_ctx *c, int32_t option, int64_t value)
         if (value != 0 && value != 1) return fail(CPM_ERR_ARG, "flows form %lld (0 one launch per hour, 1 one launch over the kept runs of all hours)", (long long)value);
         c->zg.flows_kept = value != 0;
         return CPM_OK;
+    case CPM_OPT_LAST_HOUR:
+        if (value != 0 && value != 1) return fail(CPM_ERR_ARG, "last hour %lld (0 the plain sampler, 1 counts only)", (long long)value);
+        c->zg.count_only = c->zb.count_only = value != 0;
+        return CPM_OK;
     case CPM_OPT_PROFILE_KERNEL:
         if (value < CPM_PROFILE_SAMPLER || value > CPM_PROFILE_UPLOAD) return fail(CPM_ERR_ARG, "profile kernel %lld", (long long)value);
         c->prof_what = static_cast<int>(value);
@@ -1313,13 +1323,14 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
         return CPM_OK;
     case CPM_INFO_LAST_KERNEL:
     case CPM_INFO_LAST_FORM:
+    case CPM_INFO_LAST_HOUR:
     case CPM_INFO_STEPS_REPEATED:
         if (c->ivp_pending) {  // a record of committed steps: an IVP still in flight is committed (or repeated) first
             HIP_TRY(hipSetDevice(c->device));
             int32_t rc_ivp = finish_ivp(c);
             if (rc_ivp != CPM_OK) return rc_ivp;
         }
-        *value_out = what == CPM_INFO_LAST_KERNEL ? c->last_kernel : what == CPM_INFO_LAST_FORM ? c->last_form : c->steps_repeated;
+        *value_out = what == CPM_INFO_LAST_KERNEL ? c->last_kernel : what == CPM_INFO_LAST_FORM ? c->last_form : what == CPM_INFO_LAST_HOUR ? c->last_hour : c->steps_repeated;
         return CPM_OK;
     case CPM_INFO_BATCH:
         *value_out = c->batch_B;
@@ -2326,6 +2337,7 @@ int32_t cpm_resample_batch(cpm_ctx *c, const uint64_t *seeds, uint32_t flags, in
     if (batched > 0) {
         c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
         c->last_form = CPM_FORM_BATCH;
+        c->last_hour = c->zb.last_hour_counted;
     }
     return CPM_OK;
 }
@@ -2367,6 +2379,7 @@ int32_t cpm_resample_batch_dev(cpm_ctx *c, const uint64_t *seeds, uint32_t flags
     c->last_batch_fleets = B;
     c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
     c->last_form = CPM_FORM_BATCH;
+    c->last_hour = c->zb.last_hour_counted;
     return CPM_OK;
 }
 

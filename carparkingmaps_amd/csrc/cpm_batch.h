@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void k_batch_fill(BatchFill f)
 
 // grid = Z x ceil(nf / per_wg): workgroup (z, s) stages zone z's pack once and walks fleets s * per_wg .. of the hour's records.
 // GROUPED as in the hourly sampler: stayers and runs; !GROUPED, hour T of a resample without travel times (sampled, never placed): the
-// plain form, counts only -- as the single path runs that hour.
+// plain form, counts only -- as the single path runs that hour with CPM_OPT_LAST_HOUR 0 (1, the default: k_batch_count, cpm_count.h).
 // Between two fleets the workgroup meets: the LDS beside the pack (SampleLds: ranks, staged drivers, counters) is reset per fleet, and
 // a first fleet whose bucket is empty returns from the body without a barrier -- its wait (vmcnt(0)) and this barrier put the pack
 // in front of the next fleet.
@@ -159,6 +159,8 @@ struct BatchWork {
     int cap_mult_alloc = 0;
     uint32_t cap = 0, scap = 0, idbits = 0, gdiv = 0, zpg = 1;
     bool buckets0_valid = false;  // ids0 / cnt0 describe the context's current car state
+    bool count_only = true;       // CPM_OPT_LAST_HOUR: hour T without travel times by k_batch_count (cpm_count.h)
+    int last_hour_counted = 0;    // ... 1 when the last run's hour T was that launch (CPM_INFO_LAST_HOUR)
     uint32_t *ids0 = nullptr, *cnt0 = nullptr;
     unsigned long long *bstatus = nullptr;
     uint32_t *ids = nullptr, *cnt = nullptr, *D = nullptr, *cntg = nullptr, *scratch = nullptr;
@@ -397,10 +399,15 @@ inline int32_t batch_run(BatchWork &w, hipStream_t stream, const GroupedTables &
     const size_t lds = sizeof(uint32_t) * rw;
     const int per_wg = batch_per_wg(nf, Z, lds, cu_count);
     const int tblock = travel_block(mean, false);
+    w.last_hour_counted = 0;
     for (int t = 0; t < T; ++t) {
         const GroupedArgs *at = w.args + static_cast<size_t>(t) * nf;
         const bool grouped = t + 1 < T || travel;  // (hour T without travel times: counts only, as in grouped_run)
-        if (tb.smap) {
+        if (!grouped && w.count_only) {  // counts only: no pack, no search, nothing stored per car (cpm_count.h)
+            hipLaunchKernelGGL(k_batch_count, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(nf)), dim3(kCountBlock), 0, stream, at,
+                               static_cast<uint32_t>(grouped_cpt_wide(mean)));  // (the cars per lane of the plain launch it stands for)
+            w.last_hour_counted = 1;
+        } else if (tb.smap) {
             if (grouped) batch_launch_sample_s<true, true>(at, nf, per_wg, Z, lds, mean, stream);
             else batch_launch_sample_s<false, true>(at, nf, per_wg, Z, lds, mean, stream);
         } else {

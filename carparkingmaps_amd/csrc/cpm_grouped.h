@@ -2672,6 +2672,7 @@ __global__ __launch_bounds__(1024) void k_zone_order(const unsigned long long *_
 
 }  // namespace cpm
 #include "cpm_day.h"  // the hours of a run in ONE launch (k_grouped_day), built from the bodies above
+#include "cpm_count.h"  // hour T of a resample, counts only (k_grouped_count)
 namespace cpm {
 
 // ------------------------------------------------------------------------------------------------ workspace and driver
@@ -2746,6 +2747,8 @@ struct GroupedWork {
     bool flows_kept = false;                                     // OD trip counts (cpm_flows.h) from the kept runs of all hours in one launch (CPM_OPT_FLOWS_KEPT), not hour by hour
     int last_form = -1;                                          // form the applied hours of the last run took (CPM_INFO_LAST_FORM coding: 0 two
                                                                  // launches, 1 one, 3 placing first, 6 all in one launch), from grouped_run's decision
+    bool count_only = true;                                      // CPM_OPT_LAST_HOUR: hour T of a resample by k_grouped_count (cpm_count.h) where the plain sampler ran
+    int last_hour_counted = 0;                                   // CPM_INFO_LAST_HOUR: 1 when the last run's hour T was a count-only launch
 
     // destination groups of a run: general (any zones per group) for sparse row packs, power-of-two for dense ones (grouped_gdiv_of)
     void set_groups(bool general)
@@ -3033,6 +3036,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     };
     int t_first = 0;
     w.last_form = day_n >= 2 ? 6 : 0;  // (raised below by the first hour that runs a one-launch form)
+    w.last_hour_counted = 0;
     if (day_n >= 2) {
         prof_begin(CPM_PROFILE_SAMPLER);
         grouped_launch_day(w.day_hours, day_n, Z, tb.Zq, G, tb.smap, static_cast<int>(w.zpg), nchunk, w.day_mix, mean, stream);
@@ -3050,7 +3054,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         // hour T of a resample is sampled, never applied (src/resampling.jl:81-83): counts only -- unless its travel times are wanted,
         // which are computed from the runs
         const bool last_hour = !ivp && t + 1 == T;
-        const bool grouped = !last_hour || travel || flows || stays || w.parts > 1;  // (heavy buckets: the grouped form splits them over workgroups, the plain one walks them)
+        const bool grouped = !last_hour || travel || flows || stays || w.parts > 1;  // (heavy buckets: the grouped form splits them over workgroups, the plain and count-only ones walk them)
         uint32_t *cnt_next = w.cnt + static_cast<size_t>(t + 1) * 2 * Z;  // stayers; the arrivals Z words behind
         uint32_t *ids_next = (t & 1) ? w.idsB : w.idsA;
         GroupedArgs a;
@@ -3090,7 +3094,10 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         else if (pf) grouped_launch_hour_pf<false>(a, mean, stream);
         else if (fuse) grouped_launch_hour(a, mean, stream);
         else if (grouped) grouped_launch_sample<true>(a, mean, w.parts > 1, stream);
-        else grouped_launch_sample<false>(a, mean, w.parts > 1, stream);
+        else if (w.count_only) {  // hour T, counts only: nobody reads the destinations the plain form draws (cpm_count.h)
+            grouped_launch_count(a, mean, w.parts > 1, stream);
+            w.last_hour_counted = 1;
+        } else grouped_launch_sample<false>(a, mean, w.parts > 1, stream);
         prof_end(CPM_PROFILE_SAMPLER);
         if (grouped && !fuse && !pf) grouped_launch_heavy(a, w.parts, w.hgrid, mean, stream);
         if (!last_hour) {

@@ -84,13 +84,19 @@ class Sampler:
         counts do not depend on it.  get_info(6) tells which form the installed table took."""
         _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_SPARSE_UPLOAD, 1 if on else 0))
 
+    def set_last_hour(self, count_only=True):
+        """Hour T of a grouped resample (sampled, never applied): True (the library's default) runs the count-only kernel wherever
+        only the hour's counts are wanted, False the plain form of the full sampler.  The counts do not depend on it; get_info(11)
+        tells what the most recent step ran."""
+        _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_LAST_HOUR, 1 if count_only else 0))
+
     def get_info(self, what):
         """cpm_get_info (keys: _lib.CPM_INFO_*).  What the context would run next: 1 = kernel family AUTO resolves to now, 2 =
         bucket-region size in multiples of the mean bucket, 3 = workgroups per heavy zone, 4 = form of the hour (0 two launches, 1 one,
         3 placing first, 6 all hours in one launch), 5 = steps that bailed out of a one-launch form, 6 = words of a sparse row pack (0:
         dense tables; > 0 after build_p_dest on a sparse datamatrix or after set_p_dest under set_sparse_upload on a table that qualifies).  What its most recent step ran: 7 = the kernel family that produced its results (0 before any step), 8 = the
         form its grouped hours took (coded as 4; -1 when the family is not the grouped one), 9 = step attempts the library discarded
-        and ran again so far."""
+        and ran again so far, 11 = 1 when its hour T ran the count-only kernel (set_last_hour)."""
         v = C.c_int64(0)
         _lib.check(self._L.cpm_get_info(self._h, int(what), C.byref(v)))
         return int(v.value)

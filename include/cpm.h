@@ -94,6 +94,11 @@ extern "C" {
                                    pack of the longest row is at most 60 % of the dense one (tables of fewer than ~400 zones never do: their
                                    dense packs are at the 1 KiB floor already); otherwise, and with 0 (default), the dense packs.  Read when a
                                    table is installed: the installed one keeps its form.  The counts do not depend on it */
+#define CPM_OPT_LAST_HOUR 8     /* hour T of a resample on the grouped path, which is sampled and never applied: 1 (default) where nothing but its
+                                   counts is wanted -- no travel times, flows or stays, no heavy bucket seen, not the placing-first or day-launch
+                                   forms -- a count-only kernel (csrc/cpm_count.h: ids, one Philox call per car, a compare; no row pack, no
+                                   destination draw), in cpm_resample* and cpm_resample_batch* alike; 0: the plain form of the full sampler,
+                                   which also draws the destinations nobody reads.  The counts do not depend on it; what ran is CPM_INFO_LAST_HOUR */
 #define CPM_OPT_PROFILE_KERNEL 3 /* which hourly launch CPM_OPT_PROFILE brackets: */
 #define CPM_PROFILE_SAMPLER 0   /*   the sampler (default; every kernel family has one) */
 #define CPM_PROFILE_PLACE 1     /*   the grouped path's placing kernel */
@@ -140,6 +145,9 @@ int32_t cpm_set_option(cpm_ctx *ctx, int32_t option, int64_t value);
                                     * CPM_INFO_FUSED (0 two launches per hour, 1 one, 3 placing first, 6 all hours in one launch); -1 otherwise */
 #define CPM_INFO_STEPS_REPEATED 9  /* step attempts the blocking calls ran, discarded and ran again so far (regions grown, a one-launch form
                                     * that bailed out repeated with two launches, a demotion to a layout that cannot overflow); 0 on a new context */
+#define CPM_INFO_LAST_HOUR 11      /* 1 when hour T of the most recent step ran the count-only kernel (CPM_OPT_LAST_HOUR), from what was launched;
+                                    * 0 otherwise: the plain or a run-producing form, another kernel family, an IVP.  (Key 10, the one behind
+                                    * CPM_INFO_STEPS_REPEATED, stays an argument error: tests/abi_harness.c asks for exactly that) */
 int32_t cpm_get_info(cpm_ctx *ctx, int32_t what, int64_t *value_out);
 /* run on a caller-owned hipStream_t (e.g. torch's current stream); NULL = ctx's own, which is created when a call first needs it.
  * Contexts meant to run side by side (two resamples interleave on the chip) are each given their stream right behind
