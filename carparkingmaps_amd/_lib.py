@@ -35,6 +35,9 @@ FLOWS_CSR_SYMBOLS = ["cpm_resample_flows_csr_dev", "cpm_resample_flows_csr", "cp
 # every symbol include/cpm_stays.h declares (checked by tests/test_stays.py); a header and a list of its own, likewise
 STAYS_SYMBOLS = ["cpm_resample_stays", "cpm_resample_stays_dev"]
 
+# every symbol include/cpm_paths.h declares (checked by tests/test_paths.py); a header and a list of its own, likewise
+PATHS_SYMBOLS = ["cpm_resample_paths", "cpm_resample_paths_dev", "cpm_paths_expand_dev"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -71,6 +74,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_flows.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_flows_csr.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_stays.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_paths.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -149,7 +153,10 @@ def load():
     L.cpm_get_flows_csr.argtypes = [vp, vp, vp, i64]
     L.cpm_resample_stays.argtypes = [vp, u64, u32, vp, vp, vp, vp, vp]
     L.cpm_resample_stays_dev.argtypes = [vp, u64, u32, vp, vp, vp]
-    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS:
+    L.cpm_resample_paths.argtypes = [vp, u64, u32, vp, vp, vp, vp]
+    L.cpm_resample_paths_dev.argtypes = [vp, u64, u32, vp, vp]
+    L.cpm_paths_expand_dev.argtypes = [vp, u64, u32, vp, vp, vp]
+    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

@@ -15,10 +15,12 @@
 #include "../../include/cpm_flows.h"
 #include "../../include/cpm_flows_csr.h"
 #include "../../include/cpm_stays.h"
+#include "../../include/cpm_paths.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
+#include "cpm_paths.h"
 #include "cpm_tables.h"
 #include "cpm_exact.h"
 #include "cpm_grouped.h"
@@ -148,6 +150,12 @@ struct cpm_ctx {
     int64_t stay_last_cap = 0;
     int32_t *d_stays = nullptr;        // [T][Z][T]
     int32_t *d_stay_parked = nullptr;  // [Z][T]
+    // per-car day records (include/cpm_paths.h): the blocking call's array, kept from its first use, and the columns
+    // cpm_paths_expand_dev writes where the caller wants no matrix
+    uint32_t *d_paths = nullptr;       // [T][n]
+    int64_t paths_cap = 0;
+    char *d_expand_cols = nullptr;     // [5][n] 8-byte words
+    int64_t expand_cap = 0;
     int64_t rec_cap = 0;
     bool have_state = false;
     // results
@@ -742,8 +750,10 @@ int32_t ensure_travel_tables(cpm_ctx *c)
 
 // fd: where the OD trip counts of the step go, from whatever family produces the counts: nowhere, DEVICE int32[T][Z][Z] (cpm_flows.h)
 // or DEVICE CSR arrays (cpm_flows_csr.h).  sd: where its parking stays go (cpm_stays.h): nowhere, or DEVICE int32[T][Z][T] + int32[Z][T]
-// (sd.last is the context's own side array, set here)
-int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, cpm::FlowsDest fd = cpm::FlowsDest{}, cpm::StaysDest sd = cpm::StaysDest{})
+// (sd.last is the context's own side array, set here).  pd: where the per-car record of the day goes (cpm_paths.h): nowhere, or DEVICE
+// uint32[T][n], every word of which is written by whatever family runs
+int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, cpm::FlowsDest fd = cpm::FlowsDest{}, cpm::StaysDest sd = cpm::StaysDest{},
+                         cpm::PathsDest pd = cpm::PathsDest{})
 {
     int32_t *const d_flows = fd.dense;
     if (sd.any() && c->T > cpm::kStaysMaxT) return fail(CPM_ERR_ARG, "stays: T = %lld, the per-car word keeps an hour in 8 bits (T <= %d)", (long long)c->T, cpm::kStaysMaxT);
@@ -809,7 +819,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
             if (rc_tt != CPM_OK) return rc_tt;
         }
         int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, travel, d_counts, c->cu_count,
-                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd);
+                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd, pd);
         rc = parked_pass(rc);
         if (rc == CPM_OK) c->last_form = c->zg.last_form;
         if (rc == CPM_OK) c->last_hour = c->zg.last_hour_counted;
@@ -829,7 +839,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     if (kernel == CPM_KERNEL_ZONE_LDS) {
         return parked_pass(cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
                                           c->d_zone0, seed, travel, c->d_dm, d_counts, c->cu_count, [&](int what) { prof_begin(c, what); },
-                                          [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd));
+                                          [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd, pd));
     }
     int32_t rc = ensure_rec(c);
     if (rc != CPM_OK) return rc;
@@ -846,6 +856,8 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         }
         if (sd.any()) HIP_TRY(cpm::stays_launch_cars(c->stream, nullptr, zin, nullptr, out, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), t, sd));
     }
+    // the per-car record of the day (cpm_paths.h): d_rec is that record, hour by hour in car order
+    if (pd.any()) HIP_TRY(hipMemcpyAsync(pd.paths, c->d_rec, sizeof(uint32_t) * static_cast<size_t>(c->T) * c->n, hipMemcpyDeviceToDevice, c->stream));
     return parked_pass(launch_histogram(c, d_counts));
 }
 
@@ -954,9 +966,10 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
 
 // The blocking resample: the count tensor of a valid step in c->h_counts (c->d_counts, status word included).  Leaves c->kernel
 // changed when it had to fall back to a layout that cannot overflow: the caller restores it.
-int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsDest d_flows = cpm::FlowsDest{}, cpm::StaysDest d_stays = cpm::StaysDest{})
+int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsDest d_flows = cpm::FlowsDest{}, cpm::StaysDest d_stays = cpm::StaysDest{},
+                          cpm::PathsDest d_paths = cpm::PathsDest{})
 {
-    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays);
+    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays, d_paths);
     const size_t zt = static_cast<size_t>(c->Z * c->T), nwords = 2 * zt + 2;
     auto fetch = [&]() -> int32_t {  // the count tensor, Σ time and the status word: one copy into pinned memory, one wait
         HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, sizeof(int64_t) * nwords, hipMemcpyDeviceToHost, c->stream));
@@ -970,14 +983,14 @@ int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsD
     // problem still fits (two launches per hour after a bail-out) ...  (each discarded attempt: CPM_INFO_STEPS_REPEATED)
     while (rc == CPM_OK && c->h_counts[nwords - 1] != 0 && pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && absorb_status(c, c->h_counts[nwords - 1])) {
         ++c->steps_repeated;
-        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays);
+        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays, d_paths);
         if (rc == CPM_OK) rc = fetch();
     }
     if (rc == CPM_OK && c->h_counts[nwords - 1] != 0) {  // ... else on a layout that cannot overflow
         ++c->steps_repeated;
         if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED) c->grouped_overflowed = true;
         c->kernel = cpm::exact_path_fits(static_cast<int>(c->Z)) ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
-        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays);
+        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays, d_paths);
         if (rc == CPM_OK) rc = fetch();
     }
     return rc;
@@ -1223,6 +1236,8 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_flows_hour);
     dfree(c->d_stay_last);
     dfree(c->d_stays);
+    dfree(c->d_paths);
+    dfree(c->d_expand_cols);
     dfree(c->d_stay_parked);
     dfree(c->d_counts);
     dfree(c->d_err);
@@ -2045,6 +2060,98 @@ int32_t cpm_resample_stays(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     HIP_TRY(hipMemcpyAsync(stays_out, c->d_stays, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(parked_out, c->d_stay_parked, sizeof(int32_t) * zt, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ per-car day records (include/cpm_paths.h)
+int32_t cpm_resample_paths_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, void *d_counts, void *d_paths)
+{
+    CTX_TRY(c);
+    if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
+    if (!d_paths) return fail(CPM_ERR_ARG, "null d_paths");
+    cpm::PathsDest pd;
+    pd.paths = static_cast<uint32_t *>(d_paths);
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), cpm::FlowsDest{}, cpm::StaysDest{}, pd);
+}
+
+int32_t cpm_resample_paths(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, uint32_t *paths_out)
+{
+    CTX_TRY(c);
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
+    if (!paths_out) return fail(CPM_ERR_ARG, "null paths_out");
+    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
+        cpm_ctx *c;
+        int saved;
+        ~KernelGuard() { c->kernel = saved; }
+    } kernel_guard{c, c->kernel};
+    {
+        int32_t rc_ivp = finish_ivp(c);
+        if (rc_ivp != CPM_OK) return rc_ivp;
+    }
+    const int64_t words = c->T * c->n;
+    if (c->paths_cap < words || !c->d_paths) {  // kept from the first use (until the fleet grows)
+        dfree(c->d_paths);
+        c->d_paths = nullptr;
+        c->paths_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_paths, sizeof(uint32_t) * static_cast<size_t>(std::max<int64_t>(words, 1))));
+        c->paths_cap = words;
+    }
+    cpm::PathsDest pd;
+    pd.paths = c->d_paths;
+    int32_t rc = resample_blocking(c, seed, flags, cpm::FlowsDest{}, cpm::StaysDest{}, pd);
+    if (rc != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z * c->T);
+    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
+    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
+    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    // (the record of the attempt whose counts were fetched: every attempt writes every word, and the last one enqueued is the one returned)
+    if (words > 0) {
+        HIP_TRY(hipMemcpyAsync(paths_out, c->d_paths, sizeof(uint32_t) * static_cast<size_t>(words), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return CPM_OK;
+}
+
+// k_export_hour as cpm_resample's compat route launches it, with the record in the place of the per-car kernels' d_rec and the
+// caller's device columns in the place of the staging columns: T launches on the stream, no synchronisation
+int32_t cpm_paths_expand_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, const void *d_paths, void *d_state, void *d_trans)
+{
+    CTX_TRY(c);
+    if (!d_paths) return fail(CPM_ERR_ARG, "null d_paths");
+    {
+        int32_t rc_ivp = finish_ivp(c);
+        if (rc_ivp != CPM_OK) return rc_ivp;
+    }
+    if (!c->have_state) return fail(CPM_ERR_STATE, "paths_expand: no car state (cpm_init_states / cpm_set_state)");
+    const bool travel = (flags & CPM_FLAG_TRAVEL) != 0;
+    if (travel && !c->have_dm()) return fail(CPM_ERR_STATE, "CPM_FLAG_TRAVEL needs cpm_set_datamatrix");
+    const int64_t n = c->n;
+    if (n == 0 || (!d_state && !d_trans)) return CPM_OK;
+    int64_t *spare_state = nullptr;
+    double *spare_f = nullptr;
+    if (!d_state || !d_trans) {  // (the kernel writes all five columns: those nobody asked for go to the context's own)
+        if (c->expand_cap < n || !c->d_expand_cols) {
+            dfree(c->d_expand_cols);
+            c->d_expand_cols = nullptr;
+            c->expand_cap = 0;
+            HIP_TRY(hipMalloc(&c->d_expand_cols, static_cast<size_t>(n) * 8 * 5));
+            c->expand_cap = n;
+        }
+        spare_state = reinterpret_cast<int64_t *>(c->d_expand_cols);
+        spare_f = reinterpret_cast<double *>(c->d_expand_cols) + n;
+    }
+    const uint32_t *rec = static_cast<const uint32_t *>(d_paths);
+    const size_t tn = static_cast<size_t>(c->T) * n;
+    for (int t = 0; t < c->T; ++t) {
+        const uint32_t *zsrc = (t == 0) ? c->d_zone0 : rec + static_cast<size_t>(t - 1) * n;
+        int64_t *state_col = d_state ? static_cast<int64_t *>(d_state) + static_cast<size_t>(t) * n : spare_state;
+        double *f = d_trans ? static_cast<double *>(d_trans) + static_cast<size_t>(t) * n : spare_f;
+        const size_t col = d_trans ? tn : static_cast<size_t>(n);
+        hipLaunchKernelGGL(cpm::k_export_hour, dim3(nblk(n, 256)), dim3(256), 0, c->stream, zsrc, rec + static_cast<size_t>(t) * n, n, c->cars, state_col, f,
+                           f + col, f + 2 * col, f + 3 * col, travel ? c->d_dm : nullptr, c->d_dist, static_cast<int>(c->Z), static_cast<int>(c->T), t,
+                           static_cast<uint32_t>(c->T - 1 + t), seed);
+        HIP_TRY(hipGetLastError());
+    }
     return CPM_OK;
 }
 

@@ -30,6 +30,7 @@
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
+#include "cpm_paths.h"
 
 namespace cpm {
 
@@ -468,7 +469,7 @@ template <typename F1, typename F2>
 int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, const double *d_cdf, int Z, int Zp, int T, int64_t n, CarIndex cars,
                   const uint32_t *d_zone0, uint64_t seed, bool travel, const double *d_dm, int64_t *d_counts, int cu_count, F1 prof_begin,
                   F2 prof_end, std::string &err, bool ivp = false, uint32_t *d_zone0_out = nullptr, FlowsDest fd = FlowsDest{},
-                  StaysDest sd = StaysDest{})
+                  StaysDest sd = StaysDest{}, PathsDest paths = PathsDest{})
 {
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
@@ -524,6 +525,8 @@ int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, cons
         }
         // parking stays (cpm_stays.h): the same records; slot i is car ids[i] (zeroed `stays` and side array: the caller's)
         if (sd.any() && !ivp && (e = stays_launch_cars(stream, ids, nullptr, off, w.dest, n, Z, T, t, sd)) != hipSuccess) return hip_fail(e, "stays of the hour");
+        // the per-car record of the day (cpm_paths.h): the same records again, every slot to its car's word of the hour's row
+        if (paths.any() && !ivp && (e = paths_launch_slots(stream, ids, w.dest, n, t, paths)) != hipSuccess) return hip_fail(e, "paths of the hour");
         if (ivp || t + 1 < T) {  // resampling: hour T's transition is sampled but never applied (src/resampling.jl:81-83)
             uint32_t *cur = w.cursor + static_cast<size_t>(t) * Z;
             uint32_t *ids_next = (t & 1) ? w.idsB : w.idsA;

@@ -39,6 +39,7 @@
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
+#include "cpm_paths.h"
 
 namespace cpm {
 
@@ -2902,10 +2903,11 @@ __global__ __launch_bounds__(256) void k_grouped_zero(unsigned long long *__rest
 template <typename F1, typename F2>
 int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb, int64_t n, CarIndex cars, const uint32_t *d_zone0,
                     uint64_t seed, bool travel, int64_t *d_counts, int cu_count, F1 prof_begin, F2 prof_end, std::string &err, bool ivp = false,
-                    uint32_t *d_zone0_out = nullptr, FlowsDest fd = FlowsDest{}, StaysDest sd = StaysDest{})
+                    uint32_t *d_zone0_out = nullptr, FlowsDest fd = FlowsDest{}, StaysDest sd = StaysDest{}, PathsDest pd = PathsDest{})
 {
     static_assert(kFlowRuns == kGroups, "k_grouped_flows reads the runs of cpm_grouped.h");
     static_assert(kStayRuns == kGroups, "k_grouped_stays reads the runs of cpm_grouped.h");
+    static_assert(kPathRuns == kGroups, "k_grouped_paths reads the runs of cpm_grouped.h");
     int32_t *const d_flows = fd.dense;
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
@@ -2933,9 +2935,13 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     // Parking stays (cpm_stays.h, sd): from the same runs, one launch per hour -- the per-car side array is carried from hour to hour,
     // so a grid of (Z, T) would race on it: over kept runs it is T launches in hour order at the end.  Stays alone never ask for
     // the kept form (the day launch apart, which has no hourly boundary).
+    // The per-car record of the day (cpm_paths.h, pd): from the same runs, a carry and a scatter per hour -- carry(t) reads the row
+    // scatter(t - 1) wrote, so these too run in hour order, behind every hour or, over kept runs, T pairs at the end.  Paths alone
+    // never ask for the kept form (the day launch apart).
     const bool flows = fd.any() && !ivp;
     const bool stays = sd.any() && !ivp;
-    const bool history = (travel || (flows && (w.flows_kept || w.fused_day)) || (stays && w.fused_day)) && !ivp && w.ensure_history();
+    const bool paths = pd.any() && !ivp;
+    const bool history = (travel || (flows && (w.flows_kept || w.fused_day)) || ((stays || paths) && w.fused_day)) && !ivp && w.ensure_history();
     const int G = tb.G;
     const size_t rw = static_cast<size_t>(pack_row_words(tb.Zq, G, tb.smap));
     const int64_t mean = (n + Z - 1) / Z;
@@ -2944,7 +2950,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     const bool shape = w.fused_ok && w.parts <= 1 && fused_shape_ok(Z, tb.Zq, G, tb.smap) && (!w.fused_auto || fused_pays(Z, tb.Zq, G, cu_count, tb.smap, mean));
     // ... and one launch for ALL hours that are applied (k_grouped_day): the IVP's T - 1, a resample's first T - 1 (hour T is sampled,
     // never applied: the plain form behind the placing of hour T - 1, k_grouped_hour_pf); hourly travel launches need hourly boundaries
-    const int day_n = (shape && w.fused_day && w.cap < (1u << kCntXccShift) && (!(travel || flows || stays) || history)) ? (ivp ? hours : hours - 1) : 0;
+    const int day_n = (shape && w.fused_day && w.cap < (1u << kCntXccShift) && (!(travel || flows || stays || paths) || history)) ? (ivp ? hours : hours - 1) : 0;
     const int nchunk = (Z + kFusedChunk - 1) / kFusedChunk;
     GroupedDay day{};
     auto hour_base = [&](GroupedArgs &a) {  // what all hours of a run share
@@ -3054,7 +3060,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         // hour T of a resample is sampled, never applied (src/resampling.jl:81-83): counts only -- unless its travel times are wanted,
         // which are computed from the runs
         const bool last_hour = !ivp && t + 1 == T;
-        const bool grouped = !last_hour || travel || flows || stays || w.parts > 1;  // (heavy buckets: the grouped form splits them over workgroups, the plain and count-only ones walk them)
+        const bool grouped = !last_hour || travel || flows || stays || paths || w.parts > 1;  // (heavy buckets: the grouped form splits them over workgroups, the plain and count-only ones walk them)
         uint32_t *cnt_next = w.cnt + static_cast<size_t>(t + 1) * 2 * Z;  // stayers; the arrivals Z words behind
         uint32_t *ids_next = (t & 1) ? w.idsB : w.idsA;
         GroupedArgs a;
@@ -3142,7 +3148,18 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
             const int32_t rc_st = stays_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, T, t, n, sd, err);
             if (rc_st != CPM_OK) return rc_st;
         }
+        if (paths && !history) {
+            const int32_t rc_pa = paths_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, t, n, d_zone0, pd, err);
+            if (rc_pa != CPM_OK) return rc_pa;
+        }
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "grouped zone hour launch");
+    }
+    if (paths && history) {  // the kept runs of all hours: T pairs of launches, in hour order
+        for (int t = 0; t < T; ++t) {
+            const int32_t rc_pa = paths_launch_grouped(stream, w.Dq + w.run_words() * static_cast<size_t>(t), w.cntg + w.len_words() * static_cast<size_t>(t), Z,
+                                                       w.scap, w.idbits, w.zpg, t, n, d_zone0, pd, err);
+            if (rc_pa != CPM_OK) return rc_pa;
+        }
     }
     if (stays && history) {  // the kept runs of all hours: T launches, in hour order
         for (int t = 0; t < T; ++t) {

@@ -239,7 +239,7 @@ class Sampler:
     def solve_ivp_async(self, seed):
         _lib.check(self._L.cpm_solve_ivp_async(self._h, int(seed)))
 
-    def resample(self, seed, travel=False, want_state=False, want_trans=False, flows=False, stays=False):
+    def resample(self, seed, travel=False, want_state=False, want_trans=False, flows=False, stays=False, paths=False):
         """Returns dict(parking, driving: (Z,T) int64 F-order; sum_tt_q16: int; state, trans or None).
         flows=True (include/cpm_flows.h): the dict gains `flows`, the OD trip counts of every hour: (T, Z, Z) int32, C order,
         flows[t, o, d] = cars that drove from zone o + 1 to zone d + 1 in hour t + 1 (trips inside a zone on the diagonal), from the
@@ -250,9 +250,21 @@ class Sampler:
         stays=True (include/cpm_stays.h): the dict gains `stays`, (T, Z, T) int32, C order, stays[t, z, L] = cars that drove out of (or
         within) zone z + 1 in hour t (0-based) after L whole parked hours there (L == t: parked since the day began), and `parked`,
         (Z, T) int32, parked[z, a] = cars parked in zone z + 1 since hour a that did not drive in the last hour (stay_length_histogram).
-        Not together with flows, want_state or want_trans."""
+        Not together with flows, want_state or want_trans.
+        paths=True (include/cpm_paths.h): the dict gains `paths`, (T, n) uint32, C order, n the context's car count:
+        paths[t, i] = (destination of car i in hour t, 0-based; its own zone when it did not drive) | 0x80000000 when it drove, from
+        the kernel family that produced the counts (paths_to_matrices, paths_flows).  Not together with flows, stays, want_state or
+        want_trans."""
         parking = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
         driving = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
+        if paths:
+            if flows or stays or want_state or want_trans:
+                raise ValueError("paths=True cannot be combined with flows, stays, want_state or want_trans")
+            out = self.paths_empty()
+            tt = C.c_int64(0)
+            _lib.check(self._L.cpm_resample_paths(self._h, int(seed), _lib.CPM_FLAG_TRAVEL if travel else 0, _vp(parking), _vp(driving),
+                                                  C.cast(C.byref(tt), C.c_void_p), _vp(out)))
+            return dict(parking=parking, driving=driving, sum_tt_q16=int(tt.value), state=None, trans=None, paths=out)
         if stays:
             if flows or want_state or want_trans:
                 raise ValueError("stays=True cannot be combined with flows, want_state or want_trans")
@@ -346,6 +358,32 @@ class Sampler:
         flags = _lib.CPM_FLAG_TRAVEL if travel else 0
         _lib.check(self._L.cpm_resample_stays_dev(self._h, int(seed), flags, C.c_void_p(int(d_counts_ptr)), C.c_void_p(int(d_stays_ptr)),
                                                   C.c_void_p(int(d_parked_ptr))))
+
+    # -- per-car day records (include/cpm_paths.h) --
+    def paths_words(self):
+        """uint32 words of the record: T * n, n the context's car count."""
+        return self.T * self.car_count
+
+    def paths_empty(self):
+        """The host array resample(paths=True) fills: (T, n) uint32, C order (the library writes every word)."""
+        return np.empty((self.T, self.car_count), dtype=np.uint32, order="C")
+
+    def resample_paths_dev(self, seed, d_counts_ptr, d_paths_ptr, travel=False):
+        """Enqueue on the context's stream; d_counts_ptr as for resample_dev, d_paths_ptr = device address of uint32[T*n]
+        (paths[t][i]).  A non-zero status word in the count tensor invalidates the record: repeat the step."""
+        flags = _lib.CPM_FLAG_TRAVEL if travel else 0
+        _lib.check(self._L.cpm_resample_paths_dev(self._h, int(seed), flags, C.c_void_p(int(d_counts_ptr)) if d_counts_ptr else None,
+                                                  C.c_void_p(int(d_paths_ptr)) if d_paths_ptr else None))
+
+    def paths_expand_dev(self, seed, d_paths_ptr, d_state_ptr, d_trans_ptr, travel=False):
+        """Enqueue on the context's stream: the reference's matrices from a record, on the device.  d_state_ptr = device address of
+        int64[T*n] (state_matrix, C x T column-major, 1-based) or 0, d_trans_ptr = device address of float64[4*T*n]
+        (transition_matrix, C x T x 4 column-major) or 0.  The context's state and the seed must be those of the step that produced
+        the record; travel=True re-derives the travel-time and distance columns, which are zero otherwise."""
+        flags = _lib.CPM_FLAG_TRAVEL if travel else 0
+        _lib.check(self._L.cpm_paths_expand_dev(self._h, int(seed), flags, C.c_void_p(int(d_paths_ptr)) if d_paths_ptr else None,
+                                                C.c_void_p(int(d_state_ptr)) if d_state_ptr else None,
+                                                C.c_void_p(int(d_trans_ptr)) if d_trans_ptr else None))
 
     # -- batches (include/cpm_batch.h): B fleets, each with its own p_drive and seed, from this context's state and p_destin --
     def set_p_drive_batch(self, p_drives):
@@ -457,6 +495,37 @@ def stay_length_histogram(stays, parked):
     left = np.diagonal(by_hour).copy()
     completed = np.tril(by_hour, -1).sum(axis=0)
     return dict(completed=completed, left_censored=left, open=parked.sum(axis=0, dtype=np.int64)[::-1].copy())
+
+
+def paths_to_matrices(paths, zone0):
+    """The reference's state_matrix ((n, T) int64, 1-based zones) and transition_matrix[:, :, 0:2] ((n, T, 2) float64: drove, 1-based
+    destination) from the record of resample(paths=True) and zone0, the 1-based state the step started from (numpy only)."""
+    paths = np.asarray(paths)
+    zone0 = np.asarray(zone0, dtype=np.int64)
+    if paths.ndim != 2 or zone0.shape != (paths.shape[1],):
+        raise ValueError(f"paths {paths.shape} / zone0 {zone0.shape}: expected (T, n) and (n,)")
+    T, n = paths.shape
+    dest = (paths & np.uint32(0x7FFFFFFF)).astype(np.int64).T + 1          # (n, T)
+    state = np.empty((n, T), dtype=np.int64)
+    state[:, 0] = zone0
+    state[:, 1:] = dest[:, :T - 1]
+    trans = np.empty((n, T, 2), dtype=np.float64)
+    trans[:, :, 0] = (paths >> np.uint32(31)).T
+    trans[:, :, 1] = dest
+    return state, trans
+
+
+def paths_flows(paths, zone0, Z):
+    """The (T, Z, Z) int32 OD trip counts resample(flows=True) returns, from the record of resample(paths=True) and zone0, the
+    1-based state the step started from (numpy only): flows[t, o, d] = cars that drove from zone o + 1 to zone d + 1 in hour t."""
+    state, trans = paths_to_matrices(paths, zone0)
+    T = state.shape[1]
+    flows = np.zeros((T, Z, Z), dtype=np.int32)
+    for t in range(T):
+        drove = trans[:, t, 0] == 1
+        cell = (state[drove, t] - 1) * Z + (trans[drove, t, 1].astype(np.int64) - 1)
+        flows[t] = np.bincount(cell, minlength=Z * Z).reshape(Z, Z)
+    return flows
 
 
 def parse_uber_csv(path):
