@@ -748,13 +748,15 @@ int32_t ensure_travel_tables(cpm_ctx *c)
     return CPM_OK;
 }
 
-// fd: where the OD trip counts of the step go, from whatever family produces the counts: nowhere, DEVICE int32[T][Z][Z] (cpm_flows.h)
-// or DEVICE CSR arrays (cpm_flows_csr.h).  sd: where its parking stays go (cpm_stays.h): nowhere, or DEVICE int32[T][Z][T] + int32[Z][T]
-// (sd.last is the context's own side array, set here).  pd: where the per-car record of the day goes (cpm_paths.h): nowhere, or DEVICE
-// uint32[T][n], every word of which is written by whatever family runs
-int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, cpm::FlowsDest fd = cpm::FlowsDest{}, cpm::StaysDest sd = cpm::StaysDest{},
-                         cpm::PathsDest pd = cpm::PathsDest{})
+// side (cpm_runs.h): where the side outputs of the step go, from whatever family produces the counts.  flows: the OD trip counts --
+// nowhere, DEVICE int32[T][Z][Z] (cpm_flows.h) or DEVICE CSR arrays (cpm_flows_csr.h).  stays: the parking stays (cpm_stays.h) -- nowhere,
+// or DEVICE int32[T][Z][T] + int32[Z][T] (stays.last is the context's own side array, set here).  paths: the per-car record of the day
+// (cpm_paths.h) -- nowhere, or DEVICE uint32[T][n], every word of which is written by whatever family runs
+int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_counts, cpm::SideDest side = cpm::SideDest{})
 {
+    cpm::FlowsDest &fd = side.flows;
+    cpm::StaysDest &sd = side.stays;
+    const cpm::PathsDest &pd = side.paths;
     int32_t *const d_flows = fd.dense;
     if (sd.any() && c->T > cpm::kStaysMaxT) return fail(CPM_ERR_ARG, "stays: T = %lld, the per-car word keeps an hour in 8 bits (T <= %d)", (long long)c->T, cpm::kStaysMaxT);
     if (sd.any() && c->Z > static_cast<int64_t>(cpm::kStayZoneMask)) return fail(CPM_ERR_ARG, "stays: Z = %lld, the per-car word keeps a zone in 24 bits", (long long)c->Z);
@@ -819,7 +821,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
             if (rc_tt != CPM_OK) return rc_tt;
         }
         int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, travel, d_counts, c->cu_count,
-                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd, pd);
+                                      [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, side);
         rc = parked_pass(rc);
         if (rc == CPM_OK) c->last_form = c->zg.last_form;
         if (rc == CPM_OK) c->last_hour = c->zg.last_hour_counted;
@@ -839,7 +841,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     if (kernel == CPM_KERNEL_ZONE_LDS) {
         return parked_pass(cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
                                           c->d_zone0, seed, travel, c->d_dm, d_counts, c->cu_count, [&](int what) { prof_begin(c, what); },
-                                          [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, fd, sd, pd));
+                                          [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, side));
     }
     int32_t rc = ensure_rec(c);
     if (rc != CPM_OK) return rc;
@@ -966,10 +968,9 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
 
 // The blocking resample: the count tensor of a valid step in c->h_counts (c->d_counts, status word included).  Leaves c->kernel
 // changed when it had to fall back to a layout that cannot overflow: the caller restores it.
-int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsDest d_flows = cpm::FlowsDest{}, cpm::StaysDest d_stays = cpm::StaysDest{},
-                          cpm::PathsDest d_paths = cpm::PathsDest{})
+int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::SideDest side = cpm::SideDest{})
 {
-    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays, d_paths);
+    int32_t rc = resample_enqueue(c, seed, flags, c->d_counts, side);
     const size_t zt = static_cast<size_t>(c->Z * c->T), nwords = 2 * zt + 2;
     auto fetch = [&]() -> int32_t {  // the count tensor, Σ time and the status word: one copy into pinned memory, one wait
         HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, sizeof(int64_t) * nwords, hipMemcpyDeviceToHost, c->stream));
@@ -983,14 +984,14 @@ int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::FlowsD
     // problem still fits (two launches per hour after a bail-out) ...  (each discarded attempt: CPM_INFO_STEPS_REPEATED)
     while (rc == CPM_OK && c->h_counts[nwords - 1] != 0 && pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && absorb_status(c, c->h_counts[nwords - 1])) {
         ++c->steps_repeated;
-        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays, d_paths);
+        rc = resample_enqueue(c, seed, flags, c->d_counts, side);
         if (rc == CPM_OK) rc = fetch();
     }
     if (rc == CPM_OK && c->h_counts[nwords - 1] != 0) {  // ... else on a layout that cannot overflow
         ++c->steps_repeated;
         if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED) c->grouped_overflowed = true;
         c->kernel = cpm::exact_path_fits(static_cast<int>(c->Z)) ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
-        rc = resample_enqueue(c, seed, flags, c->d_counts, d_flows, d_stays, d_paths);
+        rc = resample_enqueue(c, seed, flags, c->d_counts, side);
         if (rc == CPM_OK) rc = fetch();
     }
     return rc;
@@ -1980,9 +1981,9 @@ int32_t cpm_resample_flows_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, void *
     CTX_TRY(c);
     if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
     if (!d_flows) return fail(CPM_ERR_ARG, "null d_flows");
-    cpm::FlowsDest fd;
-    fd.dense = static_cast<int32_t *>(d_flows);
-    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), fd);
+    cpm::SideDest side;
+    side.flows.dense = static_cast<int32_t *>(d_flows);
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), side);
 }
 
 int32_t cpm_resample_flows(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, int32_t *flows_out)
@@ -2001,9 +2002,9 @@ int32_t cpm_resample_flows(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     }
     const size_t cells = static_cast<size_t>(c->T) * c->Z * c->Z;
     if (!c->d_flows) HIP_TRY(hipMalloc(&c->d_flows, sizeof(int32_t) * std::max<size_t>(cells, 1)));
-    cpm::FlowsDest fd;
-    fd.dense = c->d_flows;
-    int32_t rc = resample_blocking(c, seed, flags, fd);
+    cpm::SideDest side;
+    side.flows.dense = c->d_flows;
+    int32_t rc = resample_blocking(c, seed, flags, side);
     if (rc != CPM_OK) return rc;
     const size_t zt = static_cast<size_t>(c->Z * c->T);
     std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
@@ -2022,10 +2023,10 @@ int32_t cpm_resample_stays_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, void *
     if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
     if (!d_stays) return fail(CPM_ERR_ARG, "null d_stays");
     if (!d_parked) return fail(CPM_ERR_ARG, "null d_parked");
-    cpm::StaysDest sd;
-    sd.stays = static_cast<int32_t *>(d_stays);
-    sd.parked = static_cast<int32_t *>(d_parked);
-    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), cpm::FlowsDest{}, sd);
+    cpm::SideDest side;
+    side.stays.stays = static_cast<int32_t *>(d_stays);
+    side.stays.parked = static_cast<int32_t *>(d_parked);
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), side);
 }
 
 int32_t cpm_resample_stays(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, int32_t *stays_out,
@@ -2047,10 +2048,10 @@ int32_t cpm_resample_stays(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     const size_t zt = static_cast<size_t>(c->Z * c->T), cells = zt * static_cast<size_t>(c->T);
     if (!c->d_stays) HIP_TRY(hipMalloc(&c->d_stays, sizeof(int32_t) * std::max<size_t>(cells, 1)));
     if (!c->d_stay_parked) HIP_TRY(hipMalloc(&c->d_stay_parked, sizeof(int32_t) * std::max<size_t>(zt, 1)));
-    cpm::StaysDest sd;
-    sd.stays = c->d_stays;
-    sd.parked = c->d_stay_parked;
-    int32_t rc = resample_blocking(c, seed, flags, cpm::FlowsDest{}, sd);
+    cpm::SideDest side;
+    side.stays.stays = c->d_stays;
+    side.stays.parked = c->d_stay_parked;
+    int32_t rc = resample_blocking(c, seed, flags, side);
     if (rc != CPM_OK) return rc;
     std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
     std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
@@ -2069,9 +2070,9 @@ int32_t cpm_resample_paths_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, void *
     CTX_TRY(c);
     if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
     if (!d_paths) return fail(CPM_ERR_ARG, "null d_paths");
-    cpm::PathsDest pd;
-    pd.paths = static_cast<uint32_t *>(d_paths);
-    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), cpm::FlowsDest{}, cpm::StaysDest{}, pd);
+    cpm::SideDest side;
+    side.paths.paths = static_cast<uint32_t *>(d_paths);
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), side);
 }
 
 int32_t cpm_resample_paths(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, uint32_t *paths_out)
@@ -2096,9 +2097,9 @@ int32_t cpm_resample_paths(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
         HIP_TRY(hipMalloc(&c->d_paths, sizeof(uint32_t) * static_cast<size_t>(std::max<int64_t>(words, 1))));
         c->paths_cap = words;
     }
-    cpm::PathsDest pd;
-    pd.paths = c->d_paths;
-    int32_t rc = resample_blocking(c, seed, flags, cpm::FlowsDest{}, cpm::StaysDest{}, pd);
+    cpm::SideDest side;
+    side.paths.paths = c->d_paths;
+    int32_t rc = resample_blocking(c, seed, flags, side);
     if (rc != CPM_OK) return rc;
     const size_t zt = static_cast<size_t>(c->Z * c->T);
     std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
@@ -2163,12 +2164,12 @@ int32_t cpm_resample_flows_csr_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, vo
     if (!d_row_ptr) return fail(CPM_ERR_ARG, "null d_row_ptr");
     if (cap < 0) return fail(CPM_ERR_ARG, "negative cap");
     if (cap > 0 && (!d_dest || !d_count)) return fail(CPM_ERR_ARG, "null d_dest / d_count with cap > 0");
-    cpm::FlowsDest fd;
-    fd.row_ptr = static_cast<int64_t *>(d_row_ptr);
-    fd.dest = static_cast<int32_t *>(d_dest);
-    fd.count = static_cast<int32_t *>(d_count);
-    fd.cap = cap;
-    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), fd);
+    cpm::SideDest side;
+    side.flows.row_ptr = static_cast<int64_t *>(d_row_ptr);
+    side.flows.dest = static_cast<int32_t *>(d_dest);
+    side.flows.count = static_cast<int32_t *>(d_count);
+    side.flows.cap = cap;
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), side);
 }
 
 int32_t cpm_resample_flows_csr(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, int64_t *row_ptr_out,
@@ -2206,12 +2207,12 @@ int32_t cpm_resample_flows_csr(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_
     int32_t rc = ensure_entries(std::max<int64_t>(std::min<int64_t>(bound, (int64_t{1} << 30) / 8), 1));
     if (rc != CPM_OK) return rc;
     for (int attempt = 0;; ++attempt) {
-        cpm::FlowsDest fd;
-        fd.row_ptr = c->d_csr_row_ptr;
-        fd.dest = c->d_csr_dest;
-        fd.count = c->d_csr_count;
-        fd.cap = c->csr_cap;
-        rc = resample_blocking(c, seed, flags, fd);
+        cpm::SideDest side;
+        side.flows.row_ptr = c->d_csr_row_ptr;
+        side.flows.dest = c->d_csr_dest;
+        side.flows.count = c->d_csr_count;
+        side.flows.cap = c->csr_cap;
+        rc = resample_blocking(c, seed, flags, side);
         if (rc != CPM_OK) return rc;
         // (the rows of the attempt whose counts were fetched: every attempt writes all of row_ptr, and the last one enqueued is the one returned)
         HIP_TRY(hipMemcpyAsync(row_ptr_out, c->d_csr_row_ptr, sizeof(int64_t) * (zt + 1), hipMemcpyDeviceToHost, c->stream));

@@ -468,9 +468,11 @@ inline void exact_launch_sample(hipStream_t stream, const uint32_t *ids, const u
 template <typename F1, typename F2>
 int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, const double *d_cdf, int Z, int Zp, int T, int64_t n, CarIndex cars,
                   const uint32_t *d_zone0, uint64_t seed, bool travel, const double *d_dm, int64_t *d_counts, int cu_count, F1 prof_begin,
-                  F2 prof_end, std::string &err, bool ivp = false, uint32_t *d_zone0_out = nullptr, FlowsDest fd = FlowsDest{},
-                  StaysDest sd = StaysDest{}, PathsDest paths = PathsDest{})
+                  F2 prof_end, std::string &err, bool ivp = false, uint32_t *d_zone0_out = nullptr, SideDest side = SideDest{})
 {
+    const FlowsDest &fd = side.flows;
+    const StaysDest &sd = side.stays;
+    const PathsDest &paths = side.paths;
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP;

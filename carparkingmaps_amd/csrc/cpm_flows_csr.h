@@ -1,6 +1,6 @@
 // cpm_flows_csr.h -- the hourly origin-destination trip counts of a resample as compressed sparse rows (include/cpm_flows_csr.h): the
 // non-zero cells of flows[t][o][d] (cpm_flows.h), row r = t * Z + o, destinations ascending.  Nothing here touches a kernel of
-// cpm_flows.h: the grouped family's rows come from the same runs k_grouped_flows reads, by three launches
+// cpm_flows.h: the grouped family's rows come from the drivers' runs, through the reader of cpm_runs.h, by three launches
 //   k_flows_csr_count   the row's histogram in LDS, its non-zero bins counted              -> row_ptr[r + 1] = nnz of row r
 //   k_flows_csr_scan    one block: prefix of those in (t, o) order                         -> row_ptr[r + 1] = end of row r
 //   k_flows_csr_fill    the histogram again, its non-zero bins compacted in LDS            -> dest / count [row_ptr[r] ..)
@@ -18,25 +18,11 @@
 
 namespace cpm {
 
-// Where the flows of a step go: nowhere, the dense tensor (cpm_flows.h), or CSR arrays.
-struct FlowsDest {
-    int32_t *dense = nullptr;    // DEVICE int32[T][Z][Z]
-    int64_t *row_ptr = nullptr;  // DEVICE int64[T * Z + 1]: the CSR form
-    int32_t *dest = nullptr;     // DEVICE int32[cap]
-    int32_t *count = nullptr;    // DEVICE int32[cap]
-    int64_t cap = 0;             // entries dest / count hold: nothing is stored at or behind it
-    int32_t *hour_block = nullptr;  // DEVICE int32[Z * Z + 4], scratch of the per-car families (one hour's dense block)
-    bool csr() const { return row_ptr != nullptr; }
-    bool any() const { return dense != nullptr || row_ptr != nullptr; }
-};
-
-constexpr int kCsrBlock = 256;      // = kFlowsBlock: the run loads are k_grouped_flows'
-constexpr int kCsrWaves = kCsrBlock / 64;
+constexpr int kCsrWaves = kRunsBlock / 64;  // (every row kernel here runs blocks of kRunsBlock threads, whether it reads runs or not)
 constexpr int kCsrScanBlock = 1024;
 constexpr int kCsrScanItems = 4;    // consecutive rows per thread and tile
-static_assert(kCsrBlock == kFlowsBlock, "the CSR kernels load the runs as k_grouped_flows does");
 
-// LDS: the histogram (as k_grouped_flows, three words of slack for a dense row off a 16-byte boundary); the fill adds the row's
+// LDS: the histogram (as k_grouped_flows', three words of slack for a dense row off a 16-byte boundary); the fill adds the row's
 // compacted destinations, shifted by up to three words so that LDS and output addresses agree modulo 16 bytes
 __host__ __device__ inline uint32_t flows_csr_quads(int Z) { return (static_cast<uint32_t>(Z) + 3u + 3u) / 4u; }  // (16-byte pieces of one array: flows_lds_bytes(Z) / 16)
 inline size_t flows_csr_lds_bytes(int Z, bool fill) { return static_cast<size_t>(flows_csr_quads(Z)) * 16 * (fill ? 2 : 1); }
@@ -87,19 +73,19 @@ __device__ __forceinline__ void flows_csr_row_tail(const uint32_t *bins, uint32_
         // their neighbours (and for the counts of a caller whose two arrays are aligned differently)
         const uint32_t end = shift + m;
         const uint32_t nquad = (end + 3u) / 4u;
-        const flows_u32x4 *stage4 = reinterpret_cast<const flows_u32x4 *>(stage);
+        const runs_u32x4 *stage4 = reinterpret_cast<const runs_u32x4 *>(stage);
         int32_t *d16 = drow - shift, *c16 = crow - shift;
-        for (uint32_t i = tid; i < nquad; i += kCsrBlock) {
+        for (uint32_t i = tid; i < nquad; i += kRunsBlock) {
             const uint32_t w0 = 4u * i;
-            flows_u32x4 d = stage4[i], c;  // (words outside [shift, shift + nnz) are zero: a valid bin)
+            runs_u32x4 d = stage4[i], c;  // (words outside [shift, shift + nnz) are zero: a valid bin)
             c.x = bins[min(d.x, Z - 1u)];
             c.y = bins[min(d.y, Z - 1u)];
             c.z = bins[min(d.z, Z - 1u)];
             c.w = bins[min(d.w, Z - 1u)];
             const bool whole = w0 >= shift && w0 + 4u <= end;
-            if (whole) *reinterpret_cast<flows_u32x4 *>(d16 + w0) = d;
+            if (whole) *reinterpret_cast<runs_u32x4 *>(d16 + w0) = d;
             if (whole && count_wide) {
-                *reinterpret_cast<flows_u32x4 *>(c16 + w0) = c;
+                *reinterpret_cast<runs_u32x4 *>(c16 + w0) = c;
             } else {
                 const uint32_t dv[4] = {d.x, d.y, d.z, d.w}, cv[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
@@ -115,72 +101,39 @@ __device__ __forceinline__ void flows_csr_row_tail(const uint32_t *bins, uint32_
 }
 
 // One block per (origin zone, hour), the arguments and the two grids of k_grouped_flows.  row_ptr is that of the launch's first hour:
-// row_ptr[r], r = blockIdx.y * Z + zone.  The run loads are k_grouped_flows': length and the first four 16-byte pieces requested
-// together, the LDS zeroed while they fly, the tail masked by length, longer runs by further passes.
+// row_ptr[r], r = blockIdx.y * Z + zone.
 template <bool FILL>
 __device__ __forceinline__ void flows_csr_grouped(const uint32_t *__restrict__ D, const uint32_t *__restrict__ cntg, int Z, uint32_t scap, uint32_t idbits, uint32_t zpg,
                                                   size_t d_stride, size_t c_stride, int64_t *__restrict__ row_ptr, int32_t *__restrict__ dest,
                                                   int32_t *__restrict__ count, int64_t cap)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t csr_lds[];
-    const int z = blockIdx.x;
-    const int tid = threadIdx.x;
-    const uint32_t g = static_cast<uint32_t>(tid) >> 3, j = static_cast<uint32_t>(tid) & 7u;
-    D += d_stride * blockIdx.y + (static_cast<size_t>(z) * kFlowRuns + g) * scap;
-    const uint32_t len_raw = cntg[c_stride * blockIdx.y + static_cast<size_t>(z) * kFlowRuns + g];
-    flows_u32x4 q[kFlowsQuads];
-#pragma unroll
-    for (int u = 0; u < kFlowsQuads; ++u) {
-        const uint32_t k = min((j + 8u * u) * 4u, scap - 4u);
-        q[u] = *reinterpret_cast<const flows_u32x4 *>(D + k);
-    }
-    int64_t *rp = row_ptr + static_cast<size_t>(blockIdx.y) * Z + z;
+    RunLane r = run_open(D, cntg, scap, d_stride * blockIdx.y, c_stride * blockIdx.y);
+    int64_t *rp = row_ptr + static_cast<size_t>(blockIdx.y) * Z + blockIdx.x;
     int64_t start = 0;
     if constexpr (FILL) start = rp[0];
     const uint32_t nquad = flows_csr_quads(Z) * (FILL ? 2u : 1u);  // (histogram and, FILL, the staged row)
-    flows_u32x4 *lds4 = reinterpret_cast<flows_u32x4 *>(csr_lds);
-    for (uint32_t i = tid; i < nquad; i += kCsrBlock) lds4[i] = flows_u32x4{0u, 0u, 0u, 0u};
+    runs_u32x4 *lds4 = reinterpret_cast<runs_u32x4 *>(csr_lds);
+    for (uint32_t i = threadIdx.x; i < nquad; i += kRunsBlock) lds4[i] = runs_u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
-    const uint32_t len = min(len_raw, scap);  // (a run that outgrew scap has raised the status word: the attempt is discarded)
-    const uint32_t gbase = g * zpg;
-    auto bin = [&](uint32_t entry, uint32_t at) {
-        const uint32_t b = gbase + (entry >> idbits);
-        if (at < len && b < static_cast<uint32_t>(Z)) atomicAdd(&csr_lds[b], 1u);
-    };
-#pragma unroll
-    for (int u = 0; u < kFlowsQuads; ++u) {
-        const uint32_t k = (j + 8u * u) * 4u;
-        bin(q[u].x, k);
-        bin(q[u].y, k + 1u);
-        bin(q[u].z, k + 2u);
-        bin(q[u].w, k + 3u);
-    }
-    for (uint32_t k0 = 32u * kFlowsQuads; k0 < len; k0 += 32u * kFlowsQuads) {
-#pragma unroll
-        for (int u = 0; u < kFlowsQuads; ++u) {
-            const uint32_t k = min(k0 + (j + 8u * u) * 4u, scap - 4u);
-            q[u] = *reinterpret_cast<const flows_u32x4 *>(D + k);
-        }
-#pragma unroll
-        for (int u = 0; u < kFlowsQuads; ++u) {
-            const uint32_t k = k0 + (j + 8u * u) * 4u;  // (at or behind the run's end where the load above was clamped: masked)
-            bin(q[u].x, k);
-            bin(q[u].y, k + 1u);
-            bin(q[u].z, k + 2u);
-            bin(q[u].w, k + 3u);
-        }
-    }
+    const uint32_t gbase = r.g * zpg;
+    run_walk(r, [&](uint32_t k0, uint32_t len) {
+        run_entries(r, k0, len, [&](int, uint32_t entry, bool live) {
+            const uint32_t b = gbase + (entry >> idbits);
+            if (live && b < static_cast<uint32_t>(Z)) atomicAdd(&csr_lds[b], 1u);
+        });
+    });
     __syncthreads();
     flows_csr_row_tail<FILL>(csr_lds, csr_lds + 4u * flows_csr_quads(Z), static_cast<uint32_t>(Z), rp + 1, start, dest, count, cap);
 }
 
-__global__ __launch_bounds__(kCsrBlock) void k_flows_csr_count(const uint32_t *__restrict__ D, const uint32_t *__restrict__ cntg, int Z, uint32_t scap,
+__global__ __launch_bounds__(kRunsBlock) void k_flows_csr_count(const uint32_t *__restrict__ D, const uint32_t *__restrict__ cntg, int Z, uint32_t scap,
                                                                uint32_t idbits, uint32_t zpg, size_t d_stride, size_t c_stride, int64_t *__restrict__ row_ptr)
 {
     flows_csr_grouped<false>(D, cntg, Z, scap, idbits, zpg, d_stride, c_stride, row_ptr, nullptr, nullptr, 0);
 }
 
-__global__ __launch_bounds__(kCsrBlock) void k_flows_csr_fill(const uint32_t *__restrict__ D, const uint32_t *__restrict__ cntg, int Z, uint32_t scap,
+__global__ __launch_bounds__(kRunsBlock) void k_flows_csr_fill(const uint32_t *__restrict__ D, const uint32_t *__restrict__ cntg, int Z, uint32_t scap,
                                                               uint32_t idbits, uint32_t zpg, size_t d_stride, size_t c_stride, int64_t *__restrict__ row_ptr,
                                                               int32_t *__restrict__ dest, int32_t *__restrict__ count, int64_t cap)
 {
@@ -230,38 +183,24 @@ __global__ __launch_bounds__(kCsrScanBlock) void k_flows_csr_scan(int64_t *__res
 // The per-car families: one block per row o of ONE hour's dense block (k_flows_cars' output, Z x Z, four words of slack behind it),
 // read in 16-byte pieces into the LDS the grouped kernels build their histogram in.  row_ptr is the hour's: row_ptr[o].
 template <bool FILL>
-__global__ __launch_bounds__(kCsrBlock) void k_flows_csr_from_dense(const int32_t *__restrict__ block, int Z, int64_t *__restrict__ row_ptr,
+__global__ __launch_bounds__(kRunsBlock) void k_flows_csr_from_dense(const int32_t *__restrict__ block, int Z, int64_t *__restrict__ row_ptr,
                                                                     int32_t *__restrict__ dest, int32_t *__restrict__ count, int64_t cap)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t csr_lds[];
     const uint32_t o = blockIdx.x, tid = threadIdx.x;
     const size_t first = static_cast<size_t>(o) * Z;
     const uint32_t shift = static_cast<uint32_t>(first & 3u);  // (the block is 16-byte aligned: a row starts `shift` words into a piece)
-    const flows_u32x4 *src4 = reinterpret_cast<const flows_u32x4 *>(block + (first - shift));
+    const runs_u32x4 *src4 = reinterpret_cast<const runs_u32x4 *>(block + (first - shift));
     const uint32_t nrow = (static_cast<uint32_t>(Z) + shift + 3u) / 4u;
     const uint32_t nquad = flows_csr_quads(Z);
     int64_t start = 0;
     if constexpr (FILL) start = row_ptr[o];
-    flows_u32x4 *lds4 = reinterpret_cast<flows_u32x4 *>(csr_lds);
-    for (uint32_t i = tid; i < nquad; i += kCsrBlock) lds4[i] = i < nrow ? src4[i] : flows_u32x4{0u, 0u, 0u, 0u};
+    runs_u32x4 *lds4 = reinterpret_cast<runs_u32x4 *>(csr_lds);
+    for (uint32_t i = tid; i < nquad; i += kRunsBlock) lds4[i] = i < nrow ? src4[i] : runs_u32x4{0u, 0u, 0u, 0u};
     if constexpr (FILL)
-        for (uint32_t i = tid; i < nquad; i += kCsrBlock) lds4[nquad + i] = flows_u32x4{0u, 0u, 0u, 0u};
+        for (uint32_t i = tid; i < nquad; i += kRunsBlock) lds4[nquad + i] = runs_u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
     flows_csr_row_tail<FILL>(csr_lds + shift, csr_lds + 4u * nquad, static_cast<uint32_t>(Z), row_ptr + o + 1, start, dest, count, cap);
-}
-
-// LDS above 48 KiB is asked for by name, per kernel and device, and the answer is read (as flows_lds_opt_in).
-inline hipError_t flows_csr_lds_opt_in(int which, const void *kernel, size_t lds)
-{
-    if (lds <= 48 * 1024) return hipSuccess;
-    static size_t granted[4][64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64 && granted[which][dev] >= lds) return hipSuccess;
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e == hipSuccess && dev >= 0 && dev < 64) granted[which][dev] = lds;
-    return e;
 }
 
 inline int32_t flows_csr_check(int Z, const FlowsDest &fd, std::string &err)
@@ -290,15 +229,15 @@ inline int32_t flows_csr_launch_grouped(hipStream_t stream, const uint32_t *D, c
     const int32_t rc = flows_csr_check(Z, fd, err);
     if (rc != CPM_OK) return rc;
     const size_t lds_c = flows_csr_lds_bytes(Z, false), lds_f = flows_csr_lds_bytes(Z, true);
-    hipError_t e = flows_csr_lds_opt_in(0, reinterpret_cast<const void *>(k_flows_csr_count), lds_c);
-    if (e == hipSuccess) e = flows_csr_lds_opt_in(1, reinterpret_cast<const void *>(k_flows_csr_fill), lds_f);
+    hipError_t e = lds_opt_in(k_flows_csr_count, lds_c);
+    if (e == hipSuccess) e = lds_opt_in(k_flows_csr_fill, lds_f);
     if (e != hipSuccess) return flows_csr_fail(e, "LDS", err);
     int64_t *rp = fd.row_ptr + static_cast<size_t>(t0) * Z;
     const dim3 grid(static_cast<unsigned>(Z), static_cast<unsigned>(nt));
-    launch(k_flows_csr_count, grid, dim3(kCsrBlock), lds_c, stream, D, cntg, Z, scap, idbits, zpg, d_stride, c_stride, rp);
+    launch(k_flows_csr_count, grid, dim3(kRunsBlock), lds_c, stream, D, cntg, Z, scap, idbits, zpg, d_stride, c_stride, rp);
     launch(k_flows_csr_scan, dim3(1), dim3(kCsrScanBlock), 0, stream, rp, static_cast<uint32_t>(nt) * static_cast<uint32_t>(Z), t0 == 0 ? 1 : 0);
     if (fd.cap > 0)
-        launch(k_flows_csr_fill, grid, dim3(kCsrBlock), lds_f, stream, D, cntg, Z, scap, idbits, zpg, d_stride, c_stride, rp, fd.dest, fd.count, fd.cap);
+        launch(k_flows_csr_fill, grid, dim3(kRunsBlock), lds_f, stream, D, cntg, Z, scap, idbits, zpg, d_stride, c_stride, rp, fd.dest, fd.count, fd.cap);
     if ((e = hipGetLastError()) != hipSuccess) return flows_csr_fail(e, "launch", err);
     return CPM_OK;
 }
@@ -318,16 +257,16 @@ inline int32_t flows_hour_from_cars(hipStream_t stream, const FlowsDest &fd, con
     const int32_t rc = flows_csr_check(Z, fd, err);
     if (rc != CPM_OK) return rc;
     const size_t lds_c = flows_csr_lds_bytes(Z, false), lds_f = flows_csr_lds_bytes(Z, true);
-    e = flows_csr_lds_opt_in(2, reinterpret_cast<const void *>(k_flows_csr_from_dense<false>), lds_c);
-    if (e == hipSuccess) e = flows_csr_lds_opt_in(3, reinterpret_cast<const void *>(k_flows_csr_from_dense<true>), lds_f);
+    e = lds_opt_in(k_flows_csr_from_dense<false>, lds_c);
+    if (e == hipSuccess) e = lds_opt_in(k_flows_csr_from_dense<true>, lds_f);
     if (e != hipSuccess) return flows_csr_fail(e, "LDS", err);
     if ((e = hipMemsetAsync(fd.hour_block, 0, sizeof(int32_t) * (static_cast<size_t>(Z) * Z + 4), stream)) != hipSuccess) return flows_csr_fail(e, "hour block", err);
     if ((e = flows_launch_cars(stream, zsrc, off, rec_t, n, Z, fd.hour_block)) != hipSuccess) return flows_csr_fail(e, "flows of the hour", err);
     int64_t *rp = fd.row_ptr + static_cast<size_t>(t) * Z;
-    launch(k_flows_csr_from_dense<false>, dim3(static_cast<unsigned>(Z)), dim3(kCsrBlock), lds_c, stream, fd.hour_block, Z, rp, static_cast<int32_t *>(nullptr),
+    launch(k_flows_csr_from_dense<false>, dim3(static_cast<unsigned>(Z)), dim3(kRunsBlock), lds_c, stream, fd.hour_block, Z, rp, static_cast<int32_t *>(nullptr),
            static_cast<int32_t *>(nullptr), static_cast<int64_t>(0));
     launch(k_flows_csr_scan, dim3(1), dim3(kCsrScanBlock), 0, stream, rp, static_cast<uint32_t>(Z), t == 0 ? 1 : 0);
-    if (fd.cap > 0) launch(k_flows_csr_from_dense<true>, dim3(static_cast<unsigned>(Z)), dim3(kCsrBlock), lds_f, stream, fd.hour_block, Z, rp, fd.dest, fd.count, fd.cap);
+    if (fd.cap > 0) launch(k_flows_csr_from_dense<true>, dim3(static_cast<unsigned>(Z)), dim3(kRunsBlock), lds_f, stream, fd.hour_block, Z, rp, fd.dest, fd.count, fd.cap);
     if ((e = hipGetLastError()) != hipSuccess) return flows_csr_fail(e, "launch", err);
     return CPM_OK;
 }

@@ -2903,12 +2903,12 @@ __global__ __launch_bounds__(256) void k_grouped_zero(unsigned long long *__rest
 template <typename F1, typename F2>
 int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb, int64_t n, CarIndex cars, const uint32_t *d_zone0,
                     uint64_t seed, bool travel, int64_t *d_counts, int cu_count, F1 prof_begin, F2 prof_end, std::string &err, bool ivp = false,
-                    uint32_t *d_zone0_out = nullptr, FlowsDest fd = FlowsDest{}, StaysDest sd = StaysDest{}, PathsDest pd = PathsDest{})
+                    uint32_t *d_zone0_out = nullptr, SideDest side = SideDest{})
 {
-    static_assert(kFlowRuns == kGroups, "k_grouped_flows reads the runs of cpm_grouped.h");
-    static_assert(kStayRuns == kGroups, "k_grouped_stays reads the runs of cpm_grouped.h");
-    static_assert(kPathRuns == kGroups, "k_grouped_paths reads the runs of cpm_grouped.h");
-    int32_t *const d_flows = fd.dense;
+    static_assert(kRunsPerZone == kGroups, "the reader of cpm_runs.h reads the runs of cpm_grouped.h");
+    const FlowsDest &fd = side.flows;
+    const StaysDest &sd = side.stays;
+    const PathsDest &pd = side.paths;
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP;
@@ -2928,7 +2928,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     unsigned long long *tt_sum = parking + 2 * static_cast<size_t>(T) * Z;
     unsigned long long *status = tt_sum + 1;
     // travel times: from the runs, by one launch per hour -- or, when the runs of all hours fit, by one launch at the end
-    // OD trip counts (cpm_flows.h, d_flows: int32[T][Z][Z]): from the same runs.  By one launch per hour (the default: measured)
+    // OD trip counts (cpm_flows.h, fd.dense: int32[T][Z][Z]): from the same runs.  By one launch per hour (the default: measured)
     // unless the runs are kept anyway (travel times), the context asks for the kept form (flows_kept), or the day launch runs,
     // which has no hourly boundary to launch behind -- what a travel resample does under the same mode.  The CSR form of the same
     // counts (cpm_flows_csr.h, fd.row_ptr) takes the dense form's place launch for launch.
@@ -2942,6 +2942,17 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     const bool stays = sd.any() && !ivp;
     const bool paths = pd.any() && !ivp;
     const bool history = (travel || (flows && (w.flows_kept || w.fused_day)) || ((stays || paths) && w.fused_day)) && !ivp && w.ensure_history();
+    // hours t0 .. t0 + nt - 1 of the flows from the runs at D / cntg: grid (Z, 1) behind an hour, (Z, T) over the kept runs
+    auto flows_hours = [&](const uint32_t *D, const uint32_t *cntg, size_t d_stride, size_t c_stride, int t0, int nt) -> int32_t {
+        return fd.csr() ? flows_csr_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, d_stride, c_stride, t0, nt, fd, err)
+                        : flows_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, d_stride, c_stride, t0, nt, fd.dense, err);
+    };
+    // the stays and the paths of hour t from its runs at D / cntg: behind the hour's launches, or hour by hour over the kept runs
+    auto side_hour = [&](const uint32_t *D, const uint32_t *cntg, int t) -> int32_t {
+        int32_t rc_side = stays ? stays_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, T, t, n, sd, err) : CPM_OK;
+        if (rc_side == CPM_OK && paths) rc_side = paths_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, t, n, d_zone0, pd, err);
+        return rc_side;
+    };
     const int G = tb.G;
     const size_t rw = static_cast<size_t>(pack_row_words(tb.Zq, G, tb.smap));
     const int64_t mean = (n + Z - 1) / Z;
@@ -3139,38 +3150,21 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
             else launch(k_grouped_travel<false>, dim3(Z, 1), dim3(travel_block(mean, w.parts > 1)), 0, stream, a.D, a.cntg, Z, w.scap, w.idbits, tr);
             prof_end(CPM_PROFILE_TRAVEL);
         }
-        if (flows && !history) {  // (grouped: the hour's drivers are in their runs, placed or pending)
-            const int32_t rc_fl = fd.csr() ? flows_csr_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, 0, 0, t, 1, fd, err)
-                                           : flows_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, 0, 0, t, 1, d_flows, err);
-            if (rc_fl != CPM_OK) return rc_fl;
-        }
-        if (stays && !history) {
-            const int32_t rc_st = stays_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, T, t, n, sd, err);
-            if (rc_st != CPM_OK) return rc_st;
-        }
-        if (paths && !history) {
-            const int32_t rc_pa = paths_launch_grouped(stream, a.D, a.cntg, Z, w.scap, w.idbits, w.zpg, t, n, d_zone0, pd, err);
-            if (rc_pa != CPM_OK) return rc_pa;
+        if (!history) {  // (grouped: the hour's drivers are in their runs, placed or pending)
+            int32_t rc_side = flows ? flows_hours(a.D, a.cntg, 0, 0, t, 1) : CPM_OK;
+            if (rc_side == CPM_OK) rc_side = side_hour(a.D, a.cntg, t);
+            if (rc_side != CPM_OK) return rc_side;
         }
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "grouped zone hour launch");
     }
-    if (paths && history) {  // the kept runs of all hours: T pairs of launches, in hour order
+    if ((stays || paths) && history) {  // the kept runs of all hours: T sets of launches, in hour order
         for (int t = 0; t < T; ++t) {
-            const int32_t rc_pa = paths_launch_grouped(stream, w.Dq + w.run_words() * static_cast<size_t>(t), w.cntg + w.len_words() * static_cast<size_t>(t), Z,
-                                                       w.scap, w.idbits, w.zpg, t, n, d_zone0, pd, err);
-            if (rc_pa != CPM_OK) return rc_pa;
+            const int32_t rc_side = side_hour(w.Dq + w.run_words() * static_cast<size_t>(t), w.cntg + w.len_words() * static_cast<size_t>(t), t);
+            if (rc_side != CPM_OK) return rc_side;
         }
     }
-    if (stays && history) {  // the kept runs of all hours: T launches, in hour order
-        for (int t = 0; t < T; ++t) {
-            const int32_t rc_st = stays_launch_grouped(stream, w.Dq + w.run_words() * static_cast<size_t>(t), w.cntg + w.len_words() * static_cast<size_t>(t), Z,
-                                                       w.scap, w.idbits, w.zpg, T, t, n, sd, err);
-            if (rc_st != CPM_OK) return rc_st;
-        }
-    }
-    if (flows && history) {  // the kept runs of all hours: one launch, grid (Z, T)
-        const int32_t rc_fl = fd.csr() ? flows_csr_launch_grouped(stream, w.Dq, w.cntg, Z, w.scap, w.idbits, w.zpg, w.run_words(), w.len_words(), 0, T, fd, err)
-                                       : flows_launch_grouped(stream, w.Dq, w.cntg, Z, w.scap, w.idbits, w.zpg, w.run_words(), w.len_words(), 0, T, d_flows, err);
+    if (flows && history) {  // the kept runs of all hours: one set of launches, grid (Z, T)
+        const int32_t rc_fl = flows_hours(w.Dq, w.cntg, w.run_words(), w.len_words(), 0, T);
         if (rc_fl != CPM_OK) return rc_fl;
     }
     if (travel && history) {  // every hour's drivers are still in their runs: one launch

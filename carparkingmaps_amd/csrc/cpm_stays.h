@@ -4,8 +4,8 @@
 //   stays[(t*Z + z)*T + L] = cars with state_matrix[i,t] == z+1, transition_matrix[i,t,1] == 1 and t - a(i,t) == L.
 //   parked[z*T + a]        = cars with state_matrix[i,T-1] == z+1 that did not drive in hour T-1 and have a(i,T-1) == a.
 // This is the first per-car quantity carried ACROSS hours on the grouped path, whose buckets forget which car is which: a driver's
-// entry in its origin zone's 32 runs is id | local destination << idbits (cpm_grouped.h: Dq / cntg), id the context-local car index,
-// and the side array last[n] is indexed by it:
+// entry in its origin zone's runs (cpm_runs.h) is id | local destination << idbits, id the context-local car index, and the side
+// array last[n] is indexed by it:
 //   last[i] = since << 24 | zone: the car has been parked in `zone` since hour `since` (= the hour of its last drive + 1, at most T:
 //   8 bits, T <= 255; zone < 2^24); 0 = where the day began (the context's zone0[i]), since hour 0.
 // Zeroed at the start of every attempt.  A car drives at most once an hour and sits in one zone, so the launches of ONE hour never
@@ -18,78 +18,47 @@
 #include <string>
 
 #include "cpm_kernels.h"
+#include "cpm_runs.h"
 
 namespace cpm {
 
-constexpr int kStayRuns = 32;          // runs per origin zone (= kGroups of cpm_grouped.h, asserted where the kernel is launched)
-constexpr int kStaysBlock = 256;       // 8 lanes per run, as k_grouped_flows
-constexpr int kStaysQuads = 4;         // 16-byte loads a lane has in flight per pass over its run; 16 gathers of last[] behind them
-constexpr int kStaysWaves = kStaysBlock / 64;
+constexpr int kStaysWaves = kRunsBlock / 64;
 constexpr int kStaysSmall = 4;         // stay lengths counted in registers (most stays are short: one LDS address would serialise)
 constexpr int kStaysMaxT = 255;        // `since` is 8 bits of the word
 constexpr uint32_t kStaySinceShift = 24;
 constexpr uint32_t kStayZoneMask = (1u << kStaySinceShift) - 1u;
-typedef uint32_t stays_u32x4 __attribute__((ext_vector_type(4)));
-
-// where the stays of a step go: nowhere, or DEVICE int32[T][Z][T] + int32[Z][T], with the side array of the context
-struct StaysDest {
-    int32_t *stays = nullptr;
-    int32_t *parked = nullptr;
-    uint32_t *last = nullptr;  // DEVICE uint32[n], zeroed by the caller at the start of the attempt
-    bool any() const { return stays != nullptr; }
-};
 
 inline size_t stays_lds_bytes(int T) { return sizeof(uint32_t) * kStaysWaves * static_cast<size_t>(T); }
 
 // One block per origin zone, ONE hour (t) per launch: the runs of the hour at D / cntg.  stays_t is the hour's [Z][T] block.
 // Every (t, z) row is written by exactly one block, empty zones included: no global atomic, no memset of the output.
-__global__ __launch_bounds__(kStaysBlock) void k_grouped_stays(const uint32_t *__restrict__ D, const uint32_t *__restrict__ cntg, int Z, uint32_t scap,
-                                                               uint32_t idbits, uint32_t zpg, int T, int t, uint32_t n, uint32_t *__restrict__ last,
-                                                               int32_t *__restrict__ stays_t)
+__global__ __launch_bounds__(kRunsBlock) void k_grouped_stays(const uint32_t *__restrict__ D, const uint32_t *__restrict__ cntg, int Z, uint32_t scap,
+                                                              uint32_t idbits, uint32_t zpg, int T, int t, uint32_t n, uint32_t *__restrict__ last,
+                                                              int32_t *__restrict__ stays_t)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t stay_bins[];  // [kStaysWaves][T]: a histogram per wave
-    const int z = blockIdx.x;
     const int tid = threadIdx.x;
-    const uint32_t g = static_cast<uint32_t>(tid) >> 3, j = static_cast<uint32_t>(tid) & 7u;
-    D += (static_cast<size_t>(z) * kStayRuns + g) * scap;  // (scap is a multiple of 32 words: every run starts on a 128-byte line)
-    // the run's length and the lane's first pieces are requested together, as k_grouped_flows does: a run is scap >= 64 words
-    // whatever its length, so the loads of the first pass are in bounds (what lies behind the run's end is masked below)
-    const uint32_t len_raw = cntg[static_cast<size_t>(z) * kStayRuns + g];
-    stays_u32x4 q[kStaysQuads];
-#pragma unroll
-    for (int u = 0; u < kStaysQuads; ++u) {
-        const uint32_t k = min((j + 8u * u) * 4u, scap - 4u);
-        q[u] = *reinterpret_cast<const stays_u32x4 *>(D + k);
-    }
-    for (int i = tid; i < kStaysWaves * T; i += kStaysBlock) stay_bins[i] = 0u;
+    RunLane r = run_open(D, cntg, scap, 0, 0);
+    for (int i = tid; i < kStaysWaves * T; i += kRunsBlock) stay_bins[i] = 0u;
     __syncthreads();
-    const uint32_t len = min(len_raw, scap);  // (a run that outgrew scap has raised the status word: the attempt is discarded)
     const uint32_t idmask = (idbits >= 32) ? 0xFFFFFFFFu : ((1u << idbits) - 1u);
-    const uint32_t gbase = g * zpg;
+    const uint32_t gbase = r.g * zpg;
     const uint32_t now = static_cast<uint32_t>(t + 1) << kStaySinceShift;
     uint32_t *wbins = stay_bins + (static_cast<uint32_t>(tid) >> 6) * T;
     uint32_t small[kStaysSmall] = {};
     // a pass: the lane's 16 entries -> 16 gathers in flight -> bins and the new words
-    auto pass = [&](uint32_t k0) {
-        uint32_t id[4 * kStaysQuads], dest[4 * kStaysQuads], w[4 * kStaysQuads];
-        bool ok[4 * kStaysQuads];
+    run_walk(r, [&](uint32_t k0, uint32_t len) {
+        uint32_t id[4 * kRunsQuads], dest[4 * kRunsQuads], w[4 * kRunsQuads];
+        bool ok[4 * kRunsQuads];
+        run_entries(r, k0, len, [&](int s, uint32_t entry, bool live) {
+            id[s] = entry & idmask;
+            dest[s] = gbase + (entry >> idbits);
+            ok[s] = live && id[s] < n && dest[s] < static_cast<uint32_t>(Z);  // (nothing is gathered or stored out of range)
+        });
 #pragma unroll
-        for (int u = 0; u < kStaysQuads; ++u) {
-            const uint32_t e[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+        for (int s = 0; s < 4 * kRunsQuads; ++s) w[s] = ok[s] ? last[id[s]] : 0u;
 #pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const int s = 4 * u + x;
-                const uint32_t at = k0 + (j + 8u * u) * 4u + x;  // (at or behind the run's end where the load was clamped: masked)
-                id[s] = e[x] & idmask;
-                dest[s] = gbase + (e[x] >> idbits);
-                // entries of an overflowed attempt may be anything: nothing is gathered or stored out of range
-                ok[s] = at < len && id[s] < n && dest[s] < static_cast<uint32_t>(Z);
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 4 * kStaysQuads; ++s) w[s] = ok[s] ? last[id[s]] : 0u;
-#pragma unroll
-        for (int s = 0; s < 4 * kStaysQuads; ++s) {
+        for (int s = 0; s < 4 * kRunsQuads; ++s) {
             if (!ok[s]) continue;
             const uint32_t L = static_cast<uint32_t>(t) - (w[s] >> kStaySinceShift);  // (since <= t in a valid attempt; else masked)
 #pragma unroll
@@ -97,17 +66,7 @@ __global__ __launch_bounds__(kStaysBlock) void k_grouped_stays(const uint32_t *_
             if (L >= static_cast<uint32_t>(kStaysSmall) && L < static_cast<uint32_t>(T)) atomicAdd(&wbins[L], 1u);
             last[id[s]] = now | dest[s];
         }
-    };
-    pass(0u);
-    // runs longer than a pass (popular destination groups): the same again
-    for (uint32_t k0 = 32u * kStaysQuads; k0 < len; k0 += 32u * kStaysQuads) {
-#pragma unroll
-        for (int u = 0; u < kStaysQuads; ++u) {
-            const uint32_t k = min(k0 + (j + 8u * u) * 4u, scap - 4u);
-            q[u] = *reinterpret_cast<const stays_u32x4 *>(D + k);
-        }
-        pass(k0);
-    }
+    });
     // the short stays: summed across the wave, one LDS add per wave and length
 #pragma unroll
     for (int l = 0; l < kStaysSmall; ++l) {
@@ -117,40 +76,28 @@ __global__ __launch_bounds__(kStaysBlock) void k_grouped_stays(const uint32_t *_
         if ((tid & 63) == 0 && l < T && v) atomicAdd(&wbins[l], v);
     }
     __syncthreads();
-    // the row: T words, 16-byte stores where a piece lies wholly inside it (rows are 16-byte aligned at T = 24, not at T = 7)
-    int32_t *row = stays_t + static_cast<size_t>(z) * T;
-    const uint32_t shift = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(row) >> 2) & 3u;
-    int32_t *row16 = row - shift;
-    const uint32_t end = static_cast<uint32_t>(T) + shift;
-    const uint32_t nquad = (end + 3u) / 4u;
-    for (uint32_t i = tid; i < nquad; i += kStaysBlock) {
+    // the row: T words, the waves' histograms summed (rows are 16-byte aligned at T = 24, not at T = 7)
+    row_store_shifted(stays_t + static_cast<size_t>(blockIdx.x) * T, static_cast<uint32_t>(T), [&](uint32_t i, uint32_t shift) {
         uint32_t v[4];
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
-            const uint32_t wd = 4u * i + x;
+            const uint32_t wd = 4u * i + x - shift;  // (the row's word; wraps for the words in front of it)
             uint32_t s = 0u;
-            if (wd >= shift && wd < end) {
+            if (wd < static_cast<uint32_t>(T)) {
 #pragma unroll
-                for (int wv = 0; wv < kStaysWaves; ++wv) s += stay_bins[wv * T + (wd - shift)];
+                for (int wv = 0; wv < kStaysWaves; ++wv) s += stay_bins[wv * T + wd];
             }
             v[x] = s;
         }
-        const uint32_t w0 = 4u * i;
-        if (w0 >= shift && w0 + 4u <= end) {
-            *reinterpret_cast<stays_u32x4 *>(row16 + w0) = stays_u32x4{v[0], v[1], v[2], v[3]};
-        } else {
-#pragma unroll
-            for (int x = 0; x < 4; ++x)
-                if (w0 + x >= shift && w0 + x < end) row16[w0 + x] = static_cast<int32_t>(v[x]);
-        }
-    }
+        return runs_u32x4{v[0], v[1], v[2], v[3]};
+    });
 }
 
 // hour t from the runs at D / cntg
 inline int32_t stays_launch_grouped(hipStream_t stream, const uint32_t *D, const uint32_t *cntg, int Z, uint32_t scap, uint32_t idbits, uint32_t zpg, int T,
                                     int t, int64_t n, const StaysDest &sd, std::string &err)
 {
-    launch(k_grouped_stays, dim3(static_cast<unsigned>(Z)), dim3(kStaysBlock), stays_lds_bytes(T), stream, D, cntg, Z, scap, idbits, zpg, T, t,
+    launch(k_grouped_stays, dim3(static_cast<unsigned>(Z)), dim3(kRunsBlock), stays_lds_bytes(T), stream, D, cntg, Z, scap, idbits, zpg, T, t,
            static_cast<uint32_t>(n), sd.last, sd.stays + static_cast<size_t>(t) * Z * T);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -171,18 +118,7 @@ __global__ __launch_bounds__(256) void k_stays_cars(const uint32_t *__restrict__
     if (i >= n) return;
     const uint32_t r = rec_t[i];
     if (!(r & kDriveBit)) return;
-    uint32_t o;
-    if (off) {
-        uint32_t lo = 0, hi = static_cast<uint32_t>(Z);  // off[lo] <= i < off[hi]
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (off[mid] <= static_cast<uint32_t>(i)) lo = mid;
-            else hi = mid;
-        }
-        o = lo;
-    } else {
-        o = zsrc[i] & kZoneMask;
-    }
+    const uint32_t o = off ? slot_bucket(off, Z, static_cast<uint32_t>(i)) : zsrc[i] & kZoneMask;
     const uint32_t car = ids ? ids[i] : static_cast<uint32_t>(i);
     const uint32_t d = r & kZoneMask;
     if (o >= static_cast<uint32_t>(Z) || d >= static_cast<uint32_t>(Z) || car >= static_cast<uint64_t>(n)) return;
