@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import SIM_SEED, TABLE_SEED
+from dataset_edges import _ref_categorical
 from product_form import CAR, GROUPED, ZONE_LDS, at_least, auto_family, pinned
 
 pytestmark = pytest.mark.gpu
@@ -731,17 +732,6 @@ def test_few_cars_per_zone_uses_the_car_kernel_and_matches(cpm, O):
         with pinned(s, 0):
             r = s.resample(SIM_SEED)
     assert np.array_equal(r["parking"], ref["parking"]) and np.array_equal(r["driving"], ref["driving"])
-
-
-def _ref_categorical(cdf_row, k53):
-    """first j with u <= cdf[j] after the D1 clamp (oracle semantics), 1-based; 0 for an all-zero row"""
-    last = cdf_row[-1]
-    if last == 0.0:
-        return np.zeros(len(k53), dtype=np.int64)
-    u = k53.astype(np.float64) * 2.0 ** -53  # exact: k < 2^53
-    ue = np.where(u == 0.0, np.float64(5e-324), u)
-    ue = np.minimum(ue, last)
-    return np.searchsorted(cdf_row, ue, side="left").astype(np.int64) + 1
 
 
 def test_high_word_search_equals_the_f64_search_on_ties_and_edges(cpm, O):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, SIM_SEED, TABLE_SEED
+from dataset_edges import _probe_k53, _ref_categorical
 from product_form import GROUPED, pinned
 
 gpu = pytest.mark.gpu
@@ -21,25 +22,6 @@ ERR_TABLE = -4       # CPM_ERR_TABLE
 
 def _zone0(C, cpz):
     return np.arange(C, dtype=np.int64) // cpz + 1
-
-
-def _ref_categorical(cdf_row, k53):
-    """first j with u <= cdf[j] after the D1 clamp (oracle semantics), 1-based; 0 for an all-zero row"""
-    last = cdf_row[-1]
-    if last == 0.0:
-        return np.zeros(len(k53), dtype=np.int64)
-    u = k53.astype(np.float64) * 2.0 ** -53  # exact: k < 2^53
-    ue = np.where(u == 0.0, np.float64(5e-324), u)
-    ue = np.minimum(ue, last)
-    return np.searchsorted(cdf_row, ue, side="left").astype(np.int64) + 1
-
-
-def _probe_k53(cdf, rng):
-    """one below and one above every breakpoint, +- 2^21 around it, k = 0, 1, 2^53 - 1 and 3,000 random k"""
-    t53 = np.floor(np.minimum(cdf, 1.0 - 2.0 ** -53) * 2.0 ** 53).astype(np.int64)
-    return np.concatenate([np.array([0, 1, 2 ** 53 - 1, 2 ** 21, 2 ** 21 - 1])] +
-                          [np.clip(t53 + d, 0, 2 ** 53 - 1) for d in (-2 ** 21, -1, 0, 1, 2 ** 21)] +
-                          [rng.integers(0, 2 ** 53, size=3000)]).astype(np.uint64)
 
 
 def _row_cells(p_dest):
