@@ -21,6 +21,7 @@ SYMBOLS = [
     "cpm_debug_categorical", "cpm_createdatamatrix_rows", "cpm_createdatamatrix_csv", "cpm_get_datamatrix",
     "cpm_set_distance_from_centroids", "cpm_get_distance", "cpm_parse_uber_csv", "cpm_set_distance", "cpm_get_info",
     "cpm_init_states_strided", "cpm_synth_tables_skewed", "cpm_synth_datamatrix", "cpm_refresh_tables",
+    "cpm_debug_travel_draw", "cpm_debug_f64_kit",
 ]
 
 # every symbol include/cpm_batch.h declares (checked by tests/test_batch_host.py); kept apart: SYMBOLS is cpm.h's list
@@ -51,6 +52,8 @@ CPM_INFO_KERNEL, CPM_INFO_CAP_MULT, CPM_INFO_PARTS, CPM_INFO_FUSED, CPM_INFO_FUS
 # ... and what its most recent step ran
 CPM_INFO_LAST_KERNEL, CPM_INFO_LAST_FORM, CPM_INFO_STEPS_REPEATED = 7, 8, 9
 CPM_INFO_LAST_HOUR = 11  # 1: hour T of the most recent step ran the count-only kernel (10 stays unknown: tests/abi_harness.c)
+CPM_INFO_TRAVEL_TABLE = 12  # the travel table of the resident datamatrix: 0 none yet, 1 compact rows (dataset route), 2 sparse rows, 3 dense gather
+CPM_KIT_LOG, CPM_KIT_SQRT, CPM_KIT_ERF, CPM_KIT_PPND, CPM_KIT_EXP_NEG = 0, 1, 2, 3, 4  # cpm_debug_f64_kit's functions
 # include/cpm_batch.h: the installed batch tables' fleets, the fleets the batched kernels produced in the most recent batch step, and the
 # CPM_INFO_LAST_FORM of such a step
 CPM_MAX_BATCH = 64
@@ -133,6 +136,8 @@ def load():
     L.cpm_last_kernel_ms.argtypes = [vp, vp, i32, C.POINTER(i32)]
     L.cpm_algorithmic_bytes_per_hour.argtypes = [vp, C.POINTER(i64)]
     L.cpm_debug_categorical.argtypes = [vp, i64, i64, i64, vp, vp, C.POINTER(i32)]
+    L.cpm_debug_travel_draw.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.cpm_debug_f64_kit.argtypes = [vp, i32, i64, vp, vp]
     L.cpm_createdatamatrix_rows.argtypes = [vp, i64, vp]
     L.cpm_createdatamatrix_csv.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
     L.cpm_get_datamatrix.argtypes = [vp, vp]

@@ -28,6 +28,7 @@
 #include "cpm_dataset.h"
 #include "cpm_upload.h"
 #include "cpm_ingest.h"
+#include "cpm_kit_debug.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
 
@@ -1351,6 +1352,9 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
     case CPM_INFO_BATCH:
         *value_out = c->batch_B;
         return CPM_OK;
+    case CPM_INFO_TRAVEL_TABLE:  // what ensure_travel_tables left for the resident datamatrix
+        *value_out = !c->tt_valid ? 0 : c->tts_valid ? (c->tts_fixed ? 1 : 2) : 3;
+        return CPM_OK;
     case CPM_INFO_LAST_BATCH_FLEETS:
         if (c->ivp_pending) {
             HIP_TRY(hipSetDevice(c->device));
@@ -2317,6 +2321,56 @@ int32_t cpm_debug_categorical(cpm_ctx *c, int64_t origin1, int64_t hour1, int64_
     dfree(d_n);
     if (e != hipSuccess) return fail(CPM_ERR_HIP, "debug_categorical: %s", hipGetErrorString(e));
     if (n_exact_out) *n_exact_out = h_n;
+    return CPM_OK;
+}
+
+int32_t cpm_debug_travel_draw(cpm_ctx *c, int64_t n, const uint64_t *k53, const double *mean, const double *sd, double *draw_out,
+                              double *mass_out, int64_t *q16_out)
+{
+    CTX_TRY(c);
+    if (n < 0 || (n > 0 && (!k53 || !mean || !sd || !draw_out || !mass_out || !q16_out))) return fail(CPM_ERR_ARG, "debug_travel_draw: bad argument list");
+    if (n == 0) return CPM_OK;
+    const size_t bytes = sizeof(double) * static_cast<size_t>(n);  // (every array holds n 8-byte elements)
+    char *d = nullptr;                                              // k53 | mean | sd | draw | mass | q16
+    hipError_t e = hipMalloc(&d, 6 * bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, k53, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + bytes, mean, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * bytes, sd, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(cpm::k_debug_travel_draw, dim3(nblk(n, 256)), dim3(256), 0, c->stream, n, reinterpret_cast<const uint64_t *>(d),
+                           reinterpret_cast<const double *>(d + bytes), reinterpret_cast<const double *>(d + 2 * bytes),
+                           reinterpret_cast<double *>(d + 3 * bytes), reinterpret_cast<double *>(d + 4 * bytes),
+                           reinterpret_cast<long long *>(d + 5 * bytes));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(draw_out, d + 3 * bytes, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(mass_out, d + 4 * bytes, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(q16_out, d + 5 * bytes, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    dfree(d);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP, "debug_travel_draw: %s", hipGetErrorString(e));
+    return CPM_OK;
+}
+
+int32_t cpm_debug_f64_kit(cpm_ctx *c, int32_t fn, int64_t n, const double *x, double *out)
+{
+    CTX_TRY(c);
+    if (fn < CPM_KIT_LOG || fn > CPM_KIT_EXP_NEG) return fail(CPM_ERR_ARG, "debug_f64_kit: unknown function %d", fn);
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(CPM_ERR_ARG, "debug_f64_kit: bad argument list");
+    if (n == 0) return CPM_OK;
+    const size_t bytes = sizeof(double) * static_cast<size_t>(n);
+    char *d = nullptr;  // x | out
+    hipError_t e = hipMalloc(&d, 2 * bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, x, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(cpm::k_debug_f64_kit, dim3(nblk(n, 256)), dim3(256), 0, c->stream, static_cast<int>(fn), n,
+                           reinterpret_cast<const double *>(d), reinterpret_cast<double *>(d + bytes));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + bytes, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    dfree(d);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP, "debug_f64_kit: %s", hipGetErrorString(e));
     return CPM_OK;
 }
 

@@ -221,7 +221,9 @@ __device__ __noinline__ double ppnd_tail(double q)
     double r = 0.5 - aq;  // min(p, 1 - p)
     double val;
     if (!(r > 0.0)) {
-        val = 9.0;  // beyond every window the sampler clamps to
+        // r = 0 needs a mass of exactly 1.0 (sigma < ~mu / 85: a > 8.3) and u = 0: 2^-53 per draw.  9 sigma is beyond the window, and clamped
+        // to its edge, only while a <= 9; for sigma < mu / 90 the draw mu - 9 sigma lies INSIDE it.  Pinned as it is (tests/test_travel_kit.py)
+        val = 9.0;
     } else {
         r = det_sqrt(-det_log(r));
         if (r <= 5.0) {

@@ -96,7 +96,9 @@ class Sampler:
         3 placing first, 6 all hours in one launch), 5 = steps that bailed out of a one-launch form, 6 = words of a sparse row pack (0:
         dense tables; > 0 after build_p_dest on a sparse datamatrix or after set_p_dest under set_sparse_upload on a table that qualifies).  What its most recent step ran: 7 = the kernel family that produced its results (0 before any step), 8 = the
         form its grouped hours took (coded as 4; -1 when the family is not the grouped one), 9 = step attempts the library discarded
-        and ran again so far, 11 = 1 when its hour T ran the count-only kernel (set_last_hour)."""
+        and ran again so far, 11 = 1 when its hour T ran the count-only kernel (set_last_hour).  12 = the travel table the grouped path's
+        travel kernel reads for the resident datamatrix (0 none built yet, 1 the dataset route's compact rows, 2 sparse rows, 3 the
+        dense table it gathers from)."""
         v = C.c_int64(0)
         _lib.check(self._L.cpm_get_info(self._h, int(what), C.byref(v)))
         return int(v.value)
@@ -454,6 +456,29 @@ class Sampler:
         _lib.check(self._L.cpm_debug_categorical(self._h, int(origin), int(hour), int(k.shape[0]), _vp(k), _vp(out),
                                                  C.byref(n_exact)))
         return out, int(n_exact.value)
+
+    def debug_travel_draw(self, k53, mean, sd):
+        """Diagnostic: the travel kernels' truncated-normal draw, element by element, for cells (mean, sd) and the 53-bit uniforms k53
+        (u = k * 2^-53): (draw float64, mass of the window float64, draw in 2^-16 s int64).  sd == 0 is a tenth of the mean, as in the
+        kernels.  Needs no tables, datamatrix or cars."""
+        k = np.ascontiguousarray(k53, dtype=np.uint64).reshape(-1)
+        m = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        s = np.ascontiguousarray(sd, dtype=np.float64).reshape(-1)
+        if not k.shape == m.shape == s.shape:
+            raise ValueError(f"k53 {k.shape}, mean {m.shape} and sd {s.shape} must have one length")
+        draw, mass, q = np.zeros(k.shape[0]), np.zeros(k.shape[0]), np.zeros(k.shape[0], dtype=np.int64)
+        _lib.check(self._L.cpm_debug_travel_draw(self._h, int(k.shape[0]), _vp(k), _vp(m), _vp(s), _vp(draw), _vp(mass), _vp(q)))
+        return draw, mass, q
+
+    def debug_f64_kit(self, fn, x):
+        """Diagnostic: fn(x) element by element through the sampler's deterministic f64 functions as the kernels are compiled; fn =
+        _lib.CPM_KIT_LOG / _SQRT / _ERF / _PPND / _EXP_NEG, or its name ("log", "sqrt", "erf", "ppnd", "exp_neg")."""
+        if isinstance(fn, str):
+            fn = getattr(_lib, "CPM_KIT_" + fn.upper())
+        a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        out = np.zeros(a.shape[0])
+        _lib.check(self._L.cpm_debug_f64_kit(self._h, int(fn), int(a.shape[0]), _vp(a), _vp(out)))
+        return out
 
     def algorithmic_bytes_per_hour(self):
         b = C.c_int64(0)

@@ -148,6 +148,11 @@ int32_t cpm_set_option(cpm_ctx *ctx, int32_t option, int64_t value);
 #define CPM_INFO_LAST_HOUR 11      /* 1 when hour T of the most recent step ran the count-only kernel (CPM_OPT_LAST_HOUR), from what was launched;
                                     * 0 otherwise: the plain or a run-producing form, another kernel family, an IVP.  (Key 10, the one behind
                                     * CPM_INFO_STEPS_REPEATED, stays an argument error: tests/abi_harness.c asks for exactly that) */
+#define CPM_INFO_TRAVEL_TABLE 12   /* the travel table the grouped path's travel kernel reads for the resident datamatrix: 0 none built yet (no
+                                    * travel resample on the grouped path and no cpm_build_p_dest on the compact rows since the datamatrix
+                                    * came), 1 the travel rows of the dataset route's compact rows (csrc/cpm_dataset.h: fixed stride), 2 sparse
+                                    * rows built from the datamatrix itself (a row's cells fit 32 KB of LDS), 3 the dense table the kernel
+                                    * gathers from.  The travel times do not depend on it */
 int32_t cpm_get_info(cpm_ctx *ctx, int32_t what, int64_t *value_out);
 /* run on a caller-owned hipStream_t (e.g. torch's current stream); NULL = ctx's own, which is created when a call first needs it.
  * Contexts meant to run side by side (two resamples interleave on the chip) are each given their stream right behind
@@ -275,6 +280,21 @@ int32_t cpm_algorithmic_bytes_per_hour(cpm_ctx *ctx, int64_t *bytes_out);
  * *n_exact_out = how many draws took the exact (f64 row) fallback. */
 int32_t cpm_debug_categorical(cpm_ctx *ctx, int64_t origin1, int64_t hour1, int64_t n, const uint64_t *k53,
                               int64_t *dest_out, int32_t *n_exact_out_or_null);
+/* diagnostic: the travel-time draw (src/resampling.jl:62-69) of the travel kernels for given cells and 53-bit uniforms, element by
+ * element, through the kernels' own inline functions: sigma = sd[i], or a tenth of mean[i] where sd[i] == 0 (:65-67); mass_out[i] =
+ * the mass of N(mean, sigma) inside [0.9 mean, 1.1 mean]; draw_out[i] = the truncated-normal draw for u = k53[i] * 2^-53;
+ * q16_out[i] = that draw in the 2^-16 s units sum_travel_time_q16 adds up.  Reaches what no resample draws: u = 0, |u - 1/2| within
+ * 1e-11 of 1/2, the clamps to the window.  Needs a context only: no tables, no datamatrix, no cars. */
+int32_t cpm_debug_travel_draw(cpm_ctx *ctx, int64_t n, const uint64_t *k53, const double *mean, const double *sd,
+                              double *draw_out, double *mass_out, int64_t *q16_out);
+/* diagnostic: out[i] = fn(x[i]) by one of the sampler's deterministic f64 functions (csrc/cpm_rng.h), compiled with the kernels:
+ * ln and sqrt (x > 0 normal), erf (0 for x < 0 and NaN), Phi^-1(1/2 + x) (|x| <= 1/2), exp(-x) (x >= 0) */
+#define CPM_KIT_LOG 0
+#define CPM_KIT_SQRT 1
+#define CPM_KIT_ERF 2
+#define CPM_KIT_PPND 3
+#define CPM_KIT_EXP_NEG 4
+int32_t cpm_debug_f64_kit(cpm_ctx *ctx, int32_t fn, int64_t n, const double *x, double *out);
 
 #ifdef __cplusplus
 }
