@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include "../../include/cpm_flows_csr.h"
 #include "../../include/cpm_stays.h"
 #include "../../include/cpm_paths.h"
+#include "../../include/cpm_objectives.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -29,6 +31,7 @@
 #include "cpm_upload.h"
 #include "cpm_ingest.h"
 #include "cpm_kit_debug.h"
+#include "cpm_objectives.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
 
@@ -201,6 +204,13 @@ struct cpm_ctx {
     unsigned long long *h_bstatus = nullptr;
     hipEvent_t bstatus_ev = nullptr;
     bool bstatus_pending = false;
+    // the sweep's objectives (include/cpm_objectives.h, cpm_objectives.h)
+    double *d_measured = nullptr;       // [T][Z] measured parking densities, and per zone whether its row sums to != 0
+    int *d_meas_flag = nullptr;         // [Z]
+    bool have_measured = false;
+    double *d_obj_part = nullptr;       // [obj_ws_B][ceil(Z/256)] the workgroups' partial sums of the zone errors ...
+    int *d_obj_part_n = nullptr;        // ... and their counts of valid zones
+    int obj_ws_B = 0;
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -1216,6 +1226,10 @@ int32_t cpm_destroy(cpm_ctx *c)
     if (c->h_bstatus) (void)hipHostFree(c->h_bstatus);
     if (c->bstatus_ev) (void)hipEventDestroy(c->bstatus_ev);
     c->zb.release();
+    dfree(c->d_measured);
+    dfree(c->d_meas_flag);
+    dfree(c->d_obj_part);
+    dfree(c->d_obj_part_n);
     dfree(c->d_ds_cells);
     dfree(c->d_ds_cnt);
     dfree(c->d_sp);
@@ -2371,6 +2385,62 @@ int32_t cpm_debug_f64_kit(cpm_ctx *c, int32_t fn, int64_t n, const double *x, do
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     dfree(d);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP, "debug_f64_kit: %s", hipGetErrorString(e));
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ the sweep's objectives (include/cpm_objectives.h)
+
+int32_t cpm_set_measured(cpm_ctx *c, const double *measured)
+{
+    CTX_TRY(c);
+    if (!measured) {  // (host state only: what is in flight on the stream was enqueued with the data it had)
+        c->have_measured = false;
+        return CPM_OK;
+    }
+    const size_t cells = static_cast<size_t>(c->Z) * static_cast<size_t>(c->T);
+    for (size_t i = 0; i < cells; ++i)
+        if (!std::isfinite(measured[i]))
+            return fail(CPM_ERR_ARG, "set_measured: entry (zone %lld, hour %lld) is not finite", (long long)(i % c->Z) + 1, (long long)(i / c->Z) + 1);
+    if (!c->d_measured) HIP_TRY(hipMalloc(&c->d_measured, sizeof(double) * cells));
+    if (!c->d_meas_flag) HIP_TRY(hipMalloc(&c->d_meas_flag, sizeof(int) * static_cast<size_t>(c->Z)));
+    // (Z x T column-major IS [T][Z]: the layout the kernels read, Z contiguous like the count tensor)
+    HIP_TRY(hipMemcpyAsync(c->d_measured, measured, sizeof(double) * cells, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(cpm::k_measured_flag, dim3(nblk(c->Z, cpm::kObjBlock)), dim3(cpm::kObjBlock), 0, c->stream, c->d_measured, c->d_meas_flag,
+                       static_cast<int>(c->Z), static_cast<int>(c->T));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->have_measured = true;
+    return CPM_OK;
+}
+
+int32_t cpm_objectives_dev(cpm_ctx *c, const void *d_counts, int32_t B, int64_t n_cars, void *d_obj, void *d_zone_err)
+{
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!d_counts) return fail(CPM_ERR_ARG, "objectives: null d_counts");
+    if (!d_obj) return fail(CPM_ERR_ARG, "objectives: null d_obj");
+    if (B < 1 || B > CPM_MAX_BATCH) return fail(CPM_ERR_ARG, "objectives: B = %d outside 1..%d", B, CPM_MAX_BATCH);
+    if (n_cars < 1) return fail(CPM_ERR_ARG, "objectives: n_cars = %lld", (long long)n_cars);
+    CTX_TRY(c);
+    const unsigned nb = nblk(c->Z, cpm::kObjBlock);
+    if (c->obj_ws_B < B) {  // (hipFree waits for what still reads the old workspace)
+        dfree(c->d_obj_part);
+        dfree(c->d_obj_part_n);
+        c->obj_ws_B = 0;
+        HIP_TRY(hipMalloc(&c->d_obj_part, sizeof(double) * nb * static_cast<size_t>(B)));
+        HIP_TRY(hipMalloc(&c->d_obj_part_n, sizeof(int) * nb * static_cast<size_t>(B)));
+        c->obj_ws_B = B;
+    }
+    const int T = static_cast<int>(c->T);
+    unsigned long long *obj = static_cast<unsigned long long *>(d_obj);
+    // the hour sums are accumulated with atomics: the records start from zero
+    HIP_TRY(hipMemsetAsync(obj, 0, sizeof(unsigned long long) * static_cast<size_t>(B) * static_cast<size_t>(cpm::kObjHead + 2 * T), c->stream));
+    hipLaunchKernelGGL(cpm::k_obj_zones, dim3(nb, static_cast<unsigned>(B)), dim3(cpm::kObjBlock), 0, c->stream, static_cast<const long long *>(d_counts),
+                       c->have_measured ? c->d_measured : nullptr, c->have_measured ? c->d_meas_flag : nullptr, static_cast<long long>(n_cars),
+                       static_cast<int>(c->Z), T, obj, static_cast<double *>(d_zone_err), c->d_obj_part, c->d_obj_part_n);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cpm::k_obj_final, dim3(static_cast<unsigned>(B)), dim3(64), 0, c->stream, static_cast<const long long *>(d_counts), c->d_obj_part,
+                       c->d_obj_part_n, static_cast<int>(nb), static_cast<int>(c->Z), T, obj);
+    HIP_TRY(hipGetLastError());
     return CPM_OK;
 }
 

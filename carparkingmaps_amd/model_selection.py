@@ -66,6 +66,52 @@ def parking_density_error(parking, C, measured):
     return float(err.sum() / err.size)
 
 
+def parking_density_zone_errors(parking, C, measured):
+    """The definition of include/cpm_objectives.h on the host, one IEEE f64 operation per step and in its order: (err (Z,) float64
+    with -1.0 for a zone that is not valid, valid (Z,) bool).  A zone is valid when its measured row, added in hour order, is != 0 and
+    its counts are not flat; measured None: no zone is.  The hours are accumulated row by row (acc = acc + d*d), not with
+    .sum(axis=...): numpy's order of a reduction depends on the array's shape, and the device's zone errors are compared bit for bit."""
+    c = np.asarray(parking, dtype=np.int64)
+    Z, T = c.shape
+    n = float(C)
+    cmin, cmax = c.min(axis=1), c.max(axis=1)
+    if measured is None:
+        return np.full(Z, -1.0), np.zeros(Z, dtype=bool)
+    m = np.asarray(measured, dtype=np.float64)
+    msum = np.zeros(Z)
+    for t in range(T):
+        msum = msum + m[:, t]
+    valid = (msum != 0) & (cmin != cmax)
+    with np.errstate(all="ignore"):
+        lo, hi = cmin.astype(np.float64) / n, cmax.astype(np.float64) / n
+        rng = hi - lo
+        acc = np.zeros(Z)
+        for t in range(T):
+            p = c[:, t].astype(np.float64) / n
+            d = (p - lo) / rng - m[:, t]
+            acc = acc + d * d
+        err = acc / float(T)
+    return np.where(valid, err, -1.0), valid
+
+
+def objectives_from_record(rec, pt, C, T, measured_activity=None, with_parking_error=True):
+    """The result dict of Evaluator._objectives from one device record (include/cpm_objectives.h: int64[4 + 2*T]), without the count
+    arrays: the traffic activity from the driving sums through traffic_activity (a (1, T) array has the same column sums, so it is
+    bit-equal to the host path), A_drive from word 1, parking_error from the bits in word 3, and the two figures grid_sweep
+    otherwise takes from the arrays: driving_total and hours_hold_all_cars (every hour's parking sum == C)."""
+    rec = np.ascontiguousarray(rec, dtype=np.int64)
+    driving_sum, parking_sum = rec[4:4 + T], rec[4 + T:4 + 2 * T]
+    act = traffic_activity(driving_sum.reshape(1, T))
+    out = {"e_drive": pt.e_drive, "p_min": pt.p_min, "p_max": pt.p_max, "e_dest": float(pt.e_dest),
+           "A_drive": a_drive(int(rec[1]), C, T), "traffic_activity": act,
+           "driving_total": int(driving_sum.sum()), "hours_hold_all_cars": bool((parking_sum == C).all())}
+    if measured_activity is not None:
+        out["activity_error"] = traffic_activity_error(act, measured_activity)
+    if with_parking_error:
+        out["parking_error"] = float(rec[3:4].view(np.float64)[0])
+    return out
+
+
 # ------------------------------------------------------------------ one evaluation
 @dataclass
 class Point:
@@ -85,12 +131,15 @@ class Evaluator:
     measured_parking: object = None
     travel: bool = True
     fallbacks: int = 0      # pipelined points whose asynchronous step overflowed a bucket region and were evaluated again, blocking
+    device_objectives: bool = False   # reduce the counts on the device (include/cpm_objectives.h): the host reads 4 + 2*T words per point
     _e_dest: object = field(default=None, repr=False)
     _pipe: object = field(default=None, repr=False)
 
     def __post_init__(self):
         if self.measured_parking is not None:   # Julia order, like the count tensors: the error is evaluated hour-major on contiguous rows
             self.measured_parking = np.asfortranarray(np.asarray(self.measured_parking, dtype=np.float64))
+        if self.device_objectives:
+            self.sampler.set_measured(self.measured_parking)    # once: resident in the context (None: forgets what it held)
 
     def _install(self, pt):
         self.sampler.build_p_drive(pt.p_min, pt.p_max, pt.e_drive, want=False)   # (Z x T work: the Z x Z x T mean is cached by the library)
@@ -117,7 +166,43 @@ class Evaluator:
         """One point, blocking."""
         self._install(pt)
         r = self.sampler.resample(self.seed, travel=self.travel)
+        if self.device_objectives:
+            return self._from_record(pt, self._record_of_host_counts(r["parking"], r["driving"], r["sum_tt_q16"]))
         return self._objectives(pt, r["parking"], r["driving"], r["sum_tt_q16"])
+
+    # -- device objectives: the record of include/cpm_objectives.h in the place of the count tensor --
+    def _from_record(self, pt, rec):
+        return objectives_from_record(rec, pt, self.C, self.sampler.T, self.measured_activity, self.measured_parking is not None)
+
+    def _record_of_host_counts(self, parking, driving, sum_tt_q16):
+        """The counts of a blocking resample, uploaded and reduced by objectives_dev like every other point's: one definition of
+        parking_error for the whole sweep.  Blocking; tensors of its own (the pipeline's slots may be in flight)."""
+        import torch
+        s = self.sampler
+        zt = s.Z * s.T
+        flat = np.zeros(s.counts_words(), dtype=np.int64)
+        flat[:zt] = np.asarray(parking).ravel(order="F")          # Julia order (Z, T) read column by column IS [T][Z]
+        flat[zt:2 * zt] = np.asarray(driving).ravel(order="F")
+        flat[2 * zt] = int(sum_tt_q16)
+        stream = self._pipe_stream()
+        with torch.cuda.stream(stream):
+            dev = torch.from_numpy(flat).to(f"cuda:{s.device}")
+            obj = torch.zeros(s.objective_words(), dtype=torch.int64, device=f"cuda:{s.device}")
+            s.objectives_dev(dev.data_ptr(), 1, self.C, obj.data_ptr())
+            rec = obj.cpu().numpy()
+        return rec
+
+    def _obj_slot(self, slot, fleets):
+        """Slot `slot`'s records of at least `fleets` fleets, device and pinned host (grown like the count tensors in _slot)."""
+        import torch
+        p, n = self._pipe, self.sampler.objective_words() * fleets
+        if "obj_dev" not in p:
+            p["obj_dev"], p["obj_host"] = [None, None], [None, None]
+        if p["obj_dev"][slot] is None or p["obj_dev"][slot].numel() < n:
+            p["done"][slot].synchronize()
+            p["obj_dev"][slot] = torch.zeros(n, dtype=torch.int64, device=f"cuda:{self.sampler.device}")
+            p["obj_host"][slot] = torch.zeros(n, dtype=torch.int64).pin_memory()
+        return n
 
     # -- pipelined form: point k+1 runs on the GPU while the host reduces point k (two count tensors, pinned host twins) --
     def _slot(self, slot, n):
@@ -126,11 +211,7 @@ class Evaluator:
         -- its tensors and its event stay as they are."""
         import torch
         s = self.sampler
-        if self._pipe is None:
-            if s._stream is None:     # (a Sampler that was given its stream at construction keeps it; see Sampler.__init__)
-                s.set_stream(torch.cuda.Stream(device=s.device))
-            stream = s._stream_obj if hasattr(s._stream_obj, "cuda_stream") else torch.cuda.ExternalStream(s._stream, device=s.device)
-            self._pipe = dict(stream=stream, dev=[None, None], host=[None, None], done=[torch.cuda.Event() for _ in range(2)])
+        self._pipe_stream()
         p = self._pipe
         if p["dev"][slot] is None or p["dev"][slot].numel() < n:
             p["done"][slot].synchronize()  # (a slot's event has recorded nothing yet, or a step that has been reduced)
@@ -138,16 +219,32 @@ class Evaluator:
             p["host"][slot] = torch.zeros(n, dtype=torch.int64).pin_memory()
         return p
 
+    def _pipe_stream(self):
+        """The pipeline's stream (the context's own as a torch stream); the pipeline's bookkeeping is created with it."""
+        import torch
+        s = self.sampler
+        if self._pipe is None:
+            if s._stream is None:     # (a Sampler that was given its stream at construction keeps it; see Sampler.__init__)
+                s.set_stream(torch.cuda.Stream(device=s.device))
+            stream = s._stream_obj if hasattr(s._stream_obj, "cuda_stream") else torch.cuda.ExternalStream(s._stream, device=s.device)
+            self._pipe = dict(stream=stream, dev=[None, None], host=[None, None], done=[torch.cuda.Event() for _ in range(2)])
+        return self._pipe["stream"]
+
     def begin(self, pt, slot):
         """Enqueue the table update, the resample and the copy of its counts to the host for `pt`; returns at once."""
         import torch
         s = self.sampler
         n = s.counts_words()
         p = self._slot(slot, n)
+        w = self._obj_slot(slot, 1) if self.device_objectives else 0
         self._install(pt)
         with torch.cuda.stream(p["stream"]):
             s.resample_dev(self.seed, p["dev"][slot].data_ptr(), travel=self.travel)
-            p["host"][slot][:n].copy_(p["dev"][slot][:n], non_blocking=True)
+            if self.device_objectives:    # behind the resample on the same stream; only the record crosses to the host
+                s.objectives_dev(p["dev"][slot].data_ptr(), 1, self.C, p["obj_dev"][slot].data_ptr())
+                p["obj_host"][slot][:w].copy_(p["obj_dev"][slot][:w], non_blocking=True)
+            else:
+                p["host"][slot][:n].copy_(p["dev"][slot][:n], non_blocking=True)
             p["done"][slot].record(p["stream"])
 
     def finish(self, pt, slot):
@@ -155,6 +252,14 @@ class Evaluator:
         asynchronous form cannot repeat itself) is evaluated again through the blocking call, which grows the regions."""
         p = self._pipe
         p["done"][slot].synchronize()
+        if self.device_objectives:
+            rec = p["obj_host"][slot].numpy()[:self.sampler.objective_words()].copy()   # (the pinned twin is reused two points later)
+            if rec[0] != 0:               # (as below: the blocking call, whose counts go through objectives_dev as well)
+                self.fallbacks += 1
+                out = self.evaluate(pt)
+                out["fallback"] = True
+                return out
+            return self._from_record(pt, rec)
         flat = p["host"][slot].numpy()
         Z, T = self.sampler.Z, self.sampler.T
         zt = Z * T
@@ -178,11 +283,16 @@ class Evaluator:
         s = self.sampler
         n = s.counts_words() * len(pts)
         p = self._slot(slot, n)        # (sized per slot: a lane's batches need not grow monotonically, nor be of one size)
+        w = self._obj_slot(slot, len(pts)) if self.device_objectives else 0
         self._install_dest(pts[0].e_dest)
         s.build_p_drive_batch([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts])
         with torch.cuda.stream(p["stream"]):
             s.resample_batch_dev(self.seed, p["dev"][slot].data_ptr(), travel=self.travel)
-            p["host"][slot][:n].copy_(p["dev"][slot][:n], non_blocking=True)
+            if self.device_objectives:
+                s.objectives_dev(p["dev"][slot].data_ptr(), len(pts), self.C, p["obj_dev"][slot].data_ptr())
+                p["obj_host"][slot][:w].copy_(p["obj_dev"][slot][:w], non_blocking=True)
+            else:
+                p["host"][slot][:n].copy_(p["dev"][slot][:n], non_blocking=True)
             p["done"][slot].record(p["stream"])
 
     def finish_batch(self, pts, slot):
@@ -190,6 +300,19 @@ class Evaluator:
         through the blocking call (and counted in `fallbacks`), as in finish()."""
         p = self._pipe
         p["done"][slot].synchronize()
+        if self.device_objectives:
+            ow = self.sampler.objective_words()
+            recs = p["obj_host"][slot].numpy()[:ow * len(pts)].reshape(len(pts), ow).copy()   # (the pinned twin is reused two batches later)
+            outs = []
+            for b, pt in enumerate(pts):
+                if recs[b, 0] != 0:
+                    self.fallbacks += 1
+                    out = self.evaluate(pt)
+                    out["fallback"] = True
+                else:
+                    out = self._from_record(pt, recs[b])
+                outs.append(out)
+            return outs
         Z, T = self.sampler.Z, self.sampler.T
         zt, nw = Z * T, self.sampler.counts_words()
         flat = p["host"][slot].numpy()[:nw * len(pts)].reshape(len(pts), nw)
@@ -313,9 +436,14 @@ def grid_sweep(evaluator, grid, rank=0, world_size=1, gather=True, checksums=Fal
     against 2 x 0.92 one after the other, profiles/round2_notes.md) -- the hours of ONE resample cannot.
 
     batch=B: each lane's slice is cut into batches of at most B consecutive points that share e_dest (batch_cuts); a batch is ONE
-    batched resample of B fleets (Evaluator.begin_batch / finish_batch, pipelined like begin / finish).  Same results, point for point."""
+    batched resample of B fleets (Evaluator.begin_batch / finish_batch, pipelined like begin / finish).  Same results, point for point.
+
+    An Evaluator with device_objectives=True returns dicts without count arrays: driving_total and hours_hold_all_cars then come from
+    its records, and checksums=True (which needs the tensors) raises ValueError."""
     lanes = list(evaluator) if isinstance(evaluator, (list, tuple)) else [evaluator]
     C = lanes[0].C
+    if checksums and any(getattr(ev, "device_objectives", False) for ev in lanes):
+        raise ValueError("checksums=True needs the count tensors on the host: not together with Evaluator(device_objectives=True)")
     by_e_dest = sorted(range(len(grid)), key=lambda i: (float(grid[i].e_dest), type(grid[i].e_dest).__name__, i))
     mine = points_of_rank(len(grid), rank, world_size, by_e_dest)
     local = {}
@@ -361,8 +489,12 @@ def grid_sweep(evaluator, grid, rank=0, world_size=1, gather=True, checksums=Fal
     for i, r in (results() if batch is None else results_batched()):
         local[i] = {k: v for k, v in r.items() if np.isscalar(v)}
         local[i]["fallback"] = bool(r.get("fallback", False))   # evaluated twice: its asynchronous step had overflowed
-        local[i]["driving_total"] = int(r["driving"].sum())
-        local[i]["hours_hold_all_cars"] = bool((r["parking"].sum(axis=0) == C).all())
+        if "driving" in r:
+            local[i]["driving_total"] = int(r["driving"].sum())
+            local[i]["hours_hold_all_cars"] = bool((r["parking"].sum(axis=0) == C).all())
+        else:  # (device objectives: the record's sums, no arrays)
+            local[i]["driving_total"] = int(r["driving_total"])
+            local[i]["hours_hold_all_cars"] = bool(r["hours_hold_all_cars"])
         if checksums:
             local[i]["parking_crc32"] = zlib.crc32(np.ascontiguousarray(r["parking"].ravel(order="F")).tobytes())
             local[i]["driving_crc32"] = zlib.crc32(np.ascontiguousarray(r["driving"].ravel(order="F")).tobytes())

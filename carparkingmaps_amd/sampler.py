@@ -441,6 +441,29 @@ class Sampler:
         """int64 words of resample_batch_dev's tensor: B x counts_words()."""
         return self.get_info(_lib.CPM_INFO_BATCH) * self.counts_words()
 
+    # -- the sweep's objectives on the device (include/cpm_objectives.h) --
+    def set_measured(self, parking_density_measured):
+        """The measured parking densities, (Z, T), resident until replaced; None: forget them.  NaN or infinite entries raise."""
+        if parking_density_measured is None:
+            _lib.check(self._L.cpm_set_measured(self._h, None))
+            return
+        a = _f64(parking_density_measured, (self.Z, self.T))
+        _lib.check(self._L.cpm_set_measured(self._h, _vp(a)))
+
+    def objective_words(self):
+        """int64 words of one fleet's record: 4 + 2*T (status, sum_tt_q16, n_valid, bits of the f64 parking_error, driving_sum[T],
+        parking_sum[T])."""
+        return 4 + 2 * self.T
+
+    def objectives_dev(self, d_counts_ptr, B, n_cars, d_obj_ptr, d_zone_err_ptr=0):
+        """Enqueue on the context's stream: the records of B count tensors (d_counts_ptr = device address of int64[B][2*T*Z+2], as
+        resample_dev / resample_batch_dev fill it) into d_obj_ptr = device address of int64[B][objective_words()]; d_zone_err_ptr =
+        device address of float64[B][Z] (the zones' errors, -1.0 where a zone is not valid) or 0.  n_cars: the cars whose counts a
+        tensor holds (the fleet's behind an all-reduce).  No synchronisation."""
+        _lib.check(self._L.cpm_objectives_dev(self._h, C.c_void_p(int(d_counts_ptr)) if d_counts_ptr else None, int(B), int(n_cars),
+                                              C.c_void_p(int(d_obj_ptr)) if d_obj_ptr else None,
+                                              C.c_void_p(int(d_zone_err_ptr)) if d_zone_err_ptr else None))
+
     def last_kernel_ms(self):
         buf = (C.c_float * 8192)()
         n = C.c_int32(0)
