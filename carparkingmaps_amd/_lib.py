@@ -62,6 +62,12 @@ CPM_KIT_LOG, CPM_KIT_SQRT, CPM_KIT_ERF, CPM_KIT_PPND, CPM_KIT_EXP_NEG = 0, 1, 2,
 CPM_MAX_BATCH = 64
 CPM_INFO_BATCH, CPM_INFO_LAST_BATCH_FLEETS = 16, 17
 CPM_FORM_BATCH = 10
+# include/cpm.h: which instantiation the most recent step launched, one word per role (0: no such launch), written by the innermost
+# launch helper from its template parameters: kind | CPT << 8 | NQ << 16 | flags << 24 (placing kinds: kind | KRUNS << 8 | PB / 64 << 16)
+CPM_INFO_CELL_APPLIED, CPM_INFO_CELL_HEAVY, CPM_INFO_CELL_LAST, CPM_INFO_CELL_PLACE, CPM_INFO_CELL_BATCH = 20, 21, 22, 23, 24
+CPM_CELL_SAMPLE, CPM_CELL_HOUR, CPM_CELL_HOUR_PF, CPM_CELL_DAY, CPM_CELL_HEAVY, CPM_CELL_COUNT, CPM_CELL_PLACE = 1, 2, 3, 4, 5, 6, 7
+CPM_CELL_BATCH_SAMPLE, CPM_CELL_BATCH_PLACE, CPM_CELL_BATCH_COUNT = 8, 9, 10
+CPM_CELL_FLAG_GROUPED, CPM_CELL_FLAG_SPARSE, CPM_CELL_FLAG_PERM = 1, 2, 4
 
 _lib = None
 

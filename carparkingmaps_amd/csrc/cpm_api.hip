@@ -182,6 +182,7 @@ struct cpm_ctx {
     bool ivp_pending = false;
     uint64_t ivp_seed = 0;
     int ivp_form = -1;                  // the hour form of the pending IVP attempt (GroupedWork::last_form behind its grouped_run)
+    cpm::LaunchCells ivp_cells;         // ... and what its launch helpers launched (GroupedWork::last_cells), likewise
     long long *h_ivp_status = nullptr;  // pinned [2], likewise
     // what produced the results of the most recent step (CPM_INFO_LAST_KERNEL / _LAST_FORM), and the step attempts the library ran,
     // discarded and ran again so far (CPM_INFO_STEPS_REPEATED)
@@ -190,6 +191,7 @@ struct cpm_ctx {
     int64_t steps_repeated = 0;
     int last_batch_fleets = 0;          // CPM_INFO_LAST_BATCH_FLEETS: 0 after every step that is not a batch step
     int last_hour = 0;                  // CPM_INFO_LAST_HOUR: 1 when hour T of the most recent step was a count-only launch (cpm_count.h)
+    cpm::LaunchCells last_cells;        // CPM_INFO_CELL_*: the instantiations the most recent step launched, per role (all 0: none of these launchers ran)
     // batch tables and workspace (include/cpm_batch.h, cpm_batch.h)
     int batch_B = 0, batch_alloc = 0;
     double *d_pdrive_b = nullptr;       // [B][T][Z] the fleets' p_drive tables
@@ -789,6 +791,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     c->last_kernel = kernel;  // (the family this call enqueues; the grouped path's form is recorded behind its run)
     c->last_batch_fleets = 0;
     c->last_hour = 0;
+    c->last_cells = cpm::LaunchCells{};
     c->last_form = kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
     if (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED)  // (the grouped path zeroes the count tensor with its other counters, in one launch)
         HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * nwords, c->stream));
@@ -836,6 +839,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         rc = parked_pass(rc);
         if (rc == CPM_OK) c->last_form = c->zg.last_form;
         if (rc == CPM_OK) c->last_hour = c->zg.last_hour_counted;
+        if (rc == CPM_OK) c->last_cells = c->zg.last_cells;
         if (rc == CPM_OK && c->h_status && !c->status_pending) {
             c->h_status[1] = 0;
             if (hipMemcpyAsync(c->h_status, d_counts + nwords - 1, sizeof(long long), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
@@ -885,6 +889,7 @@ int32_t ivp_exact(cpm_ctx *c, uint64_t seed)
     c->last_kernel = exact ? CPM_KERNEL_ZONE_LDS : CPM_KERNEL_CAR;
     c->last_batch_fleets = 0;
     c->last_hour = 0;
+    c->last_cells = cpm::LaunchCells{};
     c->last_form = -1;
     if (exact) {
         return cpm::exact_run(c->zx, c->stream, c->d_pdrive, c->d_cdf, static_cast<int>(c->Z), c->Zp, static_cast<int>(c->T), c->n, c->cars,
@@ -908,6 +913,7 @@ int32_t ivp_grouped(cpm_ctx *c, uint64_t seed)
                                   [](int) {}, [](int) {}, g_last_error, true, c->d_ztmp);
     if (rc != CPM_OK) return rc;
     c->ivp_form = c->zg.last_form;
+    c->ivp_cells = c->zg.last_cells;
     c->h_ivp_status[1] = 0;
     HIP_TRY(hipMemcpyAsync(c->h_ivp_status, c->d_counts + 2 * c->T * c->Z + 1, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(c->h_ivp_status + 1, c->zg.maxn, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -928,6 +934,7 @@ int32_t finish_ivp(cpm_ctx *c)
         c->last_form = c->ivp_form;
         c->last_batch_fleets = 0;
         c->last_hour = 0;
+        c->last_cells = c->ivp_cells;
         HIP_TRY(cpm::grouped_commit_ivp(c->zg, c->stream));
         return CPM_OK;
     };
@@ -962,6 +969,7 @@ int32_t ivp_enqueue(cpm_ctx *c, uint64_t seed)
         c->last_form = c->last_kernel == CPM_KERNEL_ZONE_GROUPED ? 0 : -1;
         c->last_batch_fleets = 0;
         c->last_hour = 0;
+        c->last_cells = cpm::LaunchCells{};
         return CPM_OK;
     }
     if (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && grouped_fits(c, c->zg.cap_mult)) {
@@ -1370,12 +1378,22 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
         *value_out = !c->tt_valid ? 0 : c->tts_valid ? (c->tts_fixed ? 1 : 2) : 3;
         return CPM_OK;
     case CPM_INFO_LAST_BATCH_FLEETS:
+    case CPM_INFO_CELL_APPLIED:
+    case CPM_INFO_CELL_HEAVY:
+    case CPM_INFO_CELL_LAST:
+    case CPM_INFO_CELL_PLACE:
+    case CPM_INFO_CELL_BATCH:
         if (c->ivp_pending) {
             HIP_TRY(hipSetDevice(c->device));
             int32_t rc_ivp = finish_ivp(c);
             if (rc_ivp != CPM_OK) return rc_ivp;
         }
-        *value_out = c->last_batch_fleets;
+        *value_out = what == CPM_INFO_LAST_BATCH_FLEETS ? c->last_batch_fleets
+                     : what == CPM_INFO_CELL_APPLIED    ? c->last_cells.applied
+                     : what == CPM_INFO_CELL_HEAVY      ? c->last_cells.heavy
+                     : what == CPM_INFO_CELL_LAST       ? c->last_cells.last
+                     : what == CPM_INFO_CELL_PLACE      ? c->last_cells.place
+                                                        : c->last_cells.batch;
         return CPM_OK;
     default:
         return fail(CPM_ERR_ARG, "unknown info %d", what);
@@ -2570,6 +2588,8 @@ int32_t cpm_resample_batch(cpm_ctx *c, const uint64_t *seeds, uint32_t flags, in
         c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
         c->last_form = CPM_FORM_BATCH;
         c->last_hour = c->zb.last_hour_counted;
+    c->last_cells = c->zb.last_cells;
+        c->last_cells = c->zb.last_cells;
     }
     return CPM_OK;
 }
@@ -2612,6 +2632,7 @@ int32_t cpm_resample_batch_dev(cpm_ctx *c, const uint64_t *seeds, uint32_t flags
     c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
     c->last_form = CPM_FORM_BATCH;
     c->last_hour = c->zb.last_hour_counted;
+    c->last_cells = c->zb.last_cells;
     return CPM_OK;
 }
 

@@ -161,6 +161,7 @@ struct BatchWork {
     bool buckets0_valid = false;  // ids0 / cnt0 describe the context's current car state
     bool count_only = true;       // CPM_OPT_LAST_HOUR: hour T without travel times by k_batch_count (cpm_count.h)
     int last_hour_counted = 0;    // ... 1 when the last run's hour T was that launch (CPM_INFO_LAST_HOUR)
+    LaunchCells last_cells;       // CPM_INFO_CELL_*: what the launch helpers of the last run wrote (launch_cells())
     uint32_t *ids0 = nullptr, *cnt0 = nullptr;
     unsigned long long *bstatus = nullptr;
     uint32_t *ids = nullptr, *cnt = nullptr, *D = nullptr, *cntg = nullptr, *scratch = nullptr;
@@ -268,6 +269,7 @@ inline void batch_launch_sample_t(const GroupedArgs *fleets, int nf, int per_wg,
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
     }
+    (launch_cells().hour_T ? launch_cells().last : launch_cells().batch) = cell_word(kCellBatchSample, CPT, 0, GROUPED, SPARSE);
     hipLaunchKernelGGL((k_batch_sample<kSampleBlock, CPT, GROUPED, SPARSE>), dim3(static_cast<unsigned>(Z), static_cast<unsigned>((nf + per_wg - 1) / per_wg)),
                        dim3(kSampleBlock), lds, stream, fleets, nf, per_wg);
 }
@@ -295,6 +297,7 @@ inline void batch_launch_place_t(const GroupedArgs *fleets, int nf, int bpg, int
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
     }
+    launch_cells().place = kCellBatchPlace | KRUNS << 8 | (PB / 64) << 16;
     hipLaunchKernelGGL((k_batch_place<PB, KRUNS, 2>), dim3(static_cast<unsigned>(kGroups * bpg), static_cast<unsigned>(nf)), dim3(PB), lds, stream, fleets,
                        (Z + bpg - 1) / bpg);
 }
@@ -400,12 +403,16 @@ inline int32_t batch_run(BatchWork &w, hipStream_t stream, const GroupedTables &
     const int per_wg = batch_per_wg(nf, Z, lds, cu_count);
     const int tblock = travel_block(mean, false);
     w.last_hour_counted = 0;
+    LaunchCells &cells = launch_cells();
+    cells = LaunchCells{};
     for (int t = 0; t < T; ++t) {
+        cells.hour_T = t + 1 == T;
         const GroupedArgs *at = w.args + static_cast<size_t>(t) * nf;
         const bool grouped = t + 1 < T || travel;  // (hour T without travel times: counts only, as in grouped_run)
         if (!grouped && w.count_only) {  // counts only: no pack, no search, nothing stored per car (cpm_count.h)
-            hipLaunchKernelGGL(k_batch_count, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(nf)), dim3(kCountBlock), 0, stream, at,
-                               static_cast<uint32_t>(grouped_cpt_wide(mean)));  // (the cars per lane of the plain launch it stands for)
+            const uint32_t cpt = static_cast<uint32_t>(grouped_cpt_wide(mean));  // (the cars per lane of the plain launch it stands for)
+            cells.last = kCellBatchCount | cpt << 8 | (tb.smap ? kCellSparse : 0u) << 24;
+            hipLaunchKernelGGL(k_batch_count, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(nf)), dim3(kCountBlock), 0, stream, at, cpt);
             w.last_hour_counted = 1;
         } else if (tb.smap) {
             if (grouped) batch_launch_sample_s<true, true>(at, nf, per_wg, Z, lds, mean, stream);
@@ -443,6 +450,7 @@ inline int32_t batch_run(BatchWork &w, hipStream_t stream, const GroupedTables &
         hipLaunchKernelGGL(k_batch_travel_finish, dim3(static_cast<unsigned>(nf)), dim3(kTravelParts), 0, stream, w.args, w.tt_part);
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "batch travel-time sums");
     }
+    w.last_cells = cells;
     return CPM_OK;
 }
 

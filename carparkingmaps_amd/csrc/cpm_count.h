@@ -92,6 +92,7 @@ __global__ __launch_bounds__(kCountBlock) void k_batch_count(const GroupedArgs *
 inline void grouped_launch_count(const GroupedArgs &a, int64_t mean, bool heavy_follows, hipStream_t stream)
 {
     const uint32_t cpt = static_cast<uint32_t>(heavy_follows ? grouped_cpt(mean) : grouped_cpt_wide(mean));
+    launch_cells().sampler(kCellCount | cpt << 8 | (a.smap ? kCellSparse : 0u) << 24);  // (a run-time argument here: the value the kernel is handed)
     launch(k_grouped_count, dim3(a.Z), dim3(kCountBlock), 0, stream, a, cpt);
 }
 

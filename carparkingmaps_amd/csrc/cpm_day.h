@@ -491,6 +491,7 @@ inline void grouped_launch_day_nq(const GroupedArgs *hours, int nhours, int Zq, 
         }
     }
     const int per_hour = kGroups * (zpg + nchunk);
+    launch_cells().sampler(cell_word(kCellDay, CPT, NQ, true, SPARSE));
     launch(k_grouped_day<CPT, NQ, SPARSE>, dim3(static_cast<unsigned>(nhours) * static_cast<unsigned>(per_hour)), dim3(kFusedThreads), lds, stream, hours, per_hour, nchunk, mix);
 }
 template <int CPT>

@@ -1968,6 +1968,30 @@ __global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_groupe
     }
 }
 
+// What the launch helpers of the current run launched (CPM_INFO_CELL_*, include/cpm.h): one word per role, written by the INNERMOST
+// helper from its own template parameters -- not from the rule that chose them, so the record is true even where a ladder is wrong.
+//   word = kind | CPT << 8 | NQ << 16 | flags << 24   (placing kinds: kind | KRUNS << 8 | (PB / 64) << 16);  0: no such launch
+// Host memory only: GroupedArgs and every kernel are as they were.  grouped_run / batch_run clear it when they begin and keep a copy
+// when they end; `hour_T` says which of the two sampler roles the helpers that follow write.
+constexpr uint32_t kCellSample = 1, kCellHour = 2, kCellHourPf = 3, kCellDay = 4, kCellHeavy = 5, kCellCount = 6, kCellPlace = 7,
+                   kCellBatchSample = 8, kCellBatchPlace = 9, kCellBatchCount = 10;
+constexpr uint32_t kCellGrouped = 1, kCellSparse = 2, kCellPerm = 4;
+struct LaunchCells {
+    uint32_t applied = 0, heavy = 0, last = 0, place = 0, batch = 0;
+    bool hour_T = false;
+    void sampler(uint32_t word) { (hour_T ? last : applied) = word; }
+};
+inline LaunchCells &launch_cells()
+{
+    static thread_local LaunchCells c;
+    return c;
+}
+constexpr uint32_t cell_word(uint32_t kind, int cpt, int nq, bool grouped, bool sparse, bool perm = false)
+{
+    return kind | static_cast<uint32_t>(cpt) << 8 | static_cast<uint32_t>(nq) << 16 |
+           ((grouped ? kCellGrouped : 0u) | (sparse ? kCellSparse : 0u) | (perm ? kCellPerm : 0u)) << 24;
+}
+
 // Geometry of a placing launch: threads per block, runs per 16 threads (KRUNS = 4 or 8: KRUNS / 2 passes of the 8-lane segments), blocks per destination group
 struct PlaceShape {
     int pb, kruns, bpg;
@@ -2005,6 +2029,7 @@ inline void grouped_launch_place_t(hipStream_t stream, int bpg, const uint32_t *
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
     }
+    launch_cells().place = kCellPlace | KRUNS << 8 | (PB / 64) << 16;
     launch(k_grouped_place<PB, KRUNS, 2>, dim3(kGroups * bpg), dim3(PB), lds, stream, D, cntg, zpg, zps, Z, cap, scap, idbits, cnt_next,
                        ids_next, status);
 }
@@ -2375,6 +2400,7 @@ inline void grouped_launch_nq(const GroupedArgs &a, size_t lds, hipStream_t stre
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
     }
+    launch_cells().sampler(cell_word(kCellSample, CPT, NQ, GROUPED, SPARSE));
     launch(k_grouped_sample<kSampleBlock, CPT, NQ, GROUPED, SPARSE>, dim3(a.Z), dim3(kSampleBlock), lds, stream, a);
 }
 
@@ -2442,6 +2468,7 @@ inline void grouped_launch_hour_nq(const GroupedArgs &a, hipStream_t stream)
     const int nchunk = (a.Z + kFusedChunk - 1) / kFusedChunk;
     const unsigned blocks = a.lag >= nchunk ? static_cast<unsigned>(((a.Z + 7) & ~7) + nchunk * kGroups)
                                             : static_cast<unsigned>((nchunk + a.lag) * (kFusedChunk + kGroups));
+    launch_cells().sampler(cell_word(kCellHour, CPT, NQ, true, SPARSE, PERM));
     launch(k_grouped_hour<CPT, NQ, SPARSE, PERM>, dim3(blocks), dim3(kFusedThreads), lds, stream, a);
 }
 // true when an instantiation exists for this problem (the common pack sizes; others take two launches per hour)
@@ -2505,6 +2532,7 @@ inline void grouped_launch_hour_pf_nq(const GroupedArgs &a, hipStream_t stream)
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
     }
+    launch_cells().sampler(cell_word(kCellHourPf, CPT, NQ, GROUPED, SPARSE));
     launch(k_grouped_hour_pf<CPT, NQ, GROUPED, SPARSE>, dim3(static_cast<unsigned>(a.pchunks * kGroups + kGroups * static_cast<int>(gdiv_zpg(a.gdiv)))), dim3(kFusedThreads), lds, stream, a);
 }
 template <int CPT, bool GROUPED>
@@ -2547,6 +2575,7 @@ inline void grouped_launch_heavy_nq(const GroupedArgs &a, int parts, int hgrid, 
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
     }
+    launch_cells().heavy = cell_word(kCellHeavy, CPT, NQ, true, SPARSE);
     hipLaunchKernelGGL((k_grouped_sample_heavy<kSampleBlock, CPT, NQ, SPARSE>), dim3(hgrid), dim3(kSampleBlock), lds, stream, a);
 }
 
@@ -2750,6 +2779,7 @@ struct GroupedWork {
                                                                  // launches, 1 one, 3 placing first, 6 all in one launch), from grouped_run's decision
     bool count_only = true;                                      // CPM_OPT_LAST_HOUR: hour T of a resample by k_grouped_count (cpm_count.h) where the plain sampler ran
     int last_hour_counted = 0;                                   // CPM_INFO_LAST_HOUR: 1 when the last run's hour T was a count-only launch
+    LaunchCells last_cells;                                      // CPM_INFO_CELL_*: what the launch helpers of the last run wrote (launch_cells())
 
     // destination groups of a run: general (any zones per group) for sparse row packs, power-of-two for dense ones (grouped_gdiv_of)
     void set_groups(bool general)
@@ -3054,6 +3084,8 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     int t_first = 0;
     w.last_form = day_n >= 2 ? 6 : 0;  // (raised below by the first hour that runs a one-launch form)
     w.last_hour_counted = 0;
+    LaunchCells &cells = launch_cells();
+    cells = LaunchCells{};
     if (day_n >= 2) {
         prof_begin(CPM_PROFILE_SAMPLER);
         grouped_launch_day(w.day_hours, day_n, Z, tb.Zq, G, tb.smap, static_cast<int>(w.zpg), nchunk, w.day_mix, mean, stream);
@@ -3106,6 +3138,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         // hand-off counters of the hour: by chunk (k_grouped_hour) or by group (k_grouped_hour_pf; behind a day launch: a segment of their own)
         a.done_t = after_day ? w.cnt + w.pdone_base() + static_cast<size_t>(t) * kGroups * kDoneStride
                              : w.cnt + w.done_base() + static_cast<size_t>(t) * w.fused_chunks() * kDoneStride;
+        cells.hour_T = last_hour;
         prof_begin(CPM_PROFILE_SAMPLER);
         if (pf && grouped) grouped_launch_hour_pf<true>(a, mean, stream);
         else if (pf) grouped_launch_hour_pf<false>(a, mean, stream);
@@ -3194,6 +3227,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "travel-time sum");
     }
     flush_pending();  // (an IVP ends on a placing: its final buckets are read below)
+    w.last_cells = cells;
     if (ivp && T >= 2) {  // the zones of every table hour, largest first, for the runs that follow (a hint: any order gives the same counts)
         uint32_t shift = 0;
         while ((static_cast<uint64_t>(4 * std::max<int64_t>(mean, 1)) >> shift) > 255) ++shift;

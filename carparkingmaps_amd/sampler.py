@@ -105,13 +105,18 @@ class Sampler:
 
     def last_step(self):
         """The record of the most recent step: {kernel, form, repeats (cumulative), cap_mult, parts, bailouts (cumulative), batch_fleets
-        (fleets of a batch step that the batched kernels produced; 0 after any other step)}.
+        (fleets of a batch step that the batched kernels produced; 0 after any other step), cells}.  `cells` names the instantiation
+        each role of the step launched ({applied, heavy, last, place, batch}: _lib.CPM_INFO_CELL_*, words as include/cpm.h codes them,
+        0 where the step had no such launch).
         Not a plain getter: an IVP that solve_ivp_async left in flight is committed first (the call waits for the stream and may
         repeat that IVP, which then shows in `repeats`), so it must not be called while the stream is being captured."""
         return dict(kernel=self.get_info(_lib.CPM_INFO_LAST_KERNEL), form=self.get_info(_lib.CPM_INFO_LAST_FORM),
                     repeats=self.get_info(_lib.CPM_INFO_STEPS_REPEATED), cap_mult=self.get_info(_lib.CPM_INFO_CAP_MULT),
                     parts=self.get_info(_lib.CPM_INFO_PARTS), bailouts=self.get_info(_lib.CPM_INFO_FUSED_BAILOUTS),
-                    batch_fleets=self.get_info(_lib.CPM_INFO_LAST_BATCH_FLEETS))
+                    batch_fleets=self.get_info(_lib.CPM_INFO_LAST_BATCH_FLEETS),
+                    cells=dict(applied=self.get_info(_lib.CPM_INFO_CELL_APPLIED), heavy=self.get_info(_lib.CPM_INFO_CELL_HEAVY),
+                               last=self.get_info(_lib.CPM_INFO_CELL_LAST), place=self.get_info(_lib.CPM_INFO_CELL_PLACE),
+                               batch=self.get_info(_lib.CPM_INFO_CELL_BATCH)))
 
     def set_profile(self, on=True, stride=1, kernel=0):
         """hipEvents around every `stride`-th hourly launch of `kernel` (0 sampler, 1 place, 2 travel; 3: the two kernels of a

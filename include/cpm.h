@@ -153,6 +153,30 @@ int32_t cpm_set_option(cpm_ctx *ctx, int32_t option, int64_t value);
                                     * came), 1 the travel rows of the dataset route's compact rows (csrc/cpm_dataset.h: fixed stride), 2 sparse
                                     * rows built from the datamatrix itself (a row's cells fit 32 KB of LDS), 3 the dense table the kernel
                                     * gathers from.  The travel times do not depend on it */
+/* Which INSTANTIATION of the grouped path's hourly kernels the most recent step launched, one word per role, written by the innermost
+ * launch helper from its own template parameters (host memory only; committed as CPM_INFO_LAST_FORM is: a repeated attempt overwrites
+ * it, an asynchronous IVP's is published when the IVP is committed, batch steps write their own).  0: the step had no such launch.
+ *   word = kind | CPT << 8 | NQ << 16 | flags << 24     CPT: cars per thread, NQ: LDS-DMA instructions per wave for the row pack
+ *   placing kinds:  kind | KRUNS << 8 | (PB / 64) << 16  (threads per placing block, runs per 16 threads) */
+#define CPM_INFO_CELL_APPLIED 20   /* the sampler launch of the applied hours: kind CPM_CELL_SAMPLE, _HOUR, _HOUR_PF or _DAY */
+#define CPM_INFO_CELL_HEAVY 21     /* the heavy launch behind it (CPM_CELL_HEAVY), when CPM_INFO_PARTS > 1 */
+#define CPM_INFO_CELL_LAST 22      /* hour T of a resample, which is sampled and never applied: CPM_CELL_SAMPLE (grouped or plain), _HOUR_PF in its
+                                    * plain form, _COUNT; batch steps: CPM_CELL_BATCH_SAMPLE or _BATCH_COUNT */
+#define CPM_INFO_CELL_PLACE 23     /* the placing launch (CPM_CELL_PLACE, batch steps: CPM_CELL_BATCH_PLACE); 0 where the hour's own launch places */
+#define CPM_INFO_CELL_BATCH 24     /* the batched sampler of a batch step's applied hours (CPM_CELL_BATCH_SAMPLE, NQ 0: it has no such parameter) */
+#define CPM_CELL_SAMPLE 1
+#define CPM_CELL_HOUR 2
+#define CPM_CELL_HOUR_PF 3
+#define CPM_CELL_DAY 4
+#define CPM_CELL_HEAVY 5
+#define CPM_CELL_COUNT 6           /* CPT: the run-time argument the count-only kernel was handed */
+#define CPM_CELL_PLACE 7
+#define CPM_CELL_BATCH_SAMPLE 8
+#define CPM_CELL_BATCH_PLACE 9
+#define CPM_CELL_BATCH_COUNT 10
+#define CPM_CELL_FLAG_GROUPED 1    /* the instantiation that writes the drivers' runs (false: the plain form, counts only) */
+#define CPM_CELL_FLAG_SPARSE 2     /* sparse row packs */
+#define CPM_CELL_FLAG_PERM 4       /* zones dealt largest-first (k_grouped_hour) */
 int32_t cpm_get_info(cpm_ctx *ctx, int32_t what, int64_t *value_out);
 /* run on a caller-owned hipStream_t (e.g. torch's current stream); NULL = ctx's own, which is created when a call first needs it.
  * Contexts meant to run side by side (two resamples interleave on the chip) are each given their stream right behind
