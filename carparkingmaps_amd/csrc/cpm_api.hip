@@ -291,13 +291,8 @@ int32_t update_thr(cpm_ctx *c)
 template <bool CDF, bool PACK>
 hipError_t launch_build_rows(cpm_ctx *c)
 {
-    static bool attr_done[64] = {};  // LDS opt-in (two 64 x 65 f64 tiles), once per device and instantiation
-    if (c->device < 0 || c->device >= 64 || !attr_done[c->device]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cpm::k_build_rows<CDF, PACK>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(cpm::kRowLds));
-        if (e != hipSuccess) return e;
-        if (c->device >= 0 && c->device < 64) attr_done[c->device] = true;
-    }
+    const hipError_t e = cpm::lds_opt_in<cpm::k_build_rows<CDF, PACK>>(cpm::kRowLds);  // (two 64 x 65 f64 tiles)
+    if (e != hipSuccess) return e;
     dim3 grid(nblk(c->Z, cpm::kRowTile), static_cast<unsigned>(c->T));
     hipLaunchKernelGGL((cpm::k_build_rows<CDF, PACK>), grid, dim3(cpm::kRowBlock), cpm::kRowLds, c->stream, c->d_p, CDF ? c->d_cdf : nullptr,
                        PACK ? c->d_hi : nullptr, c->d_last, c->d_ckpt, static_cast<int>(c->Z), c->Zp, cpm::pack_zq(static_cast<int>(c->Z)),
@@ -347,7 +342,6 @@ int32_t build_rows(cpm_ctx *c, bool with_cdf)
     if (rc != CPM_OK) return rc;
     c->have_cdf = true;
     c->cdf_full = cdf;
-    c->zx.tables_dirty = true;
     return CPM_OK;
 }
 
@@ -384,7 +378,6 @@ int32_t ensure_full_cdf(cpm_ctx *c)
     c->d_ckpt = keep_ckpt;
     HIP_TRY(e);
     c->cdf_full = true;
-    c->zx.tables_dirty = true;
     return CPM_OK;
 }
 
@@ -503,9 +496,7 @@ int32_t launch_histogram(cpm_ctx *c, int64_t *d_counts)
     unsigned long long *driving = parking + c->T * c->Z;
     size_t lds = sizeof(uint32_t) * 2 * c->Z;
     if (lds <= 160 * 1024) {
-        if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(cpm::k_histogram),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        HIP_TRY(cpm::lds_opt_in<cpm::k_histogram>(lds));
         // enough chunks to fill the chip, few enough that the flush (2*Z atomics per block) stays small
         int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((c->n + 16383) / 16384, 2 * c->cu_count / std::max<int64_t>(c->T / 4, 1) + 8));
         int64_t chunk = (c->n + chunks - 1) / chunks;
@@ -606,7 +597,6 @@ int32_t build_p_dest_sparse(cpm_ctx *c, double e_dest, int32_t e_is_integer, boo
     rc = check_err_flag(c, "p_dest holds NaN or negative entries (reference: BoundsError, Appendix A-7)", CPM_ERR_TABLE);
     if (rc != CPM_OK) return rc;
     c->have_cdf = true;
-    c->zx.tables_dirty = true;
     *done = true;
     return CPM_OK;
 }
@@ -669,7 +659,6 @@ int32_t upload_p_dest_sparse(cpm_ctx *c, bool *done)
     c->tables_uploaded = true;
     c->p_dense_valid = true;
     c->have_cdf = true;
-    c->zx.tables_dirty = true;
     *done = true;
     return CPM_OK;
 }
@@ -1834,7 +1823,6 @@ int32_t cpm_refresh_tables(cpm_ctx *c, int32_t with_f64_cdf)
         int32_t rc_up = pack_uploaded_rows(c, c->pk_Zc);
         if (rc_up != CPM_OK) return rc_up;
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->zx.tables_dirty = true;
         return with_f64_cdf ? ensure_full_cdf(c) : CPM_OK;
     }
     if (c->sparse_tables) {  // (the tables of a compact dataset: its rows are what they are rebuilt from)
@@ -2327,11 +2315,10 @@ int32_t cpm_debug_categorical(cpm_ctx *c, int64_t origin1, int64_t hour1, int64_
         const int G = c->pk_G;
         const size_t words = static_cast<size_t>(cpm::pack_row_words(c->Zq, G, c->sparse_tables));
         const size_t lds = sizeof(uint32_t) * words;
-        if (lds > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(cpm::k_pack_search_debug), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        e = cpm::lds_opt_in<cpm::k_pack_search_debug>(lds, cpm::kPackLds);
         const size_t th = static_cast<size_t>(hour1 - 1);
         uint32_t h_scnt = 0;
-        if (c->sparse_tables) {
+        if (e == hipSuccess && c->sparse_tables) {
             e = hipMemcpyAsync(&h_scnt, c->d_scnt + row, sizeof h_scnt, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         }
@@ -2341,8 +2328,8 @@ int32_t cpm_debug_categorical(cpm_ctx *c, int64_t origin1, int64_t hour1, int64_
                                sp ? nullptr : c->d_ckpt + th * cpm::ckpt_count(static_cast<int>(c->Z)) * c->Z, sp ? nullptr : c->d_p + th * c->Z * c->Z,
                                static_cast<int>(origin1 - 1), static_cast<int>(c->Z), c->Zq, G, c->pk_Zc, sp ? c->d_sp + row * cpm::kDsCap : nullptr,
                                sp ? c->d_sj + row * cpm::kDsCap : nullptr, std::min(h_scnt, cpm::kDsCap), n, d_k, d_o, d_n);
+            e = hipGetLastError();
         }
-        e = hipGetLastError();
     }
     int h_n = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(dest_out, d_o, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream);

@@ -258,56 +258,38 @@ inline int batch_per_wg(int nf, int Z, size_t pack_bytes, int cu_count)
 }
 
 template <int CPT, bool GROUPED, bool SPARSE>
-inline void batch_launch_sample_t(const GroupedArgs *fleets, int nf, int per_wg, int Z, size_t lds, hipStream_t stream)
+inline hipError_t batch_launch_sample_t(const GroupedArgs *fleets, int nf, int per_wg, int Z, size_t lds, hipStream_t stream)
 {
-    if (lds > 48 * 1024) {  // LDS opt-in, once per device
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_batch_sample<kSampleBlock, CPT, GROUPED, SPARSE>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
+    constexpr auto kernel = k_batch_sample<kSampleBlock, CPT, GROUPED, SPARSE>;
+    const hipError_t e = lds_opt_in<kernel>(lds, kPackLds);
+    if (e != hipSuccess) return e;
     (launch_cells().hour_T ? launch_cells().last : launch_cells().batch) = cell_word(kCellBatchSample, CPT, 0, GROUPED, SPARSE);
-    hipLaunchKernelGGL((k_batch_sample<kSampleBlock, CPT, GROUPED, SPARSE>), dim3(static_cast<unsigned>(Z), static_cast<unsigned>((nf + per_wg - 1) / per_wg)),
-                       dim3(kSampleBlock), lds, stream, fleets, nf, per_wg);
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(Z), static_cast<unsigned>((nf + per_wg - 1) / per_wg)), dim3(kSampleBlock), lds, stream, fleets, nf,
+                       per_wg);
+    return hipSuccess;
 }
 template <bool GROUPED, bool SPARSE>
-inline void batch_launch_sample_s(const GroupedArgs *fleets, int nf, int per_wg, int Z, size_t lds, int64_t mean, hipStream_t stream)
+inline hipError_t batch_launch_sample_s(const GroupedArgs *fleets, int nf, int per_wg, int Z, size_t lds, int64_t mean, hipStream_t stream)
 {
-    switch (grouped_cpt_wide(mean)) {  // (no heavy launch follows: the slots of the hourly sampler where none does)
-    case 1: batch_launch_sample_t<1, GROUPED, SPARSE>(fleets, nf, per_wg, Z, lds, stream); break;
-    case 2: batch_launch_sample_t<2, GROUPED, SPARSE>(fleets, nf, per_wg, Z, lds, stream); break;
-    case 4: batch_launch_sample_t<4, GROUPED, SPARSE>(fleets, nf, per_wg, Z, lds, stream); break;
-    default: batch_launch_sample_t<6, GROUPED, SPARSE>(fleets, nf, per_wg, Z, lds, stream); break;
-    }
+    // (no heavy launch follows: the slots of the hourly sampler where none does)
+    return ladder_walk<BatchCells::cpt>(grouped_cpt_wide(mean), [&](auto CPT) { return batch_launch_sample_t<CPT, GROUPED, SPARSE>(fleets, nf, per_wg, Z, lds, stream); });
 }
 
 template <int PB, int KRUNS>
-inline void batch_launch_place_t(const GroupedArgs *fleets, int nf, int bpg, int Z, hipStream_t stream)
+inline hipError_t batch_launch_place_t(const GroupedArgs *fleets, int nf, int bpg, int Z, hipStream_t stream)
 {
+    constexpr auto kernel = k_batch_place<PB, KRUNS, 2>;
     const size_t lds = static_cast<size_t>(6) * KRUNS * 2 * PB;  // sorted ids (4 B) + their zones (2 B) per slot
-    if (lds > 48 * 1024) {
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_batch_place<PB, KRUNS, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
-    launch_cells().place = kCellBatchPlace | KRUNS << 8 | (PB / 64) << 16;
-    hipLaunchKernelGGL((k_batch_place<PB, KRUNS, 2>), dim3(static_cast<unsigned>(kGroups * bpg), static_cast<unsigned>(nf)), dim3(PB), lds, stream, fleets,
-                       (Z + bpg - 1) / bpg);
+    const hipError_t e = lds_opt_in<kernel>(lds);
+    if (e != hipSuccess) return e;
+    launch_cells().place = place_word(kCellBatchPlace, PB, KRUNS);
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(kGroups * bpg), static_cast<unsigned>(nf)), dim3(PB), lds, stream, fleets, (Z + bpg - 1) / bpg);
+    return hipSuccess;
 }
-inline void batch_launch_place(const GroupedArgs *fleets, int nf, int Z, hipStream_t stream)
+inline hipError_t batch_launch_place(const GroupedArgs *fleets, int nf, int Z, hipStream_t stream)
 {
     const PlaceShape p = place_shape(Z);
-    if (p.pb == 512 && p.kruns == 4) batch_launch_place_t<512, 4>(fleets, nf, p.bpg, Z, stream);
-    else if (p.pb == 512) batch_launch_place_t<512, 8>(fleets, nf, p.bpg, Z, stream);
-    else if (p.kruns == 4) batch_launch_place_t<1024, 4>(fleets, nf, p.bpg, Z, stream);
-    else batch_launch_place_t<1024, 8>(fleets, nf, p.bpg, Z, stream);
+    return place_walk(p, [&](auto PB, auto KRUNS) { return batch_launch_place_t<PB, KRUNS>(fleets, nf, p.bpg, Z, stream); });
 }
 
 // One run of nf <= BatchWork::sub_batch fleets: fleet f draws with seeds[f] against the thresholds of batch table tabs[f] and writes the
@@ -327,8 +309,7 @@ inline int32_t batch_run(BatchWork &w, hipStream_t stream, const GroupedTables &
     w.set_groups(tb.smap != 0);
     if (!w.buckets0_valid) {  // bucket the car-indexed state once; reused until the state changes
         const size_t lds_bins = sizeof(uint32_t) * static_cast<size_t>(Z);
-        if (lds_bins > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_bucket_cars), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bins));
+        if ((e = lds_opt_in<k_bucket_cars>(lds_bins)) != hipSuccess) return hip_fail(e, "LDS of the batch bucketing");
         if ((e = hipMemsetAsync(w.cnt0, 0, sizeof(uint32_t) * 2 * Z, stream)) != hipSuccess) return hip_fail(e, "memset cnt0");
         if ((e = hipMemsetAsync(w.bstatus, 0, sizeof(unsigned long long), stream)) != hipSuccess) return hip_fail(e, "memset status");
         const int64_t chunk = (n + w.nb0 - 1) / w.nb0;
@@ -415,13 +396,14 @@ inline int32_t batch_run(BatchWork &w, hipStream_t stream, const GroupedTables &
             hipLaunchKernelGGL(k_batch_count, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(nf)), dim3(kCountBlock), 0, stream, at, cpt);
             w.last_hour_counted = 1;
         } else if (tb.smap) {
-            if (grouped) batch_launch_sample_s<true, true>(at, nf, per_wg, Z, lds, mean, stream);
-            else batch_launch_sample_s<false, true>(at, nf, per_wg, Z, lds, mean, stream);
+            if (grouped) e = batch_launch_sample_s<true, true>(at, nf, per_wg, Z, lds, mean, stream);
+            else e = batch_launch_sample_s<false, true>(at, nf, per_wg, Z, lds, mean, stream);
         } else {
-            if (grouped) batch_launch_sample_s<true, false>(at, nf, per_wg, Z, lds, mean, stream);
-            else batch_launch_sample_s<false, false>(at, nf, per_wg, Z, lds, mean, stream);
+            if (grouped) e = batch_launch_sample_s<true, false>(at, nf, per_wg, Z, lds, mean, stream);
+            else e = batch_launch_sample_s<false, false>(at, nf, per_wg, Z, lds, mean, stream);
         }
-        if (t + 1 < T) batch_launch_place(at, nf, Z, stream);  // (hour T is sampled, never applied: src/resampling.jl:81-83)
+        if (e == hipSuccess && t + 1 < T) e = batch_launch_place(at, nf, Z, stream);  // (hour T is sampled, never applied: src/resampling.jl:81-83)
+        if (e != hipSuccess) return hip_fail(e, "LDS of the batch hour's launches");
         if (travel) {
             TravelArgs tr{};
             tr.tt = tb.tt;

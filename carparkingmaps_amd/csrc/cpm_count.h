@@ -89,11 +89,12 @@ __global__ __launch_bounds__(kCountBlock) void k_batch_count(const GroupedArgs *
     grouped_count_body(fleets[blockIdx.y], blockIdx.x, cpt, s_ndrive);
 }
 
-inline void grouped_launch_count(const GroupedArgs &a, int64_t mean, bool heavy_follows, hipStream_t stream)
+inline hipError_t grouped_launch_count(const GroupedArgs &a, int64_t mean, bool heavy_follows, hipStream_t stream)
 {
     const uint32_t cpt = static_cast<uint32_t>(heavy_follows ? grouped_cpt(mean) : grouped_cpt_wide(mean));
     launch_cells().sampler(kCellCount | cpt << 8 | (a.smap ? kCellSparse : 0u) << 24);  // (a run-time argument here: the value the kernel is handed)
     launch(k_grouped_count, dim3(a.Z), dim3(kCountBlock), 0, stream, a, cpt);
+    return hipSuccess;  // (no dynamic LDS: nothing to be refused)
 }
 
 }  // namespace cpm

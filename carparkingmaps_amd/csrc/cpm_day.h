@@ -477,50 +477,23 @@ __device__ __forceinline__ void day_fill_hour(const GroupedDay &d, int t, Groupe
 }
 
 
-template <int CPT, int NQ, bool SPARSE = false>
-inline void grouped_launch_day_nq(const GroupedArgs *hours, int nhours, int Zq, int G, int smap, int zpg, int nchunk, int mix, hipStream_t stream)
+template <int CPT, int NQ, bool SPARSE>
+inline hipError_t grouped_launch_day_t(const GroupedArgs *hours, int nhours, size_t lds, int zpg, int nchunk, int mix, hipStream_t stream)
 {
-    const size_t lds = fused_lds_bytes(Zq, G, smap);
-    if (lds > 48 * 1024) {
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_grouped_day<CPT, NQ, SPARSE>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
+    constexpr auto kernel = k_grouped_day<CPT, NQ, SPARSE>;
+    const hipError_t e = lds_opt_in<kernel>(lds, kPackLds);
+    if (e != hipSuccess) return e;
     const int per_hour = kGroups * (zpg + nchunk);
     launch_cells().sampler(cell_word(kCellDay, CPT, NQ, true, SPARSE));
-    launch(k_grouped_day<CPT, NQ, SPARSE>, dim3(static_cast<unsigned>(nhours) * static_cast<unsigned>(per_hour)), dim3(kFusedThreads), lds, stream, hours, per_hour, nchunk, mix);
+    launch(kernel, dim3(static_cast<unsigned>(nhours) * static_cast<unsigned>(per_hour)), dim3(kFusedThreads), lds, stream, hours, per_hour, nchunk, mix);
+    return hipSuccess;
 }
-template <int CPT>
-inline void grouped_launch_day_c(const GroupedArgs *hours, int nhours, int Zq, int G, int smap, int zpg, int nchunk, int mix, hipStream_t stream)
-{
-    const int need = (pack_row_words(Zq, G, smap) / 4 + kSampleBlock - 1) / kSampleBlock;
-#define CPM_DAY_ARGS hours, nhours, Zq, G, smap, zpg, nchunk, mix, stream
-    if (smap) {
-        grouped_launch_day_nq<CPT, 1, true>(CPM_DAY_ARGS);
-        return;
-    }
-    if (need <= 1) grouped_launch_day_nq<CPT, 1>(CPM_DAY_ARGS);
-    else if (need <= 2) grouped_launch_day_nq<CPT, 2>(CPM_DAY_ARGS);
-    else if (need <= 3) grouped_launch_day_nq<CPT, 3>(CPM_DAY_ARGS);
-    else if (need <= 4) grouped_launch_day_nq<CPT, 4>(CPM_DAY_ARGS);
-    else if (need <= 5) grouped_launch_day_nq<CPT, 5>(CPM_DAY_ARGS);
-    else if (need <= 6) grouped_launch_day_nq<CPT, 6>(CPM_DAY_ARGS);
-    else if (need <= 8) grouped_launch_day_nq<CPT, 8>(CPM_DAY_ARGS);
-    else grouped_launch_day_nq<CPT, 12>(CPM_DAY_ARGS);
-#undef CPM_DAY_ARGS
-}
-inline void grouped_launch_day(const GroupedArgs *hours, int nhours, int Z, int Zq, int G, int smap, int zpg, int nchunk, int mix, int64_t mean, hipStream_t stream)
+inline hipError_t grouped_launch_day(const GroupedArgs *hours, int nhours, int Z, int Zq, int G, int smap, int zpg, int nchunk, int mix, int64_t mean, hipStream_t stream)
 {
     (void)Z;
-    switch (grouped_cpt(mean)) {
-    case 1: grouped_launch_day_c<1>(hours, nhours, Zq, G, smap, zpg, nchunk, mix, stream); break;
-    case 2: grouped_launch_day_c<2>(hours, nhours, Zq, G, smap, zpg, nchunk, mix, stream); break;
-    default: grouped_launch_day_c<4>(hours, nhours, Zq, G, smap, zpg, nchunk, mix, stream); break;
-    }
+    const size_t lds = fused_lds_bytes(Zq, G, smap);
+    return cell_walk<DayCells>(grouped_cpt(mean), pack_need(Zq, G, smap), smap != 0,
+                               [&](auto CPT, auto NQ, auto SPARSE) { return grouped_launch_day_t<CPT, NQ, SPARSE>(hours, nhours, lds, zpg, nchunk, mix, stream); });
 }
 
 }  // namespace cpm

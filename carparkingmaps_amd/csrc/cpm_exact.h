@@ -27,6 +27,7 @@
 
 #include "../../include/cpm.h"
 #include "cpm_kernels.h"
+#include "cpm_dispatch.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
@@ -369,7 +370,6 @@ __global__ void k_zone_unbucket(const uint32_t *__restrict__ ids, const uint32_t
 }
 
 struct ExactWork {
-    bool tables_dirty = true;
     bool buckets0_valid = false;  // ids0/off0 describe the context's current car state
     int64_t n = 0;
     int Z = 0, T = 0, nb = 0;
@@ -424,41 +424,20 @@ inline bool exact_path_fits(int Z)
 }
 
 // two cars per thread (measured at S4k: 1 -> 38.8 us, 2 -> 36.4, 3 -> 38.5, 4 -> 44.4), 512 threads
-template <bool TRAVEL, int NP>
-inline void exact_launch_np(hipStream_t stream, size_t lds_tree, const uint32_t *ids, const uint32_t *off, uint32_t *dest_out, const double *pd,
-                            const double *cdf, int Z, int Zp, int H, CarIndex cars, uint32_t step, uint64_t seed,
-                            unsigned long long *parking_t, unsigned long long *driving_t, const double *dm, int T, int t,
-                            unsigned long long *tt_sum)
-{
-    if (lds_tree > 48 * 1024) {  // LDS opt-in, once per device
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_exact_sample<TRAVEL, 512, NP, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024);
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
-    launch(k_exact_sample<TRAVEL, 512, NP, 2>, dim3(Z), dim3(512), lds_tree, stream, ids, off, dest_out, pd, cdf, Z, Zp, H, cars, step,
-                       seed, parking_t, driving_t, dm, T, t, tt_sum);
-}
-
 template <bool TRAVEL>
-inline void exact_launch_sample(hipStream_t stream, const uint32_t *ids, const uint32_t *off, uint32_t *dest_out, const double *pd, const double *cdf,
-                                int Z, int Zp, CarIndex cars, uint32_t step, uint64_t seed, unsigned long long *parking_t,
-                                unsigned long long *driving_t, const double *dm, int T, int t, unsigned long long *tt_sum)
+inline hipError_t exact_launch_sample(hipStream_t stream, const uint32_t *ids, const uint32_t *off, uint32_t *dest_out, const double *pd, const double *cdf,
+                                      int Z, int Zp, CarIndex cars, uint32_t step, uint64_t seed, unsigned long long *parking_t,
+                                      unsigned long long *driving_t, const double *dm, int T, int t, unsigned long long *tt_sum)
 {
     const int H = tree_height(Z);
     const size_t lds_tree = sizeof(double) * (size_t(1) << H);
-    const int need = (Zp / 2 + 511) / 512;
-#define CPM_EXACT_ARGS stream, lds_tree, ids, off, dest_out, pd, cdf, Z, Zp, H, cars, step, seed, parking_t, driving_t, dm, T, t, tt_sum
-    if (need <= 1) exact_launch_np<TRAVEL, 1>(CPM_EXACT_ARGS);
-    else if (need <= 2) exact_launch_np<TRAVEL, 2>(CPM_EXACT_ARGS);
-    else if (need <= 4) exact_launch_np<TRAVEL, 4>(CPM_EXACT_ARGS);
-    else if (need <= 8) exact_launch_np<TRAVEL, 8>(CPM_EXACT_ARGS);
-    else exact_launch_np<TRAVEL, 16>(CPM_EXACT_ARGS);
-#undef CPM_EXACT_ARGS
+    return ladder_walk<ExactCells::np>((Zp / 2 + 511) / 512, [&](auto NP) {
+        constexpr auto kernel = k_exact_sample<TRAVEL, 512, NP, 2>;
+        const hipError_t e = lds_opt_in<kernel>(lds_tree, 160 * 1024);
+        if (e != hipSuccess) return e;
+        launch(kernel, dim3(Z), dim3(512), lds_tree, stream, ids, off, dest_out, pd, cdf, Z, Zp, H, cars, step, seed, parking_t, driving_t, dm, T, t, tt_sum);
+        return hipSuccess;
+    });
 }
 
 // ivp == false: the T-hour resample from the state in d_zone0 (left unchanged); counts -> d_counts.
@@ -484,13 +463,8 @@ int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, cons
     hipError_t e = w.ensure(n, Z, T, cu_count);
     if (e != hipSuccess) return hip_fail(e, "zone workspace");
     const size_t lds_bins = sizeof(uint32_t) * static_cast<size_t>(Z);
-    if (w.tables_dirty) {  // LDS opt-in above 48 KiB, once per context
-        if (lds_bins > 48 * 1024) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_zone_hist), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bins));
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_zone_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bins));
-        }
-        w.tables_dirty = false;
-    }
+    if ((e = lds_opt_in<k_zone_hist>(lds_bins)) != hipSuccess || (e = lds_opt_in<k_zone_scatter>(lds_bins)) != hipSuccess)
+        return hip_fail(e, "LDS of the zone sort");
     const int64_t chunk = ((n + w.nb - 1) / w.nb + 3) / 4 * 4;  // multiple of 4: 16-B aligned chunks
     const dim3 sgrid(static_cast<unsigned>(w.nb)), sblock(kSortBlock);
     e = hipMemsetAsync(w.cursor, 0, sizeof(uint32_t) * static_cast<size_t>(T + 1) * Z, stream);
@@ -514,12 +488,13 @@ int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, cons
         const uint32_t step = static_cast<uint32_t>(ivp ? t : T - 1 + t);
         prof_begin(CPM_PROFILE_SAMPLER);
         if (travel)
-            exact_launch_sample<true>(stream, ids, off, w.dest, pd, cdf, Z, Zp, cars, step, seed, parking + static_cast<size_t>(t) * Z,
+            e = exact_launch_sample<true>(stream, ids, off, w.dest, pd, cdf, Z, Zp, cars, step, seed, parking + static_cast<size_t>(t) * Z,
                                       driving + static_cast<size_t>(t) * Z, d_dm, T, t, tt_sum);
         else
-            exact_launch_sample<false>(stream, ids, off, w.dest, pd, cdf, Z, Zp, cars, step, seed, parking + static_cast<size_t>(t) * Z,
+            e = exact_launch_sample<false>(stream, ids, off, w.dest, pd, cdf, Z, Zp, cars, step, seed, parking + static_cast<size_t>(t) * Z,
                                        driving + static_cast<size_t>(t) * Z, d_dm, T, t, tt_sum);
         prof_end(CPM_PROFILE_SAMPLER);
+        if (e != hipSuccess) return hip_fail(e, "LDS of the zone hour's sampler");
         // OD trip counts (cpm_flows.h, cpm_flows_csr.h): the hour's records lie bucket by bucket in w.dest (zeroed dense output: the caller's)
         if (fd.any() && !ivp) {
             const int32_t rc_fl = flows_hour_from_cars(stream, fd, nullptr, off, w.dest, n, Z, t, err);

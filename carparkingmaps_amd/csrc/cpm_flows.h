@@ -53,7 +53,7 @@ inline int32_t flows_launch_grouped(hipStream_t stream, const uint32_t *D, const
         err = "flows: a row of this many zones does not fit the histogram in LDS";
         return CPM_ERR_ARG;
     }
-    hipError_t e = lds_opt_in(k_grouped_flows, lds);
+    hipError_t e = lds_opt_in<k_grouped_flows>(lds);
     if (e == hipSuccess) {
         launch(k_grouped_flows, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(nt)), dim3(kRunsBlock), lds, stream, D, cntg, Z, scap, idbits, zpg, d_stride,
                c_stride, d_flows + static_cast<size_t>(t0) * Z * Z);

@@ -229,8 +229,8 @@ inline int32_t flows_csr_launch_grouped(hipStream_t stream, const uint32_t *D, c
     const int32_t rc = flows_csr_check(Z, fd, err);
     if (rc != CPM_OK) return rc;
     const size_t lds_c = flows_csr_lds_bytes(Z, false), lds_f = flows_csr_lds_bytes(Z, true);
-    hipError_t e = lds_opt_in(k_flows_csr_count, lds_c);
-    if (e == hipSuccess) e = lds_opt_in(k_flows_csr_fill, lds_f);
+    hipError_t e = lds_opt_in<k_flows_csr_count>(lds_c);
+    if (e == hipSuccess) e = lds_opt_in<k_flows_csr_fill>(lds_f);
     if (e != hipSuccess) return flows_csr_fail(e, "LDS", err);
     int64_t *rp = fd.row_ptr + static_cast<size_t>(t0) * Z;
     const dim3 grid(static_cast<unsigned>(Z), static_cast<unsigned>(nt));
@@ -257,8 +257,8 @@ inline int32_t flows_hour_from_cars(hipStream_t stream, const FlowsDest &fd, con
     const int32_t rc = flows_csr_check(Z, fd, err);
     if (rc != CPM_OK) return rc;
     const size_t lds_c = flows_csr_lds_bytes(Z, false), lds_f = flows_csr_lds_bytes(Z, true);
-    e = lds_opt_in(k_flows_csr_from_dense<false>, lds_c);
-    if (e == hipSuccess) e = lds_opt_in(k_flows_csr_from_dense<true>, lds_f);
+    e = lds_opt_in<k_flows_csr_from_dense<false>>(lds_c);
+    if (e == hipSuccess) e = lds_opt_in<k_flows_csr_from_dense<true>>(lds_f);
     if (e != hipSuccess) return flows_csr_fail(e, "LDS", err);
     if ((e = hipMemsetAsync(fd.hour_block, 0, sizeof(int32_t) * (static_cast<size_t>(Z) * Z + 4), stream)) != hipSuccess) return flows_csr_fail(e, "hour block", err);
     if ((e = flows_launch_cars(stream, zsrc, off, rec_t, n, Z, fd.hour_block)) != hipSuccess) return flows_csr_fail(e, "flows of the hour", err);

@@ -36,6 +36,7 @@
 
 #include "../../include/cpm.h"
 #include "cpm_kernels.h"
+#include "cpm_dispatch.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
@@ -43,7 +44,6 @@
 
 namespace cpm {
 
-constexpr int kGroups = 32;              // destination groups
 constexpr int kFusedThreads = 256;       // threads of every block of the fused hour (k_grouped_hour)
 constexpr int kMaxZonesPerGroup = 1024;  // LDS bins of the place kernel
 constexpr uint32_t kHiMax = 0xFFFFFFFFu;
@@ -68,13 +68,6 @@ constexpr uint32_t kDoneAbort = 0x10000u, kDoneCount = 0xFFFFu;
 // The multiply and the subtraction per driver cost the dense headline 1.1 % (same box, interleaved), so the general form is what the
 // SPARSE sampler instantiations run (datasets: Melbourne's Z = 2,357 and its like) and dense tables keep power-of-two groups -- in the
 // same word: M = 1, s = log2 zpg, which the general formula also reads correctly (the kernels that are not hot use it for both).
-inline uint32_t grouped_zpg_of(int Z, bool general = false)
-{
-    if (general) return static_cast<uint32_t>(std::max(1, (Z + kGroups - 1) / kGroups));
-    uint32_t s = 0;
-    while ((static_cast<int64_t>(kGroups) << s) < Z) ++s;
-    return 1u << s;
-}
 inline uint32_t grouped_gdiv_of(int Z, bool general = false)
 {
     const uint32_t zpg = grouped_zpg_of(Z, general);
@@ -111,33 +104,6 @@ __device__ __forceinline__ uint32_t gdiv_local_t(uint32_t p, uint32_t dest, uint
 {
     if constexpr (GEN) return gdiv_local(p, dest, g);
     else return dest & (p >> 22);
-}
-
-// ------------------------------------------------------------------------------------------------ row packs
-__host__ __device__ inline int pack_guide_bits(int Z)
-{
-    int g = 3;  // >= 8 entries: the guide is a whole number of 16-B pieces
-    while ((1 << g) < Z) ++g;
-    // a quarter of an entry per destination: measured best at S4k (entries per destination 1: 32.0 us, 1/2: 29.9, 1/4: 29.1 --
-    // the shorter pack outweighs the longer bracket)
-    g = g - 2 < 3 ? 3 : g - 2;
-    return g;
-}
-// high words per row: Z, then at least 31 entries of 0xFFFFFFFF (the unclamped stride walk of pack_search reads up to 30 past
-// its bracket), a whole number of 128-B lines
-__host__ __device__ inline int pack_zq(int Z) { return (Z + 31 + 31) / 32 * 32; }
-__host__ __device__ inline int pack_guide_words(int G) { return (1 << G) / 2 + 4; }  // 2^G + 1 entries used (+7 pad: whole 16-B pieces)
-// smap (sparse pack, cpm_dataset.h): Zq and G of the compact row, and a u16 destination per entry behind the high words
-__host__ __device__ inline int pack_row_words(int Zq, int G, int smap = 0)  // at least 1 KiB: one whole LDS-DMA wave-instruction
-{
-    const int w = pack_guide_words(G) + Zq + (smap ? Zq / 2 : 0);  // (Zq is a multiple of 32, the guide of 4: whole 16-byte pieces)
-    return w < 256 ? 256 : w;  // (rows rounded up to whole 128-byte lines: -0.3 % at S4k, within noise -- profiles/round4_notes.md)
-}
-// a row pack must fit the 150 KiB of LDS a workgroup may ask for, and a guide entry is a u16
-inline bool pack_row_fits(int Z)
-{
-    if (Z < 2 || Z > 32768) return false;
-    return sizeof(uint32_t) * static_cast<size_t>(pack_row_words(pack_zq(Z), pack_guide_bits(Z))) <= 150 * 1024;
 }
 
 // thr[t][z] = bernoulli_threshold(p_drive[t][z]): the integer the sampler compares the 53-bit draw with (src/resampling.jl:15 as
@@ -1879,7 +1845,6 @@ constexpr int kFusedChunk = 16 * kFusedKruns;  // origin zones per chunk = runs 
 constexpr int kDoneStride = 32;  // words between the hand-off counters of consecutive chunks: a 128-B line each (64 adds and the polls of 32
                                  // placing blocks per counter; with all of an hour's counters in two lines every add and every poll of the
                                  // launch queued at one memory channel: 300 us per launch instead of 30)
-constexpr int kFusedZpg = 256;   // zones per destination group the fused form is built for (Z <= 8,192)
 
 // PERM: sampler workgroup b takes zone a.perm_t[b] -- the zones of the hour dealt LARGEST-FIRST (k_zone_order: by their size at the same
 // hour of the initial-value problem, the same tables a day earlier) -- so that the workgroups that enter last are the short ones: buckets
@@ -1968,14 +1933,9 @@ __global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_groupe
     }
 }
 
-// What the launch helpers of the current run launched (CPM_INFO_CELL_*, include/cpm.h): one word per role, written by the INNERMOST
-// helper from its own template parameters -- not from the rule that chose them, so the record is true even where a ladder is wrong.
-//   word = kind | CPT << 8 | NQ << 16 | flags << 24   (placing kinds: kind | KRUNS << 8 | (PB / 64) << 16);  0: no such launch
-// Host memory only: GroupedArgs and every kernel are as they were.  grouped_run / batch_run clear it when they begin and keep a copy
-// when they end; `hour_T` says which of the two sampler roles the helpers that follow write.
-constexpr uint32_t kCellSample = 1, kCellHour = 2, kCellHourPf = 3, kCellDay = 4, kCellHeavy = 5, kCellCount = 6, kCellPlace = 7,
-                   kCellBatchSample = 8, kCellBatchPlace = 9, kCellBatchCount = 10;
-constexpr uint32_t kCellGrouped = 1, kCellSparse = 2, kCellPerm = 4;
+// The launch record (CPM_INFO_CELL_*; the words' coding: cpm_dispatch.h).  Host memory only: GroupedArgs and every kernel are as
+// they were.  grouped_run / batch_run clear it when they begin and keep a copy when they end; `hour_T` says which of the two sampler
+// roles the helpers that follow write.
 struct LaunchCells {
     uint32_t applied = 0, heavy = 0, last = 0, place = 0, batch = 0;
     bool hour_T = false;
@@ -1986,64 +1946,27 @@ inline LaunchCells &launch_cells()
     static thread_local LaunchCells c;
     return c;
 }
-constexpr uint32_t cell_word(uint32_t kind, int cpt, int nq, bool grouped, bool sparse, bool perm = false)
-{
-    return kind | static_cast<uint32_t>(cpt) << 8 | static_cast<uint32_t>(nq) << 16 |
-           ((grouped ? kCellGrouped : 0u) | (sparse ? kCellSparse : 0u) | (perm ? kCellPerm : 0u)) << 24;
-}
-
-// Geometry of a placing launch: threads per block, runs per 16 threads (KRUNS = 4 or 8: KRUNS / 2 passes of the 8-lane segments), blocks per destination group
-struct PlaceShape {
-    int pb, kruns, bpg;
-};
-inline PlaceShape place_shape(int Z)
-{
-    const int zpg = static_cast<int>(grouped_zpg_of(Z));
-    PlaceShape p;
-    p.pb = zpg <= 512 ? 512 : 1024;
-    const int seg = p.pb / 16;
-    p.bpg = Z < 1024 ? 8 : 16;
-    while (p.bpg < 128 && (Z + p.bpg - 1) / p.bpg > 4 * seg) p.bpg *= 2;
-    p.kruns = (Z + p.bpg - 1) / p.bpg <= 4 * seg ? 4 : 8;
-    return p;
-}
-inline bool place_shape_fits(int Z)
-{
-    const PlaceShape p = place_shape(Z);
-    return (Z + p.bpg - 1) / p.bpg <= 8 * (p.pb / 16);
-}
 
 template <int PB, int KRUNS>
-inline void grouped_launch_place_t(hipStream_t stream, int bpg, const uint32_t *D, const uint32_t *cntg, int zpg, int Z, uint32_t cap, uint32_t scap,
-                                   uint32_t idbits, uint32_t *cnt_next, uint32_t *ids_next, unsigned long long *status)
+inline hipError_t grouped_launch_place_t(hipStream_t stream, int bpg, const uint32_t *D, const uint32_t *cntg, int zpg, int Z, uint32_t cap, uint32_t scap,
+                                         uint32_t idbits, uint32_t *cnt_next, uint32_t *ids_next, unsigned long long *status)
 {
+    constexpr auto kernel = k_grouped_place<PB, KRUNS, 2>;
     const int zps = (Z + bpg - 1) / bpg;
     const size_t lds = static_cast<size_t>(6) * KRUNS * 2 * PB;  // sorted ids (4 B) + their zones (2 B) per slot
-    if (lds > 48 * 1024) {  // LDS opt-in, once per device
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_grouped_place<PB, KRUNS, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(lds));
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
-    launch_cells().place = kCellPlace | KRUNS << 8 | (PB / 64) << 16;
-    launch(k_grouped_place<PB, KRUNS, 2>, dim3(kGroups * bpg), dim3(PB), lds, stream, D, cntg, zpg, zps, Z, cap, scap, idbits, cnt_next,
-                       ids_next, status);
+    const hipError_t e = lds_opt_in<kernel>(lds);
+    if (e != hipSuccess) return e;
+    launch_cells().place = place_word(kCellPlace, PB, KRUNS);
+    launch(kernel, dim3(kGroups * bpg), dim3(PB), lds, stream, D, cntg, zpg, zps, Z, cap, scap, idbits, cnt_next, ids_next, status);
+    return hipSuccess;
 }
-
-inline void grouped_launch_place(hipStream_t stream, const uint32_t *D, const uint32_t *cntg, int zpg, int Z, uint32_t cap, uint32_t scap,
-                                 uint32_t idbits, uint32_t *cnt_next, uint32_t *ids_next, unsigned long long *status)
+inline hipError_t grouped_launch_place(hipStream_t stream, const uint32_t *D, const uint32_t *cntg, int zpg, int Z, uint32_t cap, uint32_t scap,
+                                       uint32_t idbits, uint32_t *cnt_next, uint32_t *ids_next, unsigned long long *status)
 {
     const PlaceShape p = place_shape(Z);
-#define CPM_PLACE_ARGS stream, p.bpg, D, cntg, zpg, Z, cap, scap, idbits, cnt_next, ids_next, status
-    if (p.pb == 512 && p.kruns == 4) grouped_launch_place_t<512, 4>(CPM_PLACE_ARGS);
-    else if (p.pb == 512) grouped_launch_place_t<512, 8>(CPM_PLACE_ARGS);
-    else if (p.kruns == 4) grouped_launch_place_t<1024, 4>(CPM_PLACE_ARGS);
-    else grouped_launch_place_t<1024, 8>(CPM_PLACE_ARGS);
-#undef CPM_PLACE_ARGS
+    return place_walk(p, [&](auto PB, auto KRUNS) {
+        return grouped_launch_place_t<PB, KRUNS>(stream, p.bpg, D, cntg, zpg, Z, cap, scap, idbits, cnt_next, ids_next, status);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ travel times
@@ -2385,60 +2308,25 @@ __global__ __launch_bounds__(256) void k_grouped_travel_finish(unsigned long lon
 }
 
 // ------------------------------------------------------------------------------------------------ launch helpers
-constexpr int kSampleBlock = 256;  // measured at S4k: 512 threads x 2 cars: 31 us, 256 x 4: 28, 128 x 8: 44
-
-template <bool GROUPED, int CPT, int NQ, bool SPARSE = false>
-inline void grouped_launch_nq(const GroupedArgs &a, size_t lds, hipStream_t stream)
+// One function per family holds the family's body -- kernel, LDS opt-in, record word, grid, launch -- with the instantiation as its
+// template parameters; the function under it walks the family's tables (cell_walk, cpm_dispatch.h) from the run-time cars per thread
+// and the pack's need.  A refused LDS opt-in comes back as the launcher's error, before anything is launched.
+template <bool GROUPED, int CPT, int NQ, bool SPARSE>
+inline hipError_t grouped_launch_sample_t(const GroupedArgs &a, size_t lds, hipStream_t stream)
 {
-    if (lds > 48 * 1024) {  // LDS opt-in, once per device (contexts of several devices may live in one process)
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_grouped_sample<kSampleBlock, CPT, NQ, GROUPED, SPARSE>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
+    constexpr auto kernel = k_grouped_sample<kSampleBlock, CPT, NQ, GROUPED, SPARSE>;
+    const hipError_t e = lds_opt_in<kernel>(lds, kPackLds);  // (contexts of several devices may live in one process)
+    if (e != hipSuccess) return e;
     launch_cells().sampler(cell_word(kCellSample, CPT, NQ, GROUPED, SPARSE));
-    launch(k_grouped_sample<kSampleBlock, CPT, NQ, GROUPED, SPARSE>, dim3(a.Z), dim3(kSampleBlock), lds, stream, a);
+    launch(kernel, dim3(a.Z), dim3(kSampleBlock), lds, stream, a);
+    return hipSuccess;
 }
-
-template <bool GROUPED, int CPT>
-inline void grouped_launch_c(const GroupedArgs &a, hipStream_t stream)
+template <bool GROUPED>
+inline hipError_t grouped_launch_sample(const GroupedArgs &a, int64_t mean, bool heavy_follows, hipStream_t stream)
 {
-    const int words = pack_row_words(a.Zq, a.G, a.smap);
-    const size_t lds = sizeof(uint32_t) * static_cast<size_t>(words);
-    const int need = (words / 4 + kSampleBlock - 1) / kSampleBlock;
-    if (a.smap) {  // (a sparse pack is at most kDsCap entries: one LDS-DMA instruction per wave; sparse_shape_ok)
-        grouped_launch_nq<GROUPED, CPT, 1, true>(a, lds, stream);
-        return;
-    }
-    if (need <= 1) grouped_launch_nq<GROUPED, CPT, 1>(a, lds, stream);
-    else if (need <= 2) grouped_launch_nq<GROUPED, CPT, 2>(a, lds, stream);
-    else if (need <= 3) grouped_launch_nq<GROUPED, CPT, 3>(a, lds, stream);
-    else if (need <= 4) grouped_launch_nq<GROUPED, CPT, 4>(a, lds, stream);
-    else if (need <= 5) grouped_launch_nq<GROUPED, CPT, 5>(a, lds, stream);
-    else if (need <= 6) grouped_launch_nq<GROUPED, CPT, 6>(a, lds, stream);
-    else if (need <= 8) grouped_launch_nq<GROUPED, CPT, 8>(a, lds, stream);
-    else if (need <= 12) grouped_launch_nq<GROUPED, CPT, 12>(a, lds, stream);
-    else if (need <= 20) grouped_launch_nq<GROUPED, CPT, 20>(a, lds, stream);
-    else grouped_launch_nq<GROUPED, CPT, 40>(a, lds, stream);
-}
-
-inline int grouped_cpt(int64_t mean) { return mean <= 224 ? 1 : (mean <= 560 ? 2 : 4); }
-// ... and where no heavy bucket has been seen (the heavy launch shares the sampler's chunking: it stays with grouped_cpt): slots for
-// 1.5 x the mean bucket.  Buckets spread from half to 2.5 x the mean on flat tables, and a bucket beyond its workgroup's slots pays a
-// whole serial round (ids, Philox, search, ranks) per 256 cars more, while a wave only runs the K <= CPT cars per lane it holds
-// (first_pass): at S4k 42 % of the buckets needed such rounds with 4 cars per lane, 0.851 -> 0.815 ms per resample with 6 (same box,
-// interleaved; 5: 0.827, 7: 0.824 with 9 vector registers spilled, 8 at five waves per SIMD: 0.856 -- profiles/round4_notes.md).
-#ifndef CPM_CPT_RULE
-#define CPM_CPT_RULE 1
-#endif
-inline int grouped_cpt_wide(int64_t mean)
-{
-    if (CPM_CPT_RULE == 0) return grouped_cpt(mean);
-    return mean <= 170 ? 1 : (mean <= 340 ? 2 : (mean <= 700 ? 4 : 6));
+    const size_t lds = sizeof(uint32_t) * static_cast<size_t>(pack_row_words(a.Zq, a.G, a.smap));
+    return cell_walk<SampleCells>(heavy_follows ? grouped_cpt(mean) : grouped_cpt_wide(mean), pack_need(a.Zq, a.G, a.smap), a.smap != 0,
+                                  [&](auto CPT, auto NQ, auto SPARSE) { return grouped_launch_sample_t<GROUPED, CPT, NQ, SPARSE>(a, lds, stream); });
 }
 
 // the fused hour (k_grouped_hour): (chunks + lag) x (kFusedChunk sampler workgroups + kGroups placing blocks)
@@ -2446,37 +2334,25 @@ inline size_t fused_lds_bytes(int Zq, int G, int smap = 0)
 {
     return std::max(sizeof(uint32_t) * static_cast<size_t>(pack_row_words(Zq, G, smap)), static_cast<size_t>(4 + sizeof(PlaceLds<kFusedThreads, kFusedKruns, kFusedZpg>::zone_t)) * kFusedKruns * kFusedKdeep * kFusedThreads);
 }
-template <int CPT, int NQ, bool SPARSE = false, bool PERM = false>
-inline void grouped_launch_hour_nq(const GroupedArgs &a, hipStream_t stream)
+template <int CPT, int NQ, bool SPARSE, bool PERM = false>
+inline hipError_t grouped_launch_hour_t(const GroupedArgs &a, hipStream_t stream)
 {
-    if constexpr (!PERM) {
-        if (a.perm_t && a.lag >= (a.Z + kFusedChunk - 1) / kFusedChunk) {  // (zones dealt largest-first: only in the samplers-then-placing order)
-            grouped_launch_hour_nq<CPT, NQ, SPARSE, true>(a, stream);
-            return;
-        }
-    }
-    const size_t lds = fused_lds_bytes(a.Zq, a.G, a.smap);
-    if (lds > 48 * 1024) {
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_grouped_hour<CPT, NQ, SPARSE, PERM>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
     const int nchunk = (a.Z + kFusedChunk - 1) / kFusedChunk;
+    if constexpr (!PERM) {
+        if (a.perm_t && a.lag >= nchunk)  // (zones dealt largest-first: only in the samplers-then-placing order)
+            return grouped_launch_hour_t<CPT, NQ, SPARSE, true>(a, stream);
+    }
+    constexpr auto kernel = k_grouped_hour<CPT, NQ, SPARSE, PERM>;
+    const size_t lds = fused_lds_bytes(a.Zq, a.G, a.smap);
+    const hipError_t e = lds_opt_in<kernel>(lds, kPackLds);
+    if (e != hipSuccess) return e;
     const unsigned blocks = a.lag >= nchunk ? static_cast<unsigned>(((a.Z + 7) & ~7) + nchunk * kGroups)
                                             : static_cast<unsigned>((nchunk + a.lag) * (kFusedChunk + kGroups));
     launch_cells().sampler(cell_word(kCellHour, CPT, NQ, true, SPARSE, PERM));
-    launch(k_grouped_hour<CPT, NQ, SPARSE, PERM>, dim3(blocks), dim3(kFusedThreads), lds, stream, a);
+    launch(kernel, dim3(blocks), dim3(kFusedThreads), lds, stream, a);
+    return hipSuccess;
 }
-// true when an instantiation exists for this problem (the common pack sizes; others take two launches per hour)
-inline bool fused_shape_ok(int Z, int Zq, int G, int smap = 0)
-{
-    const int need = (pack_row_words(Zq, G, smap) / 4 + kSampleBlock - 1) / kSampleBlock;
-    return static_cast<int>(grouped_zpg_of(Z)) <= kFusedZpg && need <= 12;
-}
+// An instantiation exists for the common pack sizes (fused_shape_ok, cpm_dispatch.h; others take two launches per hour) ...
 // ... and where it PAYS.  MEASURED (one launch against two per hour, 1,000 cars per zone, interleaved runs on one box, ms per
 // resample): Z = 1,536: 0.524 / 0.493, 2,357: 0.664 / 0.650, 3,072: 0.710 / 0.727, 4,096: 0.868 / 0.912 (500 cars per zone: 0.703 /
 // 0.760, 2,000: 2.21 / 2.21), 5,120: 1.283 / 1.362, 6,144: 1.680 / 1.615, 8,192 x 500: 2.19 / 2.07.  It pays from two rounds of sampler
@@ -2492,131 +2368,47 @@ inline bool fused_pays(int Z, int Zq, int G, int cu_count, int smap = 0, int64_t
     const size_t lds = fused_lds_bytes(Zq, G, smap) + 4608;  // (+ the static part: SampleLds / PlaceLds)
     return Z >= 12 * std::max(cu_count, 1) && 5 * lds <= 160 * 1024;
 }
-template <int CPT>
-inline void grouped_launch_hour_c(const GroupedArgs &a, hipStream_t stream)
+inline hipError_t grouped_launch_hour(const GroupedArgs &a, int64_t mean, hipStream_t stream)
 {
-    const int need = (pack_row_words(a.Zq, a.G, a.smap) / 4 + kSampleBlock - 1) / kSampleBlock;
-    if (a.smap) {
-        grouped_launch_hour_nq<CPT, 1, true>(a, stream);
-        return;
-    }
-    if (need <= 1) grouped_launch_hour_nq<CPT, 1>(a, stream);
-    else if (need <= 2) grouped_launch_hour_nq<CPT, 2>(a, stream);
-    else if (need <= 3) grouped_launch_hour_nq<CPT, 3>(a, stream);
-    else if (need <= 4) grouped_launch_hour_nq<CPT, 4>(a, stream);
-    else if (need <= 5) grouped_launch_hour_nq<CPT, 5>(a, stream);
-    else if (need <= 6) grouped_launch_hour_nq<CPT, 6>(a, stream);
-    else if (need <= 8) grouped_launch_hour_nq<CPT, 8>(a, stream);
-    else grouped_launch_hour_nq<CPT, 12>(a, stream);
-}
-inline void grouped_launch_hour(const GroupedArgs &a, int64_t mean, hipStream_t stream)
-{
-    switch (grouped_cpt_wide(mean)) {  // (one launch per hour only while no heavy bucket has been seen)
-    case 1: grouped_launch_hour_c<1>(a, stream); break;
-    case 2: grouped_launch_hour_c<2>(a, stream); break;
-    case 4: grouped_launch_hour_c<4>(a, stream); break;
-    default: grouped_launch_hour_c<6>(a, stream); break;
-    }
+    // (one launch per hour only while no heavy bucket has been seen: the wide rule)
+    return cell_walk<HourCells>(grouped_cpt_wide(mean), pack_need(a.Zq, a.G, a.smap), a.smap != 0,
+                                [&](auto CPT, auto NQ, auto SPARSE) { return grouped_launch_hour_t<CPT, NQ, SPARSE>(a, stream); });
 }
 
-template <int CPT, int NQ, bool GROUPED, bool SPARSE = false>
-inline void grouped_launch_hour_pf_nq(const GroupedArgs &a, hipStream_t stream)
+template <int CPT, int NQ, bool GROUPED, bool SPARSE>
+inline hipError_t grouped_launch_hour_pf_t(const GroupedArgs &a, hipStream_t stream)
 {
+    constexpr auto kernel = k_grouped_hour_pf<CPT, NQ, GROUPED, SPARSE>;
     const size_t lds = fused_lds_bytes(a.Zq, a.G, a.smap);
-    if (lds > 48 * 1024) {
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_grouped_hour_pf<CPT, NQ, GROUPED, SPARSE>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
+    const hipError_t e = lds_opt_in<kernel>(lds, kPackLds);
+    if (e != hipSuccess) return e;
     launch_cells().sampler(cell_word(kCellHourPf, CPT, NQ, GROUPED, SPARSE));
-    launch(k_grouped_hour_pf<CPT, NQ, GROUPED, SPARSE>, dim3(static_cast<unsigned>(a.pchunks * kGroups + kGroups * static_cast<int>(gdiv_zpg(a.gdiv)))), dim3(kFusedThreads), lds, stream, a);
-}
-template <int CPT, bool GROUPED>
-inline void grouped_launch_hour_pf_c(const GroupedArgs &a, hipStream_t stream)
-{
-    const int need = (pack_row_words(a.Zq, a.G, a.smap) / 4 + kSampleBlock - 1) / kSampleBlock;
-    if (a.smap) {
-        grouped_launch_hour_pf_nq<CPT, 1, GROUPED, true>(a, stream);
-        return;
-    }
-    if (need <= 1) grouped_launch_hour_pf_nq<CPT, 1, GROUPED>(a, stream);
-    else if (need <= 2) grouped_launch_hour_pf_nq<CPT, 2, GROUPED>(a, stream);
-    else if (need <= 3) grouped_launch_hour_pf_nq<CPT, 3, GROUPED>(a, stream);
-    else if (need <= 4) grouped_launch_hour_pf_nq<CPT, 4, GROUPED>(a, stream);
-    else if (need <= 5) grouped_launch_hour_pf_nq<CPT, 5, GROUPED>(a, stream);
-    else if (need <= 6) grouped_launch_hour_pf_nq<CPT, 6, GROUPED>(a, stream);
-    else if (need <= 8) grouped_launch_hour_pf_nq<CPT, 8, GROUPED>(a, stream);
-    else grouped_launch_hour_pf_nq<CPT, 12, GROUPED>(a, stream);
+    launch(kernel, dim3(static_cast<unsigned>(a.pchunks * kGroups + kGroups * static_cast<int>(gdiv_zpg(a.gdiv)))), dim3(kFusedThreads), lds, stream, a);
+    return hipSuccess;
 }
 template <bool GROUPED>
-inline void grouped_launch_hour_pf(const GroupedArgs &a, int64_t mean, hipStream_t stream)
+inline hipError_t grouped_launch_hour_pf(const GroupedArgs &a, int64_t mean, hipStream_t stream)
 {
-    switch (grouped_cpt(mean)) {
-    case 1: grouped_launch_hour_pf_c<1, GROUPED>(a, stream); break;
-    case 2: grouped_launch_hour_pf_c<2, GROUPED>(a, stream); break;
-    default: grouped_launch_hour_pf_c<4, GROUPED>(a, stream); break;
-    }
+    return cell_walk<HourPfCells>(grouped_cpt(mean), pack_need(a.Zq, a.G, a.smap), a.smap != 0,
+                                  [&](auto CPT, auto NQ, auto SPARSE) { return grouped_launch_hour_pf_t<CPT, NQ, GROUPED, SPARSE>(a, stream); });
 }
 
-template <int CPT, int NQ, bool SPARSE = false>
-inline void grouped_launch_heavy_nq(const GroupedArgs &a, int parts, int hgrid, size_t lds, hipStream_t stream)
+template <int CPT, int NQ, bool SPARSE>
+inline hipError_t grouped_launch_heavy_t(const GroupedArgs &a, int hgrid, size_t lds, hipStream_t stream)
 {
-    if (lds > 48 * 1024) {
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_grouped_sample_heavy<kSampleBlock, CPT, NQ, SPARSE>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
+    constexpr auto kernel = k_grouped_sample_heavy<kSampleBlock, CPT, NQ, SPARSE>;
+    const hipError_t e = lds_opt_in<kernel>(lds, kPackLds);
+    if (e != hipSuccess) return e;
     launch_cells().heavy = cell_word(kCellHeavy, CPT, NQ, true, SPARSE);
-    hipLaunchKernelGGL((k_grouped_sample_heavy<kSampleBlock, CPT, NQ, SPARSE>), dim3(hgrid), dim3(kSampleBlock), lds, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(hgrid), dim3(kSampleBlock), lds, stream, a);
+    return hipSuccess;
 }
-
-template <int CPT>
-inline void grouped_launch_heavy_c(const GroupedArgs &a, int parts, int hgrid, hipStream_t stream)
+inline hipError_t grouped_launch_heavy(const GroupedArgs &a, int parts, int hgrid, int64_t mean, hipStream_t stream)
 {
-    const int words = pack_row_words(a.Zq, a.G, a.smap);
-    const size_t lds = sizeof(uint32_t) * static_cast<size_t>(words);
-    const int need = (words / 4 + kSampleBlock - 1) / kSampleBlock;
-    if (a.smap) {
-        grouped_launch_heavy_nq<CPT, 2, true>(a, parts, hgrid, lds, stream);
-        return;
-    }
-    if (need <= 2) grouped_launch_heavy_nq<CPT, 2>(a, parts, hgrid, lds, stream);
-    else if (need <= 5) grouped_launch_heavy_nq<CPT, 5>(a, parts, hgrid, lds, stream);
-    else if (need <= 12) grouped_launch_heavy_nq<CPT, 12>(a, parts, hgrid, lds, stream);
-    else grouped_launch_heavy_nq<CPT, 40>(a, parts, hgrid, lds, stream);
-}
-
-
-inline void grouped_launch_heavy(const GroupedArgs &a, int parts, int hgrid, int64_t mean, hipStream_t stream)
-{
-    if (parts <= 1 || hgrid == 0) return;
-    switch (grouped_cpt(mean)) {
-    case 1: grouped_launch_heavy_c<1>(a, parts, hgrid, stream); break;
-    case 2: grouped_launch_heavy_c<2>(a, parts, hgrid, stream); break;
-    default: grouped_launch_heavy_c<4>(a, parts, hgrid, stream); break;
-    }
-}
-
-// Cars per thread by the mean bucket size (cars of this GPU / zones): 256 x 4 slots for ~1000 cars per zone, 256 x 2 and 256 x 1
-// for smaller buckets (every slot runs Philox whether a car sits in it or not); larger buckets take the overflow rounds.
-template <bool GROUPED>
-inline void grouped_launch_sample(const GroupedArgs &a, int64_t mean, bool heavy_follows, hipStream_t stream)
-{
-    switch (heavy_follows ? grouped_cpt(mean) : grouped_cpt_wide(mean)) {
-    case 1: grouped_launch_c<GROUPED, 1>(a, stream); break;
-    case 2: grouped_launch_c<GROUPED, 2>(a, stream); break;
-    case 4: grouped_launch_c<GROUPED, 4>(a, stream); break;
-    default: grouped_launch_c<GROUPED, 6>(a, stream); break;
-    }
+    if (parts <= 1 || hgrid == 0) return hipSuccess;
+    const size_t lds = sizeof(uint32_t) * static_cast<size_t>(pack_row_words(a.Zq, a.G, a.smap));
+    return cell_walk<HeavyCells>(grouped_cpt(mean), pack_need(a.Zq, a.G, a.smap), a.smap != 0,
+                                 [&](auto CPT, auto NQ, auto SPARSE) { return grouped_launch_heavy_t<CPT, NQ, SPARSE>(a, hgrid, lds, stream); });
 }
 
 // Diagnostic (cpm_debug_categorical): the categorical draw of the sampler for given 53-bit draws k against one
@@ -2713,13 +2505,6 @@ namespace cpm {
 // box 0.874 -> 0.851: the unpadded form also flipped between 0.86 and 0.89 from process to process, the padded one does not)
 inline uint32_t odd_lines(uint32_t words) { return ((words / 32u) & 1u) == 0u ? words + 32u : words; }
 inline uint32_t grouped_scap(uint32_t cap) { return odd_lines((std::max<uint32_t>(64u, cap / 4) + 31u) / 32u * 32u); }
-// packed driver = id | (dest - group * zpg) << idbits: the local destination takes ceil(log2 zpg) bits, at least one
-inline uint32_t grouped_idbits(int Z, bool general = false)
-{
-    uint32_t b = 1;
-    while ((1u << b) < grouped_zpg_of(Z, general)) ++b;
-    return 32u - b;
-}
 inline uint32_t grouped_cap(int64_t n, int Z, int cap_mult)
 {
     const int64_t mean = (n + Z - 1) / Z;
@@ -2740,7 +2525,6 @@ inline bool grouped_path_fits(int64_t n, int Z, int cap_mult = 4)
 }
 
 struct GroupedWork {
-    bool attrs_set = false;
     bool buckets0_valid = false;  // ids0 / cnt0 describe the context's current car state
     int64_t n = 0;
     int Z = 0, T = 0, nb0 = 0;
@@ -2948,11 +2732,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     if (e != hipSuccess) return hip_fail(e, "grouped zone workspace");
     w.set_groups(tb.smap != 0);
     const size_t lds_bins = sizeof(uint32_t) * static_cast<size_t>(Z);
-    if (!w.attrs_set) {
-        if (lds_bins > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_bucket_cars), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bins));
-        w.attrs_set = true;
-    }
+    if ((e = lds_opt_in<k_bucket_cars>(lds_bins)) != hipSuccess) return hip_fail(e, "LDS of the bucketing");
     unsigned long long *parking = reinterpret_cast<unsigned long long *>(d_counts);
     unsigned long long *driving = parking + static_cast<size_t>(T) * Z;
     unsigned long long *tt_sum = parking + 2 * static_cast<size_t>(T) * Z;
@@ -3075,11 +2855,12 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     // placing first: the drivers of the hour before, still in their runs, wait for the next launch to move them into `ids` / `cnt`
     const uint32_t *pend_D = nullptr, *pend_cntg = nullptr;
     auto flush_pending = [&]() {  // ... or for a placing launch of their own, when that launch is not of the placing-first kind
-        if (!pend_D) return;
+        if (!pend_D) return hipSuccess;
         prof_begin(CPM_PROFILE_PLACE);
-        grouped_launch_place(stream, pend_D, pend_cntg, static_cast<int>(w.zpg), Z, w.cap, w.scap, w.idbits, const_cast<uint32_t *>(cnt) + Z, const_cast<uint32_t *>(ids), status);
+        const hipError_t ep = grouped_launch_place(stream, pend_D, pend_cntg, static_cast<int>(w.zpg), Z, w.cap, w.scap, w.idbits, const_cast<uint32_t *>(cnt) + Z, const_cast<uint32_t *>(ids), status);
         prof_end(CPM_PROFILE_PLACE);
         pend_D = pend_cntg = nullptr;
+        return ep;
     };
     int t_first = 0;
     w.last_form = day_n >= 2 ? 6 : 0;  // (raised below by the first hour that runs a one-launch form)
@@ -3088,9 +2869,9 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     cells = LaunchCells{};
     if (day_n >= 2) {
         prof_begin(CPM_PROFILE_SAMPLER);
-        grouped_launch_day(w.day_hours, day_n, Z, tb.Zq, G, tb.smap, static_cast<int>(w.zpg), nchunk, w.day_mix, mean, stream);
+        e = grouped_launch_day(w.day_hours, day_n, Z, tb.Zq, G, tb.smap, static_cast<int>(w.zpg), nchunk, w.day_mix, mean, stream);
         prof_end(CPM_PROFILE_SAMPLER);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "grouped zone day launch");
+        if (e != hipSuccess || (e = hipGetLastError()) != hipSuccess) return hip_fail(e, "grouped zone day launch");
         // the drivers of its last hour are still in their runs: placed in front of hour T's sampler workgroups, or by a launch of their own
         t_first = day_n;
         ids = ((day_n - 1) & 1) ? w.idsB : w.idsA;
@@ -3130,7 +2911,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         const bool pf = shape && (w.fused_pf || after_day);  // (also the last hour, in its plain form: the placing of the hour before it rides in front)
         const bool fuse = grouped && !last_hour && shape && !pf;
         if (w.last_form == 0 && (pf || fuse)) w.last_form = pf ? 3 : 1;
-        if (!pf) flush_pending();
+        if (!pf && (e = flush_pending()) != hipSuccess) return hip_fail(e, "LDS of the placing launch");
         a.pD = pend_D;
         a.pcntg = pend_cntg;
         a.pchunks = pend_D ? nchunk : 0;
@@ -3140,24 +2921,26 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
                              : w.cnt + w.done_base() + static_cast<size_t>(t) * w.fused_chunks() * kDoneStride;
         cells.hour_T = last_hour;
         prof_begin(CPM_PROFILE_SAMPLER);
-        if (pf && grouped) grouped_launch_hour_pf<true>(a, mean, stream);
-        else if (pf) grouped_launch_hour_pf<false>(a, mean, stream);
-        else if (fuse) grouped_launch_hour(a, mean, stream);
-        else if (grouped) grouped_launch_sample<true>(a, mean, w.parts > 1, stream);
+        if (pf && grouped) e = grouped_launch_hour_pf<true>(a, mean, stream);
+        else if (pf) e = grouped_launch_hour_pf<false>(a, mean, stream);
+        else if (fuse) e = grouped_launch_hour(a, mean, stream);
+        else if (grouped) e = grouped_launch_sample<true>(a, mean, w.parts > 1, stream);
         else if (w.count_only) {  // hour T, counts only: nobody reads the destinations the plain form draws (cpm_count.h)
-            grouped_launch_count(a, mean, w.parts > 1, stream);
+            e = grouped_launch_count(a, mean, w.parts > 1, stream);
             w.last_hour_counted = 1;
-        } else grouped_launch_sample<false>(a, mean, w.parts > 1, stream);
+        } else e = grouped_launch_sample<false>(a, mean, w.parts > 1, stream);
         prof_end(CPM_PROFILE_SAMPLER);
-        if (grouped && !fuse && !pf) grouped_launch_heavy(a, w.parts, w.hgrid, mean, stream);
+        if (e == hipSuccess && grouped && !fuse && !pf) e = grouped_launch_heavy(a, w.parts, w.hgrid, mean, stream);
+        if (e != hipSuccess) return hip_fail(e, "LDS of the hour's sampler launch");
         if (!last_hour) {
             if (pf) {
                 pend_D = a.D;
                 pend_cntg = a.cntg;
             } else if (!fuse) {
                 prof_begin(CPM_PROFILE_PLACE);
-                grouped_launch_place(stream, a.D, a.cntg, static_cast<int>(w.zpg), Z, w.cap, w.scap, w.idbits, cnt_next + Z, ids_next, status);
+                e = grouped_launch_place(stream, a.D, a.cntg, static_cast<int>(w.zpg), Z, w.cap, w.scap, w.idbits, cnt_next + Z, ids_next, status);
                 prof_end(CPM_PROFILE_PLACE);
+                if (e != hipSuccess) return hip_fail(e, "LDS of the placing launch");
             }
             ids = ids_next;
             cnt = cnt_next;
@@ -3226,7 +3009,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         hipLaunchKernelGGL(k_grouped_travel_finish, dim3(1), dim3(kTravelParts), 0, stream, w.tt_part, tt_sum);
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "travel-time sum");
     }
-    flush_pending();  // (an IVP ends on a placing: its final buckets are read below)
+    if ((e = flush_pending()) != hipSuccess) return hip_fail(e, "LDS of the placing launch");  // (an IVP ends on a placing: its final buckets are read below)
     w.last_cells = cells;
     if (ivp && T >= 2) {  // the zones of every table hour, largest first, for the runs that follow (a hint: any order gives the same counts)
         uint32_t shift = 0;

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <atomic>
 #include <mutex>
 
 #include "../../include/cpm.h"
@@ -156,53 +157,34 @@ __device__ __forceinline__ uint32_t slot_bucket(const uint32_t *__restrict__ off
     return lo;
 }
 
-// The dynamic LDS granted so far, per kernel and device (plain host bookkeeping, no HIP call).  A full table remembers nothing
-// new: a kernel it cannot hold is asked for again at every launch, which is correct and merely slower.
-struct LdsGrants {
-    static constexpr int kSlots = 32;
-    struct Slot {
-        const void *kernel;
-        int dev;
-        size_t bytes;
-    } slot[kSlots] = {};
-    int used = 0;
-    bool covers(const void *kernel, int dev, size_t bytes) const
-    {
-        for (int i = 0; i < used; ++i)
-            if (slot[i].kernel == kernel && slot[i].dev == dev) return slot[i].bytes >= bytes;
-        return false;
-    }
-    void record(const void *kernel, int dev, size_t bytes)
-    {
-        int i = 0;
-        while (i < used && !(slot[i].kernel == kernel && slot[i].dev == dev)) ++i;
-        if (i == kSlots) return;
-        if (i == used) ++used;
-        slot[i] = Slot{kernel, dev, bytes};
-    }
-};
-
 // Dynamic LDS above 48 KiB is asked for by name, once per kernel and device (and again for more), and the answer is read: a launch
 // that was not granted its LDS comes back "invalid argument" hours later in the stream (what an unchecked one cost
-// cpm_exact.h).
-inline hipError_t lds_opt_in(const void *kernel, size_t bytes)
+// cpm_exact.h).  lds_opt_in<kernel>(used, ask) in front of a launch with `used` bytes of dynamic LDS: nothing below 48 KiB; above,
+// one hipGetDevice and a load of what this kernel was granted on that device -- the state is the instantiation's own, so any
+// number of kernels is held -- and only where that is less than max(used, ask) the library's one call that sets the attribute (lds_grant), under
+// a mutex (the asking and the bookkeeping of all kernels are serialised, as they always were; the reader takes no lock).
+constexpr int kLdsDevices = 64;  // (a device beyond: asked for at every launch, which is correct and merely slower)
+inline hipError_t lds_grant(const void *kernel, std::atomic<size_t> *granted, size_t bytes)
 {
-    if (bytes <= 48 * 1024) return hipSuccess;
     static std::mutex guard;
-    static LdsGrants granted;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lock(guard);
-    if (granted.covers(kernel, dev, bytes)) return hipSuccess;
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (e == hipSuccess) granted.record(kernel, dev, bytes);
+    if (granted && granted->load(std::memory_order_relaxed) >= bytes) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (e == hipSuccess && granted) granted->store(bytes, std::memory_order_release);
     return e;
 }
-template <typename... P>
-inline hipError_t lds_opt_in(void (*kernel)(P...), size_t bytes)
+template <auto Kernel>
+inline hipError_t lds_opt_in(size_t used, size_t ask = 0)
 {
-    return lds_opt_in(reinterpret_cast<const void *>(kernel), bytes);
+    if (used <= 48 * 1024) return hipSuccess;
+    static std::atomic<size_t> granted[kLdsDevices] = {};
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::atomic<size_t> *g = dev >= 0 && dev < kLdsDevices ? &granted[dev] : nullptr;
+    const size_t bytes = used > ask ? used : ask;
+    if (g && g->load(std::memory_order_acquire) >= bytes) return hipSuccess;
+    return lds_grant(reinterpret_cast<const void *>(Kernel), g, bytes);
 }
 
 }  // namespace cpm

@@ -2,17 +2,18 @@
 
 Every hourly launcher of csrc/cpm_grouped.h, cpm_day.h, cpm_count.h and cpm_batch.h is a ladder over template parameters (CPT cars
 per thread, NQ LDS-DMA instructions per wave for the row pack, GROUPED / SPARSE / PERM), and each rung is separately compiled code.
-This module restates the host rules that choose the rung -- from the problem's Z, its cars and the context's options -- and derives
-from them
+This module restates the host rules that choose the rung (csrc/cpm_dispatch.h: the rules and each family's tables, walked by
+cell_walk) -- from the problem's Z, its cars and the context's options -- and derives from them
 
   reachable()    every cell a problem that fits the grouped path can launch, per launcher,
   unreachable()  the instantiations the build compiles that no such problem can launch, each with the rule that excludes it,
   CASES          the case table of tests/test_dispatch_cells.py: one problem per reachable cell, on the edges of the rules,
   predict()      the launch record (Sampler.last_step()["cells"], CPM_INFO_CELL_* of include/cpm.h) a step of a case must leave.
 
-The record is written by the innermost launch helpers from their own template parameters, so a disagreement between predict() and the
-record is a finding about a ladder or about this restatement; tests/test_dispatch_cells.py (CPU part) checks the band edges, that
-CASES covers reachable() entirely, and that every case fits.
+The record is written by each family's launch body (grouped_launch_sample_t and its like) from its own template parameters, so a
+disagreement between predict() and the record is a finding about a ladder or about this restatement; tests/test_dispatch_cells.py
+(CPU part) checks the band edges, that CASES covers reachable() entirely, that every case fits, and -- through tests/dispatch_probe.cc,
+a host program over cpm_dispatch.h -- that the rules restated here are the library's for every Z and every mean.
 """
 import functools
 from collections import namedtuple
@@ -79,7 +80,7 @@ def need_of(Z):
     return (pack_row_words(pack_zq(Z), pack_guide_bits(Z)) // 4 + SAMPLE_BLOCK - 1) // SAMPLE_BLOCK
 
 
-# need -> NQ: the ladders differ (grouped_launch_c, _hour_c, _hour_pf_c, _day_c, _heavy_c)
+# need -> NQ: the ladders differ (SampleCells, HourCells, HourPfCells, DayCells, HeavyCells of csrc/cpm_dispatch.h)
 LADDERS = {SAMPLE: (1, 2, 3, 4, 5, 6, 8, 12, 20, 40), HOUR: (1, 2, 3, 4, 5, 6, 8, 12), HOUR_PF: (1, 2, 3, 4, 5, 6, 8, 12),
            DAY: (1, 2, 3, 4, 5, 6, 8, 12), HEAVY_K: (2, 5, 12, 40)}
 SPARSE_NQ = {SAMPLE: 1, HOUR: 1, HOUR_PF: 1, DAY: 1, HEAVY_K: 2}   # a sparse pack is one LDS-DMA instruction per wave

@@ -1,9 +1,12 @@
-"""Every reachable instantiation of the grouped sampler's dispatch (tests/dispatch_cells.py): the rules and the case table on the CPU,
-and on the GPU every case against the oracle, bit for bit, with the launch record (CPM_INFO_CELL_*, written by the innermost launch
-helpers from their template parameters) naming exactly the cell the case claims."""
+"""Every reachable instantiation of the grouped sampler's dispatch (tests/dispatch_cells.py): the rules and the case table on the CPU
+-- the restated rules against the library's own (csrc/cpm_dispatch.h, through tests/dispatch_probe.cc) -- and on the GPU every case
+against the oracle, bit for bit, with the launch record (CPM_INFO_CELL_*, written by each family's launch body from its template
+parameters) naming exactly the cell the case claims."""
 import os
 import re
 import resource
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -77,6 +80,37 @@ def test_the_header_and_the_package_know_the_record():
                       ("CPM_CELL_FLAG_GROUPED", D.F_GROUPED), ("CPM_CELL_FLAG_SPARSE", D.F_SPARSE), ("CPM_CELL_FLAG_PERM", D.F_PERM)]:
         assert int(re.search(rf"#define\s+{name}\s+(\d+)", header).group(1)) == val == getattr(_lib, name), name
     assert "cells" in Sampler.last_step.__doc__
+
+
+def test_the_restatement_agrees_with_the_rules_of_the_library(tmp_path):
+    """tests/dispatch_probe.cc prints the rules of csrc/cpm_dispatch.h themselves (a host header: no HIP, no GPU) for every Z in
+    2..32768 and every mean in 1..1024; each line must be what dispatch_cells.py says"""
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler found")
+    exe = str(tmp_path / "dispatch_probe")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "dispatch_probe.cc")], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
+    rows = [[int(v) for v in line.split()[1:]] for line in out]
+    z_rows, m_rows, l_rows = ([r for line, r in zip(out, rows) if line[0] == k] for k in "ZML")
+    assert len(z_rows) + len(m_rows) + len(l_rows) == len(out)
+    kinds = (D.SAMPLE, D.HOUR, D.HOUR_PF, D.DAY, D.HEAVY_K)
+    assert [r[0] for r in z_rows] == list(range(2, 32769)) and [r[0] for r in m_rows] == list(range(1, 1025))
+    for r in z_rows:
+        Z, need = r[0], D.need_of(r[0])
+        p = D.place_shape(Z)
+        assert r[1:] == [int(D.pack_row_fits(Z)), need, *(D.ladder_nq(k, need) for k in kinds), D.zpg_of(Z), D.zpg_of(Z, True), D.idbits(Z),
+                         D.idbits(Z, True), p.pb, p.kruns, p.bpg, int(D.fused_shape_ok(Z)), int(D.fused_shape_ok(Z, True))], Z
+    for mean, narrow, wide in m_rows:
+        assert (narrow, wide) == (D.cpt_narrow(mean), D.cpt_wide(mean)), mean
+    assert {r[0]: (r[1], tuple(r[2:])) for r in l_rows} == {k: (D.SPARSE_NQ[k], D.LADDERS[k]) for k in kinds}
+    # the bands of the probe's own NQ column: the edges test_band_edges_of_the_sampler_ladder pins
+    bands = {}
+    for r in z_rows:
+        if r[1]:
+            lo, hi = bands.get(r[3], (r[0], r[0]))
+            bands[r[3]] = (min(lo, r[0]), max(hi, r[0]))
+    assert bands == D.nq_bands()
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the cases
