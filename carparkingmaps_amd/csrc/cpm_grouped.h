@@ -291,9 +291,13 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x)
 __device__ __forceinline__ bool any64(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 // p[i] = v with the address as uniform base + 32-bit BYTE offset (i x 4 B < 2^32: a bucket region): the store takes the base from
 // scalar registers and one VGPR instead of a 64-bit address pair built per store
+// (POLICY: next_store's, below -- the stayers' ids are read by the next launch only)
+template <int POLICY, typename W>
+__device__ __forceinline__ void next_store(W v, W *p);
+template <int POLICY = 0>
 __device__ __forceinline__ void put32(uint32_t *p, uint32_t i, uint32_t v)
 {
-    *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(p) + (i << 2)) = v;
+    next_store<POLICY>(v, reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(p) + (i << 2)));
 }
 // lane 0's value to the whole wave (every lane active): one v_readfirstlane instead of the LDS crossbar of __shfl
 __device__ __forceinline__ uint32_t from_lane0(uint32_t v) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(v))); }
@@ -615,7 +619,9 @@ typedef __attribute__((address_space(3))) const uint16_t lds_cu16;
 // Counts in vmcnt like any load.  Every wave issues exactly NQ instructions, unpredicated (so that the count is known at
 // compile time and the wave can wait for its OLDER id loads alone with s_waitcnt vmcnt(NQ)): chunk k = 64 pieces from
 // min(64 k, pieces - 64); chunks past the end repeat the last one (same bytes to the same LDS words).  pieces >= 64.
-template <int BLOCK, int NQ>
+// AUX: the cache-policy bits of the load (0 default, 2 nt: policy_pack_aux).  A row pack is read once per hour -- the next reader of
+// the same bytes comes 1.8 GB of table traffic later -- so the hourly kernels that were measured with it stream it non-temporal.
+template <int BLOCK, int NQ, int AUX = 0>
 __device__ __forceinline__ void pack_dma(uint32_t *lds, const uint32_t *pack, int pieces, int tid)
 {
     const int lane = tid & 63, wave = tid >> 6;
@@ -624,7 +630,7 @@ __device__ __forceinline__ void pack_dma(uint32_t *lds, const uint32_t *pack, in
         const int p0 = min((m * (BLOCK / 64) + wave) * 64, pieces - 64);
         // (uniform base + 32-bit byte offset: the load takes the base from scalar registers and one VGPR, no 64-bit add per piece)
         __builtin_amdgcn_global_load_lds(reinterpret_cast<const char *>(pack) + (static_cast<uint32_t>(p0 + lane) << 4),
-                                         (__attribute__((address_space(3))) void *)(lds + 4 * p0), 16, 0, 0);
+                                         (__attribute__((address_space(3))) void *)(lds + 4 * p0), 16, 0, AUX);
     }
 }
 
@@ -781,7 +787,12 @@ constexpr int kHeavyCap = 65536;  // work items (chunks of heavy buckets) the he
 #ifdef CPM_DIAGNOSTIC
 __device__ unsigned long long *g_place_stamps = nullptr;  // [blocks][8], set by cpm_diag_place_stamps
 #define CPM_STAMP_DECL_IMPL unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#ifdef CPM_STAMP_REALTIME  // (the constant 100 MHz counter, one for the whole chip, instead of the shader clock, which follows the load: spans in
+                           //  microseconds that can be set against a dispatch's duration; << 8: some stamps carry tags in their low bits)
+#define CPM_STAMP_IMPL(k) st_[k] = __builtin_amdgcn_s_memrealtime() << 8
+#else
 #define CPM_STAMP_IMPL(k) st_[k] = __builtin_amdgcn_s_memtime()
+#endif
 #define CPM_STAMP_FLUSH_IMPL                                                                          \
     do {                                                                                              \
         if (threadIdx.x == 0 && g_place_stamps) {                                                     \
@@ -844,6 +855,74 @@ __device__ __forceinline__ void hand_store(uint32_t *p, uint32_t v)
     if constexpr (FUSED) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else *p = v;
 }
+// A store of a bucket id that only the NEXT launch reads (the stayers of grouped_sample_body, the arrivals of grouped_place_body):
+// the cache policy of the store instruction, nothing else -- the next launch cannot tell the arms apart.
+//   kStorePlain    global_store_dword           the line stays dirty in this XCD's L2 until it is evicted or the launch ends
+//   kStoreThrough  global_store_dword ... sc1   agent-scope write-through (what hand_store<true> emits): on its way to memory at once
+//   kStoreNt       global_store_dword ... nt    non-temporal
+// The policy is a parameter of the two bodies, one field per store site (store_policy), so that every form of the hour takes what
+// was measured to pay for it; the forms nobody measured it for keep plain stores.  MEASURED (S4k, profiles/store_policy_notes.md):
+// plain wins at every site, in the one-launch hour and in the two launches per hour -- sc1 on the placing blocks' stores +17 % on the
+// resample, nt +13 %, sc1 on the stayers alone +1.4 %: an id store that leaves the L2 on its own is a partial-line write per few
+// dwords, and a block's exit waits for it -- so the arms stay -D selectable and the constants below say plain.  What paid is the other
+// direction: nt on the row pack's LDS-DMA (pack_dma), 76 MB per hour read once, which then stop displacing ids and runs from the L2.
+constexpr int kStorePlain = 0, kStoreThrough = 1, kStoreNt = 2;
+template <int POLICY, typename W>
+__device__ __forceinline__ void next_store(W v, W *p)  // (the value first, as an assignment evaluates it: the plain arm is the code `*p = v` was)
+{
+    static_assert(POLICY == kStorePlain || POLICY == kStoreThrough || POLICY == kStoreNt, "plain, sc1 or nt");
+    if constexpr (POLICY == kStoreThrough) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (POLICY == kStoreNt) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+// The policies of one form of the hour in one template argument: two bits per store site -- the stayers (sampler), the sorted
+// write-out, the medium runs and the surplus (placing) -- and one for the row pack's LDS-DMA (1: nt, the pack is read once per hour).
+__host__ __device__ constexpr int store_policy(int stay, int sorted, int medium, int surplus, int pack_nt)
+{
+    return stay | sorted << 2 | medium << 4 | surplus << 6 | pack_nt << 8;
+}
+__host__ __device__ constexpr int policy_stay(int p) { return p & 3; }
+__host__ __device__ constexpr int policy_sorted(int p) { return (p >> 2) & 3; }
+__host__ __device__ constexpr int policy_medium(int p) { return (p >> 4) & 3; }
+__host__ __device__ constexpr int policy_surplus(int p) { return (p >> 6) & 3; }
+__host__ __device__ constexpr int policy_pack_aux(int p) { return ((p >> 8) & 1) ? 2 : 0; }  // (aux bit 1 of global_load_lds: nt)
+// Per site and form, -D selectable for A/B libraries (tools/build_variants.sh); the product is compiled with the constants below.
+// HOUR: k_grouped_hour.  PAIR: the two launches per hour, k_grouped_sample<..., GROUPED> / k_grouped_place.  ZERO: k_grouped_zero.
+#ifndef CPM_HOUR_STAY
+#define CPM_HOUR_STAY 0
+#endif
+#ifndef CPM_HOUR_SORTED
+#define CPM_HOUR_SORTED 0
+#endif
+#ifndef CPM_HOUR_MEDIUM
+#define CPM_HOUR_MEDIUM 0
+#endif
+#ifndef CPM_HOUR_SURPLUS
+#define CPM_HOUR_SURPLUS 0
+#endif
+#ifndef CPM_HOUR_PACK_NT
+#define CPM_HOUR_PACK_NT 1  // (S4k: 0.7936 -> 0.7565 ms per resample; every store arm other than plain lost: profiles/store_policy_notes.md)
+#endif
+#ifndef CPM_PAIR_STAY
+#define CPM_PAIR_STAY 0
+#endif
+#ifndef CPM_PAIR_SORTED
+#define CPM_PAIR_SORTED 0
+#endif
+#ifndef CPM_PAIR_SURPLUS
+#define CPM_PAIR_SURPLUS 0
+#endif
+#ifndef CPM_PAIR_PACK_NT
+#define CPM_PAIR_PACK_NT 1  // (S4k in two launches per hour: 0.8657 -> 0.8149 ms per resample)
+#endif
+#ifndef CPM_ZERO_STORE
+#define CPM_ZERO_STORE 0
+#endif
+// Sparse row packs (cpm_dataset.h) keep the default policy on their stream: an hour's packs are a few MB, not 76, and the
+// Melbourne-shaped hour (Z = 2,357 x 1,000, one launch per hour) LOST 3.3 % with nt (0.5572 -> 0.5757 ms per resample).
+__host__ __device__ constexpr int policy_dense_pack_only(int p, bool sparse) { return sparse ? (p & 0xFF) : p; }
+constexpr int kPolicyHour = store_policy(CPM_HOUR_STAY, CPM_HOUR_SORTED, CPM_HOUR_MEDIUM, CPM_HOUR_SURPLUS, CPM_HOUR_PACK_NT);
+constexpr int kPolicyPair = store_policy(CPM_PAIR_STAY, CPM_PAIR_SORTED, 0, CPM_PAIR_SURPLUS, CPM_PAIR_PACK_NT);  // (no medium runs outside the one-launch hour)
 template <bool FUSED>
 __device__ __forceinline__ uint32_t hand_load(const uint32_t *p)
 {
@@ -873,7 +952,8 @@ __device__ __forceinline__ void hand_off_done(uint32_t *done_chunk, int tid)
 // STAGED (the batched sampler, cpm_batch.h): the caller has put the zone's pack into `pack` already -- no LDS-DMA here, and the ids
 // are waited for with vmcnt(0) (nothing of this body is in flight behind them).  The pack is read behind the barrier of the first
 // pass, which follows that wait in every wave.
-template <int BLOCK, int CPT, int NQ, bool GROUPED, bool FUSED, bool WAIT = false, bool SPARSE = false, bool STAGED = false>
+// POLICY (store_policy): how the stayers' ids are stored and the pack is streamed; 0 = plain stores, default loads.
+template <int BLOCK, int CPT, int NQ, bool GROUPED, bool FUSED, bool WAIT = false, bool SPARSE = false, bool STAGED = false, int POLICY = 0>
 __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const int z, uint32_t *pack, SampleLds &sl, uint32_t *done_chunk,
                                                     const uint32_t *wait_on = nullptr, uint32_t wait_need = 0)
 {
@@ -967,7 +1047,7 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
         if constexpr (STAGED) {
             wait_ids<CPT + 1, 0>(id);
         } else {
-            pack_dma<BLOCK, NQ>(pack, a.rp_t + static_cast<size_t>(z) * rw, pieces, tid);
+            pack_dma<BLOCK, NQ, policy_pack_aux(POLICY)>(pack, a.rp_t + static_cast<size_t>(z) * rw, pieces, tid);
             wait_ids<CPT + 1, NQ>(id);
         }
     }
@@ -1078,7 +1158,7 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
                 for (int c = 0; c < K; ++c) rank[c] = drive[c] ? atomicAdd(&gb[gdiv_group_t<SPARSE>(a.gdiv, dest[c])], 1u) : 0u;
 #pragma unroll
                 for (int c = 0; c < K; ++c) {
-                    if (valid[c] & !drive[c]) put32(stay_out, bS + static_cast<uint32_t>(__popcll(mS[c] & below)), id[c]);
+                    if (valid[c] & !drive[c]) put32<policy_stay(POLICY)>(stay_out, bS + static_cast<uint32_t>(__popcll(mS[c] & below)), id[c]);
                     bS += static_cast<uint32_t>(__popcll(mS[c]));
                 }
 #pragma unroll
@@ -1185,7 +1265,7 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
             uint32_t b1 = 0;
             if (lane == 0 && m1) b1 = atomicAdd(&s_nstay, static_cast<uint32_t>(__popcll(m1)));
             b1 = from_lane0(b1);
-            if (valid1 & !drive1) stay_out[b1 + static_cast<uint32_t>(__popcll(m1 & below))] = idx;
+            if (valid1 & !drive1) next_store<policy_stay(POLICY)>(idx, &stay_out[b1 + static_cast<uint32_t>(__popcll(m1 & below))]);
             if (drive1) {
                 const uint32_t g = gdiv_group_t<SPARSE>(a.gdiv, dest1[0]);
                 const uint32_t rank = atomicAdd(&gb[g], 1u);
@@ -1250,7 +1330,7 @@ __global__ __launch_bounds__(BLOCK, CPM_WPS) CPM_SGPR_ATTR void k_grouped_sample
 {
     extern __shared__ uint32_t pack[];  // the zone's row pack: guide (u16), then Zq high words
     __shared__ SampleLds sl;
-    grouped_sample_body<BLOCK, CPT, NQ, GROUPED, false, false, SPARSE>(a, blockIdx.x, pack, sl, nullptr);
+    grouped_sample_body<BLOCK, CPT, NQ, GROUPED, false, false, SPARSE, false, GROUPED ? policy_dense_pack_only(kPolicyPair, SPARSE) : 0>(a, blockIdx.x, pack, sl, nullptr);
 }
 
 // The rest of the HEAVY buckets (real Uber Movement tables are peaky: a central zone can hold tens of times the mean, and one
@@ -1397,7 +1477,9 @@ __global__ __launch_bounds__(BLOCK, 4) void k_grouped_sample_heavy(GroupedArgs a
 
 // ------------------------------------------------------------------------------------------------ placing the drivers
 // Drivers of destination group g -> their buckets.  blockIdx = j * kGroups + g: the blocks of a group share blockIdx % 8 (one XCD,
-// one L2: all writes to a bucket merge there; speed only, never correctness).  Block (g, j) takes the group-g runs of the origin
+// one L2: all writes to a bucket merge there; speed only, never correctness -- and measured to be worth it: with the id stores written
+// through (sc1) or non-temporal instead, so that the launch ends with nothing dirty in that L2, the S4k resample is 13-17 % slower,
+// next_store above and profiles/store_policy_notes.md).  Block (g, j) takes the group-g runs of the origin
 // zones [j*zps, (j+1)*zps): 8 lanes per run, 2 x KDEEP entries per lane (16 x KDEEP of a run in registers).  Run lengths and run contents sit at addresses known up
 // front, so they are requested together.
 // Threads per block: 512 (128 origin zones per block, four blocks per CU; measured at S4k against 1024 x two per CU: 11.4 us against
@@ -1478,6 +1560,13 @@ __device__ __noinline__ uint32_t place_surplus_count(PlaceLds<PB, KRUNS, ZPG> &p
     return ltotal;
 }
 // the surplus entries straight to their buckets (tbins: the running position inside each bucket)
+// (its store policy follows from the form its parameters name -- the one-launch hour, the standalone placing kernel, or one of the
+//  forms that keep plain stores -- and is no parameter of its own: the symbol of an out-of-line function stays what it was)
+template <bool FUSED, bool SIGNAL, int TAG>
+__host__ __device__ constexpr int place_surplus_policy()
+{
+    return (FUSED && !SIGNAL) ? policy_surplus(kPolicyHour) : (!FUSED && !SIGNAL && TAG == 0) ? policy_surplus(kPolicyPair) : kStorePlain;
+}
 template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool SIGNAL, bool PERM = false, int TAG = 0>
 __device__ __noinline__ void place_surplus_out(PlaceLds<PB, KRUNS, ZPG> &pl, const uint32_t *D, int g, int zs0, int zs1, uint32_t scap, uint32_t idbits,
                                                int zg0, int nzl, uint32_t cap, uint32_t *__restrict__ ids_next, uint32_t ltotal)
@@ -1495,7 +1584,7 @@ __device__ __noinline__ void place_surplus_out(PlaceLds<PB, KRUNS, ZPG> &pl, con
             if (e0 + u * PB < ltotal) {
                 const uint32_t dl = w[u] >> idbits;
                 const uint32_t p = atomicAdd(&pl.tbins[dl], 1u);
-                if (p < cap && (!SIGNAL || dl < static_cast<uint32_t>(nzl))) ids_next[static_cast<size_t>(zg0 + dl) * cap + (cap - 1u - p)] = w[u] & idmask;
+                if (p < cap && (!SIGNAL || dl < static_cast<uint32_t>(nzl))) next_store<place_surplus_policy<FUSED, SIGNAL, TAG>()>(w[u] & idmask, &ids_next[static_cast<size_t>(zg0 + dl) * cap + (cap - 1u - p)]);
             }
     }
 }
@@ -1522,7 +1611,8 @@ constexpr uint32_t kFusedSpinLimit = 1u << 15;  // default number of polls: x (o
 // sampler workgroups of chunk j by POSITION in the launch.
 // TAG: the batched placing (cpm_batch.h, TAG 1) calls instances of the out-of-line helpers of its own, so that what the compiler infers
 // from their callers -- e.g. where the run pointers point -- stays that of the hourly kernels.
-template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool SIGNAL = false, bool PERM = false, int TAG = 0>
+// POLICY (store_policy): how the arrivals' ids are stored; 0 = plain stores.
+template <int PB, int KRUNS, int KDEEP, int ZPG, bool FUSED, bool SIGNAL = false, bool PERM = false, int TAG = 0, int POLICY = 0>
 __device__ __forceinline__ void grouped_place_body(const int g, const int j, PlaceLds<PB, KRUNS, ZPG> &pl, uint32_t *sorted_ids, const uint32_t *__restrict__ D,
                                                    const uint32_t *__restrict__ cntg, int zpg, int zps, int Z, uint32_t cap, uint32_t scap, uint32_t idbits,
                                                    uint32_t *__restrict__ cnt_a_next, uint32_t *__restrict__ ids_next, unsigned long long *status,
@@ -1758,7 +1848,7 @@ __device__ __forceinline__ void grouped_place_body(const int g, const int j, Pla
 #pragma unroll
         for (int u = 0; u < kOutBatch; ++u)
             if (i0 + u * kPlaceBlock < total && p[u] < cap && (!SIGNAL || dl[u] < static_cast<uint32_t>(nzl)))
-                ids_next[static_cast<size_t>(zg0 + dl[u]) * cap + (cap - 1u - p[u])] = idv[u];  // arrivals fill a region from its top
+                next_store<policy_sorted(POLICY)>(idv[u], &ids_next[static_cast<size_t>(zg0 + dl[u]) * cap + (cap - 1u - p[u])]);  // arrivals fill a region from its top
     }
     // ... the entries 32 .. 63 of the medium runs straight to their buckets (tbins: the running position behind the sorted ones) ...
     if constexpr (kMedium) {
@@ -1770,11 +1860,12 @@ __device__ __forceinline__ void grouped_place_body(const int g, const int j, Pla
                 if (static_cast<uint32_t>(d) < nx[k]) {
                     const uint32_t dl = x4[d] >> idbits;
                     const uint32_t p = atomicAdd(&tbins[dl], 1u);
-                    if (p < cap && (!SIGNAL || dl < static_cast<uint32_t>(nzl))) ids_next[static_cast<size_t>(zg0 + dl) * cap + (cap - 1u - p)] = x4[d] & idmask;
+                    if (p < cap && (!SIGNAL || dl < static_cast<uint32_t>(nzl))) next_store<policy_medium(POLICY)>(x4[d] & idmask, &ids_next[static_cast<size_t>(zg0 + dl) * cap + (cap - 1u - p)]);
                 }
         }
     }
     // ... and the surplus of the long runs straight to their buckets
+    static_assert(policy_surplus(POLICY) == place_surplus_policy<FUSED, SIGNAL, TAG>(), "the surplus helper and the body that calls it name the same policy");
     if (any_long) place_surplus_out<PB, KRUNS, KDEEP, ZPG, FUSED, SIGNAL, PERM, TAG>(pl, D, g, zs0, zs1, scap, idbits, zg0, nzl, cap, ids_next, ltotal);
     CPM_PSTAMP(7);
 #if defined(CPM_DIAGNOSTIC) && !defined(CPM_STAMP_SAMPLER) && !defined(CPM_STAMP_BOTH)
@@ -1806,7 +1897,7 @@ __global__ __launch_bounds__(PB) void k_grouped_place(const uint32_t *__restrict
 {
     __shared__ PlaceLds<PB, KRUNS, kMaxZonesPerGroup> pl;
     extern __shared__ uint32_t sorted_ids[];  // [kSlots] ids in destination order, then [kSlots] u16: their zone inside the group
-    grouped_place_body<PB, KRUNS, KDEEP, kMaxZonesPerGroup, false>(blockIdx.x % kGroups, blockIdx.x / kGroups, pl, sorted_ids, D, cntg, zpg, zps, Z, cap,
+    grouped_place_body<PB, KRUNS, KDEEP, kMaxZonesPerGroup, false, false, false, 0, kPolicyPair>(blockIdx.x % kGroups, blockIdx.x / kGroups, pl, sorted_ids, D, cntg, zpg, zps, Z, cap,
                                                                     scap, idbits, cnt_a_next, ids_next, status, nullptr, 0u, 0u);
 }
 
@@ -1885,14 +1976,14 @@ __global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_groupe
         }
     }
     if (z >= 0) {
-        grouped_sample_body<kFusedThreads, CPT, NQ, true, true, false, SPARSE>(
+        grouped_sample_body<kFusedThreads, CPT, NQ, true, true, false, SPARSE, false, policy_dense_pack_only(kPolicyHour, SPARSE)>(
             a, z, dyn, u.s, a.done_t + static_cast<size_t>((PERM ? static_cast<int>(blockIdx.x) : z) / kFusedChunk) * kDoneStride);
     } else {
         const uint32_t need = static_cast<uint32_t>(min(kFusedChunk, a.Z - j * kFusedChunk));
 #ifdef CPM_PLACE_PRIO
         __builtin_amdgcn_s_setprio(CPM_PLACE_PRIO);
 #endif
-        grouped_place_body<kFusedThreads, kFusedKruns, kFusedKdeep, kFusedZpg, true, false, PERM>(
+        grouped_place_body<kFusedThreads, kFusedKruns, kFusedKdeep, kFusedZpg, true, false, PERM, 0, kPolicyHour>(
             g, j, u.p, dyn, a.D, a.cntg, static_cast<int>(gdiv_zpg(a.gdiv)), kFusedChunk, a.Z, a.cap, a.scap, a.idbits, a.cnt_next + a.Z, a.ids_next, a.rare->status,
             a.done_t + static_cast<size_t>(j) * kDoneStride, need, a.spin_limit, nullptr, PERM ? a.perm_t : nullptr, SPARSE);
     }
@@ -2697,8 +2788,8 @@ __global__ __launch_bounds__(256) void k_grouped_zero(unsigned long long *__rest
                                                       GroupedRare *__restrict__ rare, GroupedRare rare_now, GroupedArgs *__restrict__ hours, GroupedDay day)
 {
     const size_t stride = static_cast<size_t>(gridDim.x) * 256;
-    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < nwords; i += stride) counts[i] = 0ull;
-    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < ncnt; i += stride) cnt[i] = 0u;  // (the arrival counts are added to)
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < nwords; i += stride) next_store<CPM_ZERO_STORE>(0ull, &counts[i]);
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < ncnt; i += stride) next_store<CPM_ZERO_STORE>(0u, &cnt[i]);  // (the arrival counts are added to)
     if (blockIdx.x == 0) {
         if (threadIdx.x < 2) maxn[threadIdx.x] = 0u;
         if (threadIdx.x == 0) *rare = rare_now;  // (what the rare branches of this run's kernels read)

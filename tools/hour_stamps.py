@@ -36,13 +36,20 @@ s.resample(0x5EEDCA125)
 buf = np.zeros((nb, 8), dtype=np.uint64)
 _lib.check(L.cpm_diag_place_stamps(s._h, buf.ctypes.data_as(C.c_void_p), nb))
 t = buf.astype(np.int64)
+GAP = 200_000
+if os.environ.get("CPM_STAMP_RT") == "1":   # library built with -DCPM_STAMP_REALTIME too: the constant 100 MHz counter (<< 8), one clock for the whole chip
+    t >>= 8
+    GAP = 2_000
+    live = t[t[:, 0] != 0]
+    print(f"100 MHz counter: first block's first stamp -> last block's last stamp {(live[:, 7].max() - live[:, 0].min()) / 100:.2f} us "
+          f"(set against the dispatch's duration in rocprofv3 --kernel-trace; the ticks below are 10 ns each)")
 role = np.r_[np.ones(npl, dtype=int), np.zeros(zr, dtype=int)] if PF else np.r_[np.zeros(zr, dtype=int), np.ones(nb - zr, dtype=int)]   # 0 sampler workgroup, 1 placing block
 ok = t[:, 0] != 0
 print(f"blocks with stamps: {int(ok.sum())} of {nb} (samplers {int((ok & (role == 0)).sum())}, placing {int((ok & (role == 1)).sum())})")
 idx = np.flatnonzero(ok)
 order = np.argsort(t[idx, 0])
 idx = idx[order]
-cuts = np.flatnonzero(np.diff(t[idx, 0]) > 200_000) + 1
+cuts = np.flatnonzero(np.diff(t[idx, 0]) > GAP) + 1
 pct = lambda v, q: int(np.percentile(v, q))
 for c, (lo, hi) in enumerate(zip(np.r_[0, cuts], np.r_[cuts, len(idx)])):
     ii = idx[lo:hi]
