@@ -39,6 +39,16 @@ STAYS_SYMBOLS = ["cpm_resample_stays", "cpm_resample_stays_dev"]
 # every symbol include/cpm_paths.h declares (checked by tests/test_paths.py); a header and a list of its own, likewise
 PATHS_SYMBOLS = ["cpm_resample_paths", "cpm_resample_paths_dev", "cpm_paths_expand_dev"]
 
+# every symbol include/cpm_charge.h declares (checked by tests/test_charge.py); a header and a list of its own, likewise
+CHARGE_SYMBOLS = ["cpm_resample_charge", "cpm_resample_charge_dev"]
+
+
+class ChargeParamsC(C.Structure):
+    """cpm_charge_params of include/cpm_charge.h"""
+    _fields_ = [("capacity_wh", C.c_uint32), ("power_wh", C.c_uint32), ("initial_wh", C.c_uint32), ("wh_per_km", C.c_double),
+                ("zone_power_wh", C.c_void_p), ("soc_in", C.c_void_p)]
+
+
 # every symbol include/cpm_objectives.h declares (checked by tests/test_objectives.py); a header and a list of its own, likewise
 OBJECTIVES_SYMBOLS = ["cpm_set_measured", "cpm_objectives_dev"]
 
@@ -87,6 +97,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_flows_csr.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_stays.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_paths.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_charge.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_objectives.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
@@ -171,9 +182,11 @@ def load():
     L.cpm_resample_paths.argtypes = [vp, u64, u32, vp, vp, vp, vp]
     L.cpm_resample_paths_dev.argtypes = [vp, u64, u32, vp, vp]
     L.cpm_paths_expand_dev.argtypes = [vp, u64, u32, vp, vp, vp]
+    L.cpm_resample_charge.argtypes = [vp, u64, u32, C.POINTER(ChargeParamsC), vp, vp, vp, vp, vp, vp, vp]
+    L.cpm_resample_charge_dev.argtypes = [vp, u64, u32, C.POINTER(ChargeParamsC), vp, vp, vp, vp, vp]
     L.cpm_set_measured.argtypes = [vp, vp]
     L.cpm_objectives_dev.argtypes = [vp, vp, i32, i64, vp, vp]
-    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + OBJECTIVES_SYMBOLS:
+    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

@@ -17,12 +17,14 @@
 #include "../../include/cpm_flows_csr.h"
 #include "../../include/cpm_stays.h"
 #include "../../include/cpm_paths.h"
+#include "../../include/cpm_charge.h"
 #include "../../include/cpm_objectives.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
 #include "cpm_paths.h"
+#include "cpm_charge.h"
 #include "cpm_tables.h"
 #include "cpm_exact.h"
 #include "cpm_grouped.h"
@@ -154,6 +156,16 @@ struct cpm_ctx {
     int64_t stay_last_cap = 0;
     int32_t *d_stays = nullptr;        // [T][Z][T]
     int32_t *d_stay_parked = nullptr;  // [Z][T]
+    // charge (include/cpm_charge.h): the per-car side array of every charge call, and the blocking call's arrays
+    uint2 *d_ebat = nullptr;           // [ebat_cap] {since << 24 | zone, Wh} (csrc/cpm_charge.h)
+    int64_t ebat_cap = 0;
+    double *d_dist_rows = nullptr;     // [Z][Z] the distance matrix origin-major, built on first use, stale wherever d_dist is replaced
+    bool dist_rows_valid = false;
+    int64_t *d_chg_load = nullptr;     // [2][Z][T] charge | used
+    int32_t *d_chg_short = nullptr;    // [Z][T]
+    uint32_t *d_chg_zone_power = nullptr;  // [Z]
+    uint32_t *d_chg_soc = nullptr;     // [2][chg_soc_cap] soc_in | soc_out
+    int64_t chg_soc_cap = 0;
     // per-car day records (include/cpm_paths.h): the blocking call's array, kept from its first use, and the columns
     // cpm_paths_expand_dev writes where the caller wants no matrix
     uint32_t *d_paths = nullptr;       // [T][n]
@@ -759,9 +771,13 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     cpm::FlowsDest &fd = side.flows;
     cpm::StaysDest &sd = side.stays;
     const cpm::PathsDest &pd = side.paths;
+    cpm::ChargeDest &cd = side.charge;
     int32_t *const d_flows = fd.dense;
     if (sd.any() && c->T > cpm::kStaysMaxT) return fail(CPM_ERR_ARG, "stays: T = %lld, the per-car word keeps an hour in 8 bits (T <= %d)", (long long)c->T, cpm::kStaysMaxT);
     if (sd.any() && c->Z > static_cast<int64_t>(cpm::kStayZoneMask)) return fail(CPM_ERR_ARG, "stays: Z = %lld, the per-car word keeps a zone in 24 bits", (long long)c->Z);
+    if (cd.any() && c->T > cpm::kStaysMaxT) return fail(CPM_ERR_ARG, "charge: T = %lld, the per-car word keeps an hour in 8 bits (T <= %d)", (long long)c->T, cpm::kStaysMaxT);
+    if (cd.any() && c->Z > static_cast<int64_t>(cpm::kStayZoneMask)) return fail(CPM_ERR_ARG, "charge: Z = %lld, the per-car word keeps a zone in 24 bits", (long long)c->Z);
+    if (cd.any() && !c->have_dist) return fail(CPM_ERR_STATE, "charge: no distance matrix (cpm_set_datamatrix with dist, cpm_set_distance or cpm_set_distance_from_centroids)");
     if (!c->have_pdrive || !c->have_cdf) return fail(CPM_ERR_STATE, "resample: p_drive / p_dest not set");
     if (!c->have_state) return fail(CPM_ERR_STATE, "resample: no car state (cpm_init_states / cpm_set_state)");
     {
@@ -793,7 +809,31 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         if (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED)
             HIP_TRY(hipMemsetAsync(sd.stays, 0, sizeof(int32_t) * static_cast<size_t>(c->T) * c->Z * c->T, c->stream));
     }
+    if (cd.any()) {  // (k_charge_cars adds to `used` and `short`, k_grouped_charge writes every word itself; `charge` is zeroed by k_charge_init)
+        const size_t zt = static_cast<size_t>(c->Z) * c->T;
+        if (c->n == 0) HIP_TRY(hipMemsetAsync(cd.charge, 0, sizeof(int64_t) * zt, c->stream));
+        if (c->n == 0 || kernel != CPM_KERNEL_ZONE_GROUPED) {
+            HIP_TRY(hipMemsetAsync(cd.used, 0, sizeof(int64_t) * zt, c->stream));
+            HIP_TRY(hipMemsetAsync(cd.shrt, 0, sizeof(int32_t) * zt, c->stream));
+        }
+    }
     if (c->n == 0) return CPM_OK;
+    if (cd.any()) {  // the side array: every car where the day began with its initial charge, at the start of every attempt
+        if (c->ebat_cap < c->n) {
+            dfree(c->d_ebat);
+            c->d_ebat = nullptr;
+            c->ebat_cap = 0;
+            HIP_TRY(hipMalloc(&c->d_ebat, sizeof(uint2) * static_cast<size_t>(c->n)));
+            c->ebat_cap = c->n;
+        }
+        cd.ebat = c->d_ebat;
+        // the origin's distances: a row of the context's origin-major copy of the distance matrix, built once per matrix
+        if (!c->d_dist_rows) HIP_TRY(hipMalloc(&c->d_dist_rows, sizeof(double) * static_cast<size_t>(c->Z) * c->Z));
+        if (!c->dist_rows_valid) HIP_TRY(cpm::charge_launch_dist_rows(c->stream, c->d_dist, static_cast<int>(c->Z), c->d_dist_rows));
+        c->dist_rows_valid = true;
+        cd.dist = c->d_dist_rows;
+        HIP_TRY(cpm::charge_launch_init(c->stream, c->d_zone0, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), cd));
+    }
     if (sd.any()) {  // the side array: every car "here since the day began", at the start of every attempt
         if (c->stay_last_cap < c->n) {
             dfree(c->d_stay_last);
@@ -807,8 +847,9 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     }
     // the stays still open at the end of the day: behind the last hour of whichever family ran
     auto parked_pass = [&](int32_t rc_run) -> int32_t {
-        if (rc_run != CPM_OK || !sd.any()) return rc_run;
-        HIP_TRY(cpm::stays_launch_parked(c->stream, c->d_zone0, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), sd));
+        if (rc_run != CPM_OK) return rc_run;
+        if (sd.any()) HIP_TRY(cpm::stays_launch_parked(c->stream, c->d_zone0, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), sd));
+        if (cd.any()) HIP_TRY(cpm::charge_launch_close(c->stream, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), cd));  // (and the charging of the stays still open)
         return CPM_OK;
     };
     if (fd.csr() && kernel != CPM_KERNEL_ZONE_GROUPED) {  // (k_flows_cars adds to a dense hour block, k_flows_csr_from_dense takes it apart)
@@ -861,6 +902,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
             if (rc != CPM_OK) return rc;
         }
         if (sd.any()) HIP_TRY(cpm::stays_launch_cars(c->stream, nullptr, zin, nullptr, out, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), t, sd));
+        if (cd.any()) HIP_TRY(cpm::charge_launch_cars(c->stream, nullptr, zin, nullptr, out, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), t, c->cars, seed, cd));
     }
     // the per-car record of the day (cpm_paths.h): d_rec is that record, hour by hour in car order
     if (pd.any()) HIP_TRY(hipMemcpyAsync(pd.paths, c->d_rec, sizeof(uint32_t) * static_cast<size_t>(c->T) * c->n, hipMemcpyDeviceToDevice, c->stream));
@@ -1252,6 +1294,12 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_paths);
     dfree(c->d_expand_cols);
     dfree(c->d_stay_parked);
+    dfree(c->d_ebat);
+    dfree(c->d_dist_rows);
+    dfree(c->d_chg_load);
+    dfree(c->d_chg_short);
+    dfree(c->d_chg_zone_power);
+    dfree(c->d_chg_soc);
     dfree(c->d_counts);
     dfree(c->d_err);
     c->zx.release();
@@ -1474,6 +1522,7 @@ int32_t cpm_set_datamatrix(cpm_ctx *c, const double *datamatrix, const double *d
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_dmat = true;
     if (dist) c->have_dist = true;
+    if (dist) c->dist_rows_valid = false;
     return CPM_OK;
 }
 
@@ -1633,6 +1682,7 @@ int32_t cpm_set_distance_from_centroids(cpm_ctx *c, const double *centroid_lat, 
     dfree(d_ll);
     if (e != hipSuccess) return fail(CPM_ERR_HIP, "distance matrix: %s", hipGetErrorString(e));
     c->have_dist = true;
+    c->dist_rows_valid = false;
     c->pdrive_mean_valid = false;
     return CPM_OK;
 }
@@ -1646,6 +1696,7 @@ int32_t cpm_set_distance(cpm_ctx *c, const double *dist)
     HIP_TRY(hipMemcpyAsync(c->d_dist, dist, dbytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_dist = true;
+    c->dist_rows_valid = false;
     c->pdrive_mean_valid = false;
     return CPM_OK;
 }
@@ -1797,6 +1848,7 @@ int32_t cpm_synth_datamatrix(cpm_ctx *c, uint64_t table_seed, double density)
     if (!c->d_dm) HIP_TRY(hipMalloc(&c->d_dm, sizeof(double) * cells * 2));
     if (!c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, sizeof(double) * c->Z * c->Z));
     c->have_dmat = c->have_dist = false;
+    c->dist_rows_valid = false;
     c->tt_valid = false;
     c->tts_valid = false;
     c->ds_valid = false;
@@ -2084,6 +2136,104 @@ int32_t cpm_resample_stays(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     //  last one enqueued is the one returned)
     HIP_TRY(hipMemcpyAsync(stays_out, c->d_stays, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(parked_out, c->d_stay_parked, sizeof(int32_t) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ charge (include/cpm_charge.h)
+// the scalar parameters, checked, and the caller's arrays into a ChargeDest (the side array and the distance matrix: resample_enqueue)
+static int32_t charge_dest(const cpm_charge_params *p, cpm::ChargeDest &cd)
+{
+    if (!p) return fail(CPM_ERR_ARG, "null params");
+    if (p->capacity_wh < 1) return fail(CPM_ERR_ARG, "charge: capacity_wh = 0");
+    if (p->initial_wh > p->capacity_wh) return fail(CPM_ERR_ARG, "charge: initial_wh = %u above capacity_wh = %u", p->initial_wh, p->capacity_wh);
+    if (!(p->wh_per_km >= 0.0) || !(p->wh_per_km <= 1.7976931348623157e308)) return fail(CPM_ERR_ARG, "charge: wh_per_km = %g is not finite and >= 0", p->wh_per_km);
+    cd.capacity = p->capacity_wh;
+    cd.power = p->power_wh;
+    cd.initial = p->initial_wh;
+    cd.wh_per_km = p->wh_per_km;
+    cd.zone_power = p->zone_power_wh;
+    cd.soc_in = p->soc_in;
+    return CPM_OK;
+}
+
+int32_t cpm_resample_charge_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, const cpm_charge_params *params, void *d_counts, void *d_charge, void *d_used,
+                                void *d_short, void *d_soc)
+{
+    CTX_TRY(c);
+    if (!d_counts) return fail(CPM_ERR_ARG, "null d_counts");
+    if (!d_charge) return fail(CPM_ERR_ARG, "null d_charge");
+    if (!d_used) return fail(CPM_ERR_ARG, "null d_used");
+    if (!d_short) return fail(CPM_ERR_ARG, "null d_short");
+    cpm::SideDest side;
+    int32_t rc = charge_dest(params, side.charge);
+    if (rc != CPM_OK) return rc;
+    side.charge.charge = static_cast<int64_t *>(d_charge);
+    side.charge.used = static_cast<int64_t *>(d_used);
+    side.charge.shrt = static_cast<int32_t *>(d_short);
+    side.charge.soc = static_cast<uint32_t *>(d_soc);
+    return resample_enqueue(c, seed, flags, static_cast<int64_t *>(d_counts), side);
+}
+
+int32_t cpm_resample_charge(cpm_ctx *c, uint64_t seed, uint32_t flags, const cpm_charge_params *params, int64_t *parking, int64_t *driving,
+                            int64_t *sum_tt_q16, int64_t *charge_out, int64_t *used_out, int32_t *short_out, uint32_t *soc_out)
+{
+    CTX_TRY(c);
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
+    if (!charge_out) return fail(CPM_ERR_ARG, "null charge_out");
+    if (!used_out) return fail(CPM_ERR_ARG, "null used_out");
+    if (!short_out) return fail(CPM_ERR_ARG, "null short_out");
+    cpm::SideDest side;
+    cpm::ChargeDest &cd = side.charge;
+    {
+        int32_t rc_p = charge_dest(params, cd);
+        if (rc_p != CPM_OK) return rc_p;
+    }
+    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
+        cpm_ctx *c;
+        int saved;
+        ~KernelGuard() { c->kernel = saved; }
+    } kernel_guard{c, c->kernel};
+    {
+        int32_t rc_ivp = finish_ivp(c);
+        if (rc_ivp != CPM_OK) return rc_ivp;
+    }
+    const size_t zt = static_cast<size_t>(c->Z * c->T), n = static_cast<size_t>(c->n);
+    if (!c->d_chg_load) HIP_TRY(hipMalloc(&c->d_chg_load, sizeof(int64_t) * 2 * std::max<size_t>(zt, 1)));
+    if (!c->d_chg_short) HIP_TRY(hipMalloc(&c->d_chg_short, sizeof(int32_t) * std::max<size_t>(zt, 1)));
+    if (!c->d_chg_zone_power) HIP_TRY(hipMalloc(&c->d_chg_zone_power, sizeof(uint32_t) * std::max<size_t>(c->Z, 1)));
+    if (c->chg_soc_cap < c->n || !c->d_chg_soc) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (a _dev step in flight may not read it, but nothing is freed under the stream)
+        dfree(c->d_chg_soc);
+        c->d_chg_soc = nullptr;
+        c->chg_soc_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_chg_soc, sizeof(uint32_t) * 2 * std::max<size_t>(n, 1)));
+        c->chg_soc_cap = std::max<int64_t>(c->n, 1);
+    }
+    // the caller's host arrays to the device (pageable memory: the copies have left the host when the calls return)
+    if (cd.zone_power) {
+        HIP_TRY(hipMemcpyAsync(c->d_chg_zone_power, cd.zone_power, sizeof(uint32_t) * c->Z, hipMemcpyHostToDevice, c->stream));
+        cd.zone_power = c->d_chg_zone_power;
+    }
+    if (cd.soc_in) {
+        if (n) HIP_TRY(hipMemcpyAsync(c->d_chg_soc, cd.soc_in, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
+        cd.soc_in = c->d_chg_soc;
+    }
+    cd.charge = c->d_chg_load;
+    cd.used = c->d_chg_load + zt;
+    cd.shrt = c->d_chg_short;
+    cd.soc = soc_out ? c->d_chg_soc + c->chg_soc_cap : nullptr;
+    int32_t rc = resample_blocking(c, seed, flags, side);
+    if (rc != CPM_OK) return rc;
+    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
+    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
+    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    // (the arrays of the attempt whose counts were fetched: every attempt fills the side array anew and writes every array whole, and
+    //  the last one enqueued is the one returned)
+    HIP_TRY(hipMemcpyAsync(charge_out, cd.charge, sizeof(int64_t) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(used_out, cd.used, sizeof(int64_t) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(short_out, cd.shrt, sizeof(int32_t) * zt, hipMemcpyDeviceToHost, c->stream));
+    if (soc_out && n) HIP_TRY(hipMemcpyAsync(soc_out, cd.soc, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
 }

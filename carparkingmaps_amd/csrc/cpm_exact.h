@@ -32,6 +32,7 @@
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
 #include "cpm_paths.h"
+#include "cpm_charge.h"
 
 namespace cpm {
 
@@ -452,6 +453,7 @@ int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, cons
     const FlowsDest &fd = side.flows;
     const StaysDest &sd = side.stays;
     const PathsDest &paths = side.paths;
+    const ChargeDest &cd = side.charge;
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP;
@@ -502,6 +504,8 @@ int32_t exact_run(ExactWork &w, hipStream_t stream, const double *d_pdrive, cons
         }
         // parking stays (cpm_stays.h): the same records; slot i is car ids[i] (zeroed `stays` and side array: the caller's)
         if (sd.any() && !ivp && (e = stays_launch_cars(stream, ids, nullptr, off, w.dest, n, Z, T, t, sd)) != hipSuccess) return hip_fail(e, "stays of the hour");
+        // the charge (cpm_charge.h): the same records (zeroed `used` / `short`, initialised `charge` and side array: the caller's)
+        if (cd.any() && !ivp && (e = charge_launch_cars(stream, ids, nullptr, off, w.dest, n, Z, T, t, cars, seed, cd)) != hipSuccess) return hip_fail(e, "charge of the hour");
         // the per-car record of the day (cpm_paths.h): the same records again, every slot to its car's word of the hour's row
         if (paths.any() && !ivp && (e = paths_launch_slots(stream, ids, w.dest, n, t, paths)) != hipSuccess) return hip_fail(e, "paths of the hour");
         if (ivp || t + 1 < T) {  // resampling: hour T's transition is sampled but never applied (src/resampling.jl:81-83)

@@ -41,6 +41,7 @@
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
 #include "cpm_paths.h"
+#include "cpm_charge.h"
 
 namespace cpm {
 
@@ -2814,6 +2815,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     const FlowsDest &fd = side.flows;
     const StaysDest &sd = side.stays;
     const PathsDest &pd = side.paths;
+    const ChargeDest &cd = side.charge;
     auto hip_fail = [&](hipError_t e, const char *what) {
         err = std::string(what) + ": " + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? CPM_ERR_NOMEM : CPM_ERR_HIP;
@@ -2839,19 +2841,23 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     // The per-car record of the day (cpm_paths.h, pd): from the same runs, a carry and a scatter per hour -- carry(t) reads the row
     // scatter(t - 1) wrote, so these too run in hour order, behind every hour or, over kept runs, T pairs at the end.  Paths alone
     // never ask for the kept form (the day launch apart).
+    // The charge (cpm_charge.h, cd): from the same runs, one launch per hour in hour order like the stays -- its side array carries every
+    // car's energy from hour to hour -- behind every hour or, over kept runs, T launches at the end.
     const bool flows = fd.any() && !ivp;
     const bool stays = sd.any() && !ivp;
     const bool paths = pd.any() && !ivp;
-    const bool history = (travel || (flows && (w.flows_kept || w.fused_day)) || ((stays || paths) && w.fused_day)) && !ivp && w.ensure_history();
+    const bool charge = cd.any() && !ivp;
+    const bool history = (travel || (flows && (w.flows_kept || w.fused_day)) || ((stays || paths || charge) && w.fused_day)) && !ivp && w.ensure_history();
     // hours t0 .. t0 + nt - 1 of the flows from the runs at D / cntg: grid (Z, 1) behind an hour, (Z, T) over the kept runs
     auto flows_hours = [&](const uint32_t *D, const uint32_t *cntg, size_t d_stride, size_t c_stride, int t0, int nt) -> int32_t {
         return fd.csr() ? flows_csr_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, d_stride, c_stride, t0, nt, fd, err)
                         : flows_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, d_stride, c_stride, t0, nt, fd.dense, err);
     };
-    // the stays and the paths of hour t from its runs at D / cntg: behind the hour's launches, or hour by hour over the kept runs
+    // the stays, the paths and the charge of hour t from its runs at D / cntg: behind the hour's launches, or hour by hour over the kept runs
     auto side_hour = [&](const uint32_t *D, const uint32_t *cntg, int t) -> int32_t {
         int32_t rc_side = stays ? stays_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, T, t, n, sd, err) : CPM_OK;
         if (rc_side == CPM_OK && paths) rc_side = paths_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, t, n, d_zone0, pd, err);
+        if (rc_side == CPM_OK && charge) rc_side = charge_launch_grouped(stream, D, cntg, Z, w.scap, w.idbits, w.zpg, T, t, n, cars, seed, cd, err);
         return rc_side;
     };
     const int G = tb.G;
@@ -2862,7 +2868,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     const bool shape = w.fused_ok && w.parts <= 1 && fused_shape_ok(Z, tb.Zq, G, tb.smap) && (!w.fused_auto || fused_pays(Z, tb.Zq, G, cu_count, tb.smap, mean));
     // ... and one launch for ALL hours that are applied (k_grouped_day): the IVP's T - 1, a resample's first T - 1 (hour T is sampled,
     // never applied: the plain form behind the placing of hour T - 1, k_grouped_hour_pf); hourly travel launches need hourly boundaries
-    const int day_n = (shape && w.fused_day && w.cap < (1u << kCntXccShift) && (!(travel || flows || stays || paths) || history)) ? (ivp ? hours : hours - 1) : 0;
+    const int day_n = (shape && w.fused_day && w.cap < (1u << kCntXccShift) && (!(travel || flows || stays || paths || charge) || history)) ? (ivp ? hours : hours - 1) : 0;
     const int nchunk = (Z + kFusedChunk - 1) / kFusedChunk;
     GroupedDay day{};
     auto hour_base = [&](GroupedArgs &a) {  // what all hours of a run share
@@ -2975,7 +2981,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         // hour T of a resample is sampled, never applied (src/resampling.jl:81-83): counts only -- unless its travel times are wanted,
         // which are computed from the runs
         const bool last_hour = !ivp && t + 1 == T;
-        const bool grouped = !last_hour || travel || flows || stays || paths || w.parts > 1;  // (heavy buckets: the grouped form splits them over workgroups, the plain and count-only ones walk them)
+        const bool grouped = !last_hour || travel || flows || stays || paths || charge || w.parts > 1;  // (heavy buckets: the grouped form splits them over workgroups, the plain and count-only ones walk them)
         uint32_t *cnt_next = w.cnt + static_cast<size_t>(t + 1) * 2 * Z;  // stayers; the arrivals Z words behind
         uint32_t *ids_next = (t & 1) ? w.idsB : w.idsA;
         GroupedArgs a;
@@ -3064,7 +3070,7 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         }
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "grouped zone hour launch");
     }
-    if ((stays || paths) && history) {  // the kept runs of all hours: T sets of launches, in hour order
+    if ((stays || paths || charge) && history) {  // the kept runs of all hours: T sets of launches, in hour order
         for (int t = 0; t < T; ++t) {
             const int32_t rc_side = side_hour(w.Dq + w.run_words() * static_cast<size_t>(t), w.cntg + w.len_words() * static_cast<size_t>(t), t);
             if (rc_side != CPM_OK) return rc_side;

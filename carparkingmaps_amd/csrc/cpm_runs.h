@@ -1,4 +1,4 @@
-// cpm_runs.h -- what the side outputs of a resample share (cpm_flows.h, cpm_flows_csr.h, cpm_stays.h, cpm_paths.h): where they go
+// cpm_runs.h -- what the side outputs of a resample share (cpm_flows.h, cpm_flows_csr.h, cpm_stays.h, cpm_paths.h, cpm_charge.h): where they go
 // (SideDest), the one reader of the drivers' runs, and the helpers their kernels have in common.
 // The grouped family's drivers of an hour sit in the 32 runs of their origin zone as id | local destination << idbits (cpm_grouped.h:
 // Dq / cntg): run g of zone z is the scap words at D + (z * 32 + g) * scap, its length cntg[z * 32 + g].  A block of 256 threads reads
@@ -45,12 +45,29 @@ struct PathsDest {
     bool any() const { return paths != nullptr; }
 };
 
+// where the charge of a step goes (cpm_charge.h): nowhere, or DEVICE int64[Z][T] x 2 + int32[Z][T] (+ uint32[n]), with the parameters
+// of include/cpm_charge.h (arrays on the DEVICE), the side array of the context and its distance matrix
+struct ChargeDest {
+    int64_t *charge = nullptr;
+    int64_t *used = nullptr;
+    int32_t *shrt = nullptr;
+    uint32_t *soc = nullptr;                // or null
+    uint2 *ebat = nullptr;                  // DEVICE uint2[n], filled by k_charge_init at the start of the attempt
+    const double *dist = nullptr;           // DEVICE f64[Z][Z], the context's origin-major copy of the distance matrix: dist[o * Z + d]
+    const uint32_t *zone_power = nullptr;   // DEVICE uint32[Z] or null: `power` everywhere
+    const uint32_t *soc_in = nullptr;       // DEVICE uint32[n] or null: `initial` for every car
+    uint32_t capacity = 0, power = 0, initial = 0;
+    double wh_per_km = 0.0;
+    bool any() const { return charge != nullptr; }
+};
+
 // every side output of one step
 struct SideDest {
     FlowsDest flows;
     StaysDest stays;
     PathsDest paths;
-    bool any() const { return flows.any() || stays.any() || paths.any(); }
+    ChargeDest charge;
+    bool any() const { return flows.any() || stays.any() || paths.any() || charge.any(); }
 };
 
 constexpr int kRunsPerZone = 32;   // runs per origin zone (= kGroups of cpm_grouped.h, asserted in grouped_run)

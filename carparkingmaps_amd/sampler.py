@@ -2,6 +2,7 @@
 reference's layout (Fortran order, 1-based zone ids).  One Sampler = one cpm_ctx = one GPU.
 """
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -18,6 +19,19 @@ def _f64(a, shape=None):
 
 def _vp(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+@dataclasses.dataclass
+class ChargeParams:
+    """The parameters of resample(charge=...) (include/cpm_charge.h): battery capacity in Wh, Wh a parked car takes per hour, every
+    car's charge at hour 0, Wh per km driven; zone_power_wh: charger power per zone ((Z,) uint32, 0 = no charger) in place of
+    power_wh; soc_in: initial charge per local car ((n,) uint32, clamped to the capacity) in place of initial_wh."""
+    capacity_wh: int
+    power_wh: int = 0
+    initial_wh: int = 0
+    wh_per_km: float = 0.0
+    zone_power_wh: object = None
+    soc_in: object = None
 
 
 class Sampler:
@@ -246,7 +260,7 @@ class Sampler:
     def solve_ivp_async(self, seed):
         _lib.check(self._L.cpm_solve_ivp_async(self._h, int(seed)))
 
-    def resample(self, seed, travel=False, want_state=False, want_trans=False, flows=False, stays=False, paths=False):
+    def resample(self, seed, travel=False, want_state=False, want_trans=False, flows=False, stays=False, paths=False, charge=None):
         """Returns dict(parking, driving: (Z,T) int64 F-order; sum_tt_q16: int; state, trans or None).
         flows=True (include/cpm_flows.h): the dict gains `flows`, the OD trip counts of every hour: (T, Z, Z) int32, C order,
         flows[t, o, d] = cars that drove from zone o + 1 to zone d + 1 in hour t + 1 (trips inside a zone on the diagonal), from the
@@ -261,9 +275,25 @@ class Sampler:
         paths=True (include/cpm_paths.h): the dict gains `paths`, (T, n) uint32, C order, n the context's car count:
         paths[t, i] = (destination of car i in hour t, 0-based; its own zone when it did not drive) | 0x80000000 when it drove, from
         the kernel family that produced the counts (paths_to_matrices, paths_flows).  Not together with flows, stays, want_state or
+        want_trans.
+        charge=ChargeParams(...) or a dict of its fields (include/cpm_charge.h): the dict gains `charge`, (Z, T) int64, C order,
+        charge[z, t] = Wh the chargers of zone z + 1 delivered in hour t; `used`, (Z, T) int64, Wh taken from batteries by the trips
+        that start in zone z + 1 in hour t; `short`, (Z, T) int32, those trips the battery did not cover; and `soc`, (n,) uint32, every
+        car's charge when the day ends.  Needs a resident distance matrix.  Not together with flows, stays, paths, want_state or
         want_trans."""
         parking = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
         driving = np.zeros((self.Z, self.T), dtype=np.int64, order="F")
+        if charge is not None:
+            if flows or stays or paths or want_state or want_trans:
+                raise ValueError("charge cannot be combined with flows, stays, paths, want_state or want_trans")
+            params, keep = self._charge_params(charge)
+            out, used, short, soc = self.charge_empty(), self.used_empty(), self.short_empty(), self.soc_empty()
+            tt = C.c_int64(0)
+            _lib.check(self._L.cpm_resample_charge(self._h, int(seed), _lib.CPM_FLAG_TRAVEL if travel else 0, C.byref(params), _vp(parking),
+                                                   _vp(driving), C.cast(C.byref(tt), C.c_void_p), _vp(out), _vp(used), _vp(short), _vp(soc)))
+            del keep
+            return dict(parking=parking, driving=driving, sum_tt_q16=int(tt.value), state=None, trans=None, charge=out, used=used,
+                        short=short, soc=soc)
         if paths:
             if flows or stays or want_state or want_trans:
                 raise ValueError("paths=True cannot be combined with flows, stays, want_state or want_trans")
@@ -365,6 +395,51 @@ class Sampler:
         flags = _lib.CPM_FLAG_TRAVEL if travel else 0
         _lib.check(self._L.cpm_resample_stays_dev(self._h, int(seed), flags, C.c_void_p(int(d_counts_ptr)), C.c_void_p(int(d_stays_ptr)),
                                                   C.c_void_p(int(d_parked_ptr))))
+
+    # -- charge (include/cpm_charge.h) --
+    def _charge_params(self, charge):
+        """(the C struct of a ChargeParams or a dict of its fields with host arrays, the arrays it points to)"""
+        p = charge if isinstance(charge, ChargeParams) else ChargeParams(**charge)
+        zp = None if p.zone_power_wh is None else np.ascontiguousarray(p.zone_power_wh, dtype=np.uint32)
+        si = None if p.soc_in is None else np.ascontiguousarray(p.soc_in, dtype=np.uint32)
+        if zp is not None and zp.shape != (self.Z,):
+            raise ValueError(f"zone_power_wh: expected ({self.Z},), got {zp.shape}")
+        if si is not None and si.shape != (self.car_count,):
+            raise ValueError(f"soc_in: expected ({self.car_count},), got {si.shape}")
+        c = _lib.ChargeParamsC(int(p.capacity_wh), int(p.power_wh), int(p.initial_wh), float(p.wh_per_km),
+                               None if zp is None else zp.ctypes.data, None if si is None else si.ctypes.data)
+        return c, (zp, si)
+
+    def charge_empty(self):
+        """The host array resample(charge=...) fills with the charging load: (Z, T) int64, C order (the library writes every word)."""
+        return np.empty((self.Z, self.T), dtype=np.int64, order="C")
+
+    def used_empty(self):
+        """The host array resample(charge=...) fills with the energy the trips took: (Z, T) int64, C order."""
+        return np.empty((self.Z, self.T), dtype=np.int64, order="C")
+
+    def short_empty(self):
+        """The host array resample(charge=...) fills with the trips the battery did not cover: (Z, T) int32, C order."""
+        return np.empty((self.Z, self.T), dtype=np.int32, order="C")
+
+    def soc_empty(self):
+        """The host array resample(charge=...) fills with every car's charge at the end of the day: (n,) uint32."""
+        return np.empty((self.car_count,), dtype=np.uint32)
+
+    def resample_charge_dev(self, seed, d_counts_ptr, d_charge_ptr, d_used_ptr, d_short_ptr, d_soc_ptr, capacity_wh, power_wh=0, initial_wh=0,
+                            wh_per_km=0.0, d_zone_power_ptr=0, d_soc_in_ptr=0, travel=False):
+        """Enqueue on the context's stream; d_counts_ptr as for resample_dev, d_charge_ptr / d_used_ptr = device addresses of
+        int64[Z*T], d_short_ptr of int32[Z*T], d_soc_ptr of uint32[n] or 0; d_zone_power_ptr / d_soc_in_ptr = device addresses of
+        uint32[Z] / uint32[n] or 0, which must stay valid until the step has run.  A non-zero status word in the count tensor
+        invalidates all four arrays: repeat the step."""
+        flags = _lib.CPM_FLAG_TRAVEL if travel else 0
+        p = _lib.ChargeParamsC(int(capacity_wh), int(power_wh), int(initial_wh), float(wh_per_km), int(d_zone_power_ptr) or None,
+                               int(d_soc_in_ptr) or None)
+        _lib.check(self._L.cpm_resample_charge_dev(self._h, int(seed), flags, C.byref(p), C.c_void_p(int(d_counts_ptr)) if d_counts_ptr else None,
+                                                   C.c_void_p(int(d_charge_ptr)) if d_charge_ptr else None,
+                                                   C.c_void_p(int(d_used_ptr)) if d_used_ptr else None,
+                                                   C.c_void_p(int(d_short_ptr)) if d_short_ptr else None,
+                                                   C.c_void_p(int(d_soc_ptr)) if d_soc_ptr else None))
 
     # -- per-car day records (include/cpm_paths.h) --
     def paths_words(self):
