@@ -52,6 +52,10 @@ class ChargeParamsC(C.Structure):
 # every symbol include/cpm_objectives.h declares (checked by tests/test_objectives.py); a header and a list of its own, likewise
 OBJECTIVES_SYMBOLS = ["cpm_set_measured", "cpm_objectives_dev"]
 
+# every symbol include/cpm_expected.h declares (checked by tests/test_expected.py); a header and a list of its own, likewise
+EXPECTED_SYMBOLS = ["cpm_expected_dev", "cpm_expected_batch_dev", "cpm_expected", "cpm_expected_batch"]
+CPM_EXPECT_IVP = 1  # flags of the expected calls: start the day from pi0 carried through hours 0 .. T-2
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -99,6 +103,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_paths.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_charge.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_objectives.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -186,7 +191,11 @@ def load():
     L.cpm_resample_charge_dev.argtypes = [vp, u64, u32, C.POINTER(ChargeParamsC), vp, vp, vp, vp, vp]
     L.cpm_set_measured.argtypes = [vp, vp]
     L.cpm_objectives_dev.argtypes = [vp, vp, i32, i64, vp, vp]
-    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS:
+    L.cpm_expected_dev.argtypes = [vp, vp, u32, vp, vp]
+    L.cpm_expected_batch_dev.argtypes = [vp, vp, u32, vp]
+    L.cpm_expected.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.cpm_expected_batch.argtypes = [vp, vp, u32, vp, vp]
+    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS + EXPECTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cpm.h"
@@ -19,6 +20,7 @@
 #include "../../include/cpm_paths.h"
 #include "../../include/cpm_charge.h"
 #include "../../include/cpm_objectives.h"
+#include "../../include/cpm_expected.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -34,6 +36,7 @@
 #include "cpm_ingest.h"
 #include "cpm_kit_debug.h"
 #include "cpm_objectives.h"
+#include "cpm_expected.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
 
@@ -225,6 +228,18 @@ struct cpm_ctx {
     double *d_obj_part = nullptr;       // [obj_ws_B][ceil(Z/256)] the workgroups' partial sums of the zone errors ...
     int *d_obj_part_n = nullptr;        // ... and their counts of valid zones
     int obj_ws_B = 0;
+    // expected densities (include/cpm_expected.h, cpm_expected.h): per-table arrays, built on first use and stale wherever d_last is rebuilt
+    int *d_exp_ell = nullptr;           // [T][Z] last destination with p > 0 (Z: a zero row)
+    double *d_exp_r = nullptr;          // [T][Z] max(0, 1 - last)
+    int *d_exp_start = nullptr;         // [T][Z + 1] where each destination's origins begin in ...
+    int *d_exp_list = nullptr;          // [T][Z] ... the origins sorted by (ell, origin)
+    unsigned long long *d_exp_bad = nullptr;  // the first row whose total exceeds 1, and its pinned twin
+    unsigned long long *h_exp_bad = nullptr;
+    bool exp_aux_valid = false;
+    double *d_exp_ws = nullptr;         // [4][exp_ws_B][Zs] pi and x, ping and pong
+    int exp_ws_B = 0;
+    double *d_exp_out = nullptr;        // [exp_out_B][2][T][Z] + [Z] + [Z]: the blocking calls' outputs, pi_next and pi_0
+    int exp_out_B = 0;
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -331,6 +346,7 @@ int32_t build_rows(cpm_ctx *c, bool with_cdf)
     const bool pack = cpm::pack_row_fits(static_cast<int>(c->Z));
     const bool cdf = with_cdf || !pack;
     c->have_cdf = false;
+    c->exp_aux_valid = false;
     c->cdf_full = false;
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     if (!c->d_ckpt) HIP_TRY(hipMalloc(&c->d_ckpt, sizeof(double) * static_cast<size_t>(rows) * cpm::ckpt_count(static_cast<int>(c->Z))));
@@ -595,6 +611,7 @@ int32_t build_p_dest_sparse(cpm_ctx *c, double e_dest, int32_t e_is_integer, boo
     if (rc != CPM_OK) return rc;
     c->have_cdf = false;
     c->cdf_full = false;
+    c->exp_aux_valid = false;
     hipLaunchKernelGGL(cpm::k_ds_pdest, dim3(cpm::ds_grid(rows)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_ds_cells, c->d_ds_cnt, cpm::kDsCap,
                        rows, static_cast<int>(c->Z), e_dest, e_is_integer, nc, zq_c, g_c, c->d_hi, c->d_last, c->d_sp, c->d_sj, c->d_scnt, c->d_err);
     HIP_TRY(hipGetLastError());
@@ -619,6 +636,7 @@ int32_t pack_uploaded_rows(cpm_ctx *c, int nc)
 {
     const int64_t rows = c->T * c->Z;
     const int zq_c = cpm::pack_zq(nc), g_c = cpm::pack_guide_bits(nc);
+    c->exp_aux_valid = false;
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     int32_t rc = ensure_hi(c, static_cast<size_t>(rows) * cpm::pack_row_words(zq_c, g_c, 1));
     if (rc != CPM_OK) return rc;
@@ -1167,6 +1185,151 @@ int32_t batch_enqueue(cpm_ctx *c, const std::vector<uint64_t> &seeds, const std:
     return CPM_OK;
 }
 
+// ------------------------------------------------------------------ expected densities (include/cpm_expected.h)
+int32_t exp_device_check()
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CPM_ERR_HIP, "expected: no HIP device: this library has no CPU path");
+    return CPM_OK;
+}
+
+// l, r, the residual lists and the row-total check of the installed p_destin tables (cpm_expected.h): once per table.  Synchronises
+// (the check is read back).
+int32_t ensure_exp_aux(cpm_ctx *c)
+{
+    if (c->exp_aux_valid) return CPM_OK;
+    int32_t rc = ensure_dense_p(c);
+    if (rc != CPM_OK) return rc;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t rows = static_cast<size_t>(Z) * T;
+    if (!c->d_exp_ell) HIP_TRY(hipMalloc(&c->d_exp_ell, sizeof(int) * rows));
+    if (!c->d_exp_r) HIP_TRY(hipMalloc(&c->d_exp_r, sizeof(double) * rows));
+    if (!c->d_exp_start) HIP_TRY(hipMalloc(&c->d_exp_start, sizeof(int) * (rows + T)));
+    if (!c->d_exp_list) HIP_TRY(hipMalloc(&c->d_exp_list, sizeof(int) * rows));
+    if (!c->d_exp_bad) HIP_TRY(hipMalloc(&c->d_exp_bad, sizeof(unsigned long long)));
+    if (!c->h_exp_bad) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_exp_bad), sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->d_exp_bad, 0xff, sizeof(unsigned long long), c->stream));
+    const dim3 grid(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T));
+    cpm::launch(cpm::k_exp_aux, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p, c->d_last, Z, c->d_exp_ell, c->d_exp_r, c->d_exp_bad);
+    HIP_TRY(hipGetLastError());
+    const size_t lds = sizeof(int) * static_cast<size_t>(Z);
+    HIP_TRY(cpm::lds_opt_in<cpm::k_exp_lists>(lds));
+    cpm::launch(cpm::k_exp_lists, grid, dim3(cpm::kExpBlock), lds, c->stream, c->d_exp_ell, Z, c->d_exp_start, c->d_exp_list);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_exp_bad, c->d_exp_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const unsigned long long bad = *c->h_exp_bad;
+    if (bad != ~0ull)
+        return fail(CPM_ERR_TABLE, "expected: the row total of hour %llu, origin %llu exceeds 1: not the sampler's law (include/cpm_expected.h)",
+                    bad / static_cast<unsigned long long>(Z) + 1, bad % static_cast<unsigned long long>(Z) + 1);
+    c->exp_aux_valid = true;
+    return CPM_OK;
+}
+
+template <int NB>
+void launch_exp_hour(cpm_ctx *c, int t, const double *q_cur, const double *q_next, size_t q_stride, const double *pi_in, const double *x_in,
+                     double *pi_out, double *x_out, double *park, double *drv, size_t out_stride, int Zs, int nf)
+{
+    const int Z = static_cast<int>(c->Z);
+    const size_t row = static_cast<size_t>(t) * Z;
+    cpm::launch(cpm::k_exp_hour<NB>, dim3(nblk(Z, cpm::kExpRows)), dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, c->d_last + row, c->d_exp_r + row,
+                c->d_exp_start + static_cast<size_t>(t) * (Z + 1), c->d_exp_list + row, q_cur, q_next, q_stride, pi_in, x_in, pi_out, x_out, park, drv,
+                out_stride, Z, Zs, nf);
+}
+
+// The recurrence for B fleets whose p_drive tables ([T][Z] each) lie q_stride words apart at pd: enqueued on the context's stream.
+// out: [B][2][T][Z].  pi_next: [Z] or nullptr (B = 1).
+int32_t expected_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *out, double *pi_next)
+{
+    if (!c->have_cdf || !(c->d_p || c->sparse_tables) || !c->d_last) return fail(CPM_ERR_STATE, "expected: p_dest not set");
+    int32_t rc = ensure_exp_aux(c);
+    if (rc != CPM_OK) return rc;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const int Zs = (Z + 1) & ~1;  // (every fleet's vector starts on a 16-byte line)
+    if (c->exp_ws_B < B) {  // (hipFree waits for what still reads the old workspace)
+        dfree(c->d_exp_ws);
+        c->exp_ws_B = 0;
+        HIP_TRY(hipMalloc(&c->d_exp_ws, sizeof(double) * 4 * static_cast<size_t>(B) * Zs));
+        c->exp_ws_B = B;
+    }
+    const size_t half = static_cast<size_t>(c->exp_ws_B) * Zs;
+    double *ws_pi[2] = {c->d_exp_ws, c->d_exp_ws + half};
+    double *ws_x[2] = {c->d_exp_ws + 2 * half, c->d_exp_ws + 3 * half};
+    const size_t zt = static_cast<size_t>(Z) * T, out_stride = 2 * zt;
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0;  // operators in front of the day
+    // step s applies the operator of hour (s < pre ? s : s - pre); the state behind step pre - 1 (or pi_0) is hour 0 of the outputs
+    cpm::launch(cpm::k_exp_init, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream, d_pi0, pd, q_stride, Z, Zs,
+                ws_pi[0], ws_x[0], pre == 0 ? out : nullptr, pre == 0 ? out + zt : nullptr, out_stride);
+    HIP_TRY(hipGetLastError());
+    const int steps = pre + T;
+    for (int s = 0; s < steps; ++s) {
+        const int t = s < pre ? s : s - pre;
+        const int day_next = s + 1 - pre;  // the hour of the day whose state this step produces (< 0: still in front of it)
+        const bool more = s + 1 < steps;
+        const int t_next = s + 1 < pre ? s + 1 : s + 1 - pre;
+        const int in = s & 1, ot = in ^ 1;
+        for (int f0 = 0; f0 < B; f0 += cpm::kExpMaxNB) {
+            const int nf = std::min(B - f0, cpm::kExpMaxNB);
+            const double *q_cur = pd + f0 * q_stride + static_cast<size_t>(t) * Z;
+            const double *q_next = more ? pd + f0 * q_stride + static_cast<size_t>(t_next) * Z : nullptr;
+            double *park = nullptr, *drv = nullptr;
+            if (day_next >= 0 && day_next < T) {
+                park = out + f0 * out_stride + static_cast<size_t>(day_next) * Z;
+                drv = park + zt;
+            } else if (day_next == T && pi_next) {
+                park = pi_next;  // (B = 1)
+            }
+            const size_t w0 = static_cast<size_t>(f0) * Zs;
+            // the smallest instantiation that holds the pass (fleets beyond nf repeat the last one and are not stored)
+            using Go = void (*)(cpm_ctx *, int, const double *, const double *, size_t, const double *, const double *, double *, double *, double *, double *,
+                                size_t, int, int);
+            const Go go = nf > 4 ? Go(launch_exp_hour<8>) : nf > 2 ? Go(launch_exp_hour<4>) : nf > 1 ? Go(launch_exp_hour<2>) : Go(launch_exp_hour<1>);
+            go(c, t, q_cur, q_next, q_stride, ws_pi[in] + w0, ws_x[in] + w0, ws_pi[ot] + w0, ws_x[ot] + w0, park, drv, out_stride, Zs, nf);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return CPM_OK;
+}
+
+int32_t exp_flags_check(uint32_t flags)
+{
+    if (flags & ~CPM_EXPECT_IVP) return fail(CPM_ERR_ARG, "expected: unknown flag bits 0x%x", flags);
+    return CPM_OK;
+}
+
+// the blocking calls' device arrays: outputs of B fleets, then pi_next [Z], then pi_0 [Z]
+int32_t ensure_exp_out(cpm_ctx *c, int B)
+{
+    if (c->exp_out_B >= B && c->d_exp_out) return CPM_OK;
+    dfree(c->d_exp_out);
+    c->exp_out_B = 0;
+    HIP_TRY(hipMalloc(&c->d_exp_out, sizeof(double) * (static_cast<size_t>(B) * 2 * c->Z * c->T + 2 * c->Z)));
+    c->exp_out_B = B;
+    return CPM_OK;
+}
+
+int32_t expected_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *parking, double *driving,
+                          double *pi_next)
+{
+    if (pi0)
+        for (int64_t z = 0; z < c->Z; ++z)
+            if (!std::isfinite(pi0[z]) || pi0[z] < 0.0) return fail(CPM_ERR_ARG, "expected: pi0 of zone %lld is NaN, infinite or negative", (long long)z + 1);
+    int32_t rc = ensure_exp_out(c, B);
+    if (rc != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z) * c->T;
+    double *d_next = c->d_exp_out + static_cast<size_t>(c->exp_out_B) * 2 * zt, *d_pi0 = d_next + c->Z;
+    if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream));
+    rc = expected_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, c->d_exp_out, pi_next ? d_next : nullptr);
+    if (rc != CPM_OK) return rc;
+    for (int b = 0; b < B; ++b) {
+        HIP_TRY(hipMemcpyAsync(parking + b * zt, c->d_exp_out + b * 2 * zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(driving + b * zt, c->d_exp_out + b * 2 * zt + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (pi_next) HIP_TRY(hipMemcpyAsync(pi_next, d_next, sizeof(double) * c->Z, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1269,6 +1432,14 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_meas_flag);
     dfree(c->d_obj_part);
     dfree(c->d_obj_part_n);
+    dfree(c->d_exp_ell);
+    dfree(c->d_exp_r);
+    dfree(c->d_exp_start);
+    dfree(c->d_exp_list);
+    dfree(c->d_exp_bad);
+    if (c->h_exp_bad) (void)hipHostFree(c->h_exp_bad);
+    dfree(c->d_exp_ws);
+    dfree(c->d_exp_out);
     dfree(c->d_ds_cells);
     dfree(c->d_ds_cnt);
     dfree(c->d_sp);
@@ -2597,6 +2768,57 @@ int32_t cpm_objectives_dev(cpm_ctx *c, const void *d_counts, int32_t B, int64_t 
                        c->d_obj_part_n, static_cast<int>(nb), static_cast<int>(c->Z), T, obj);
     HIP_TRY(hipGetLastError());
     return CPM_OK;
+}
+
+// ------------------------------------------------------------------ expected densities (include/cpm_expected.h)
+
+int32_t cpm_expected_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, void *d_out, void *d_pi_next)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!d_out) return fail(CPM_ERR_ARG, "expected_dev: null d_out");
+    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
+    return expected_enqueue(c, static_cast<const double *>(d_pi0), flags, 1, c->d_pdrive, 0, static_cast<double *>(d_out), static_cast<double *>(d_pi_next));
+}
+
+int32_t cpm_expected_batch_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, void *d_out)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!d_out) return fail(CPM_ERR_ARG, "expected_batch_dev: null d_out");
+    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (c->batch_B < 1) return fail(CPM_ERR_STATE, "expected: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
+    return expected_enqueue(c, static_cast<const double *>(d_pi0), flags, c->batch_B, c->d_pdrive_b, static_cast<size_t>(c->Z * c->T),
+                            static_cast<double *>(d_out), nullptr);
+}
+
+int32_t cpm_expected(cpm_ctx *c, const double *pi0, uint32_t flags, double *parking, double *driving, double *pi_next)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "expected: null density outputs");
+    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
+    return expected_blocking(c, pi0, flags, 1, c->d_pdrive, 0, parking, driving, pi_next);
+}
+
+int32_t cpm_expected_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double *parking, double *driving)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "expected_batch: null density outputs");
+    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (c->batch_B < 1) return fail(CPM_ERR_STATE, "expected: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
+    return expected_blocking(c, pi0, flags, c->batch_B, c->d_pdrive_b, static_cast<size_t>(c->Z * c->T), parking, driving, nullptr);
 }
 
 // ------------------------------------------------------------------ batch (include/cpm_batch.h)

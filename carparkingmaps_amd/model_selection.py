@@ -66,6 +66,18 @@ def parking_density_error(parking, C, measured):
     return float(err.sum() / err.size)
 
 
+def expected_objectives(parking_density, driving_density, measured_activity=None, measured_parking=None):
+    """The sweep's two noise-free objectives from Sampler.expected()'s (Z, T) densities: the functions above with the densities in
+    place of counts / C.  Returns dict(traffic_activity (T,), and activity_error / parking_error where the measured data is given).
+    No A_drive: the expected travel-time sum needs a second product over the datamatrix."""
+    out = {"traffic_activity": traffic_activity(driving_density)}
+    if measured_activity is not None:
+        out["activity_error"] = traffic_activity_error(out["traffic_activity"], measured_activity)
+    if measured_parking is not None:
+        out["parking_error"] = parking_density_error(parking_density, 1, measured_parking)
+    return out
+
+
 def parking_density_zone_errors(parking, C, measured):
     """The definition of include/cpm_objectives.h on the host, one IEEE f64 operation per step and in its order: (err (Z,) float64
     with -1.0 for a zone that is not valid, valid (Z,) bool).  A zone is valid when its measured row, added in hour order, is != 0 and

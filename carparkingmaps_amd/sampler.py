@@ -544,6 +544,49 @@ class Sampler:
                                               C.c_void_p(int(d_obj_ptr)) if d_obj_ptr else None,
                                               C.c_void_p(int(d_zone_err_ptr)) if d_zone_err_ptr else None))
 
+    # -- expected densities by Markov propagation (include/cpm_expected.h): no cars, no random numbers --
+    def _pi0(self, pi0):
+        return None if pi0 is None else np.ascontiguousarray(_f64(pi0, (self.Z,)))
+
+    def expected(self, pi0=None, ivp=False, want_next=False):
+        """The mean of the sampler's chain from the installed tables, blocking: (parking_density, driving_density), each (Z, T)
+        float64 F-order; parking_density[:, t] = pi_t, driving_density = pi_t * p_drive as the Bernoulli maps it.  C * these are
+        the expected counts of resample().  pi0: (Z,) or None (uniform 1/Z); ivp: start the day from pi0 carried through hours
+        0 .. T-2 (the expected solve_ivp).  want_next: also return pi after the day's last operator."""
+        a = self._pi0(pi0)
+        parking = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        driving = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        nxt = np.zeros(self.Z, dtype=np.float64) if want_next else None
+        _lib.check(self._L.cpm_expected(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(parking), _vp(driving), _vp(nxt)))
+        return (parking, driving, nxt) if want_next else (parking, driving)
+
+    def expected_batch(self, pi0=None, ivp=False):
+        """The same for every fleet of the installed batch tables: (parking_density, driving_density), each (Z, T, B); fleet b bit
+        for bit expected() with p_drive[:, :, b] installed."""
+        a = self._pi0(pi0)
+        B = self.get_info(_lib.CPM_INFO_BATCH)
+        parking = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
+        driving = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
+        _lib.check(self._L.cpm_expected_batch(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(parking), _vp(driving)))
+        return parking, driving
+
+    def expected_words(self):
+        """float64 words of one fleet's expected_dev tensor: 2*T*Z (parking[T][Z], then driving[T][Z])."""
+        return 2 * self.T * self.Z
+
+    def expected_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False, d_pi_next_ptr=0):
+        """Enqueue on the context's stream: d_out_ptr = device address of float64[expected_words()]; d_pi0_ptr = device address of
+        float64[Z] or 0 (uniform); d_pi_next_ptr = device address of float64[Z] or 0.  (The first call after the p_destin tables
+        changed builds its per-table arrays and synchronises once.)"""
+        _lib.check(self._L.cpm_expected_dev(self._h, C.c_void_p(int(d_pi0_ptr)) if d_pi0_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
+                                            C.c_void_p(int(d_out_ptr)) if d_out_ptr else None,
+                                            C.c_void_p(int(d_pi_next_ptr)) if d_pi_next_ptr else None))
+
+    def expected_batch_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False):
+        """Enqueue on the context's stream: d_out_ptr = device address of float64[B][expected_words()] for the installed batch tables."""
+        _lib.check(self._L.cpm_expected_batch_dev(self._h, C.c_void_p(int(d_pi0_ptr)) if d_pi0_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
+                                                  C.c_void_p(int(d_out_ptr)) if d_out_ptr else None))
+
     def last_kernel_ms(self):
         buf = (C.c_float * 8192)()
         n = C.c_int32(0)
