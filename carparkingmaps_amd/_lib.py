@@ -56,6 +56,10 @@ OBJECTIVES_SYMBOLS = ["cpm_set_measured", "cpm_objectives_dev"]
 EXPECTED_SYMBOLS = ["cpm_expected_dev", "cpm_expected_batch_dev", "cpm_expected", "cpm_expected_batch"]
 CPM_EXPECT_IVP = 1  # flags of the expected calls: start the day from pi0 carried through hours 0 .. T-2
 
+# every symbol include/cpm_expected_travel.h declares (checked by tests/test_expected_travel.py); a header and a list of its own, likewise
+EXPECTED_TRAVEL_SYMBOLS = ["cpm_expected_trip_dev", "cpm_expected_trip", "cpm_expected_travel_dev", "cpm_expected_travel",
+                           "cpm_expected_travel_batch", "cpm_expected_trip_builds"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -104,6 +108,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_charge.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_objectives.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_travel.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -195,10 +200,18 @@ def load():
     L.cpm_expected_batch_dev.argtypes = [vp, vp, u32, vp]
     L.cpm_expected.argtypes = [vp, vp, u32, vp, vp, vp]
     L.cpm_expected_batch.argtypes = [vp, vp, u32, vp, vp]
-    for name in SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS + EXPECTED_SYMBOLS:
+    L.cpm_expected_trip_dev.argtypes = [vp, vp]
+    L.cpm_expected_trip.argtypes = [vp, vp, vp]
+    L.cpm_expected_travel_dev.argtypes = [vp, vp, i32, vp, vp]
+    L.cpm_expected_travel.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.cpm_expected_travel_batch.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.cpm_expected_trip_builds.argtypes = [vp]
+    for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
+                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32
+    L.cpm_expected_trip_builds.restype = i64  # (a counter; negative: a status code)
     _lib = L
     return L
 

@@ -21,6 +21,7 @@
 #include "../../include/cpm_charge.h"
 #include "../../include/cpm_objectives.h"
 #include "../../include/cpm_expected.h"
+#include "../../include/cpm_expected_travel.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -37,6 +38,7 @@
 #include "cpm_kit_debug.h"
 #include "cpm_objectives.h"
 #include "cpm_expected.h"
+#include "cpm_expected_travel.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
 
@@ -240,6 +242,16 @@ struct cpm_ctx {
     int exp_ws_B = 0;
     double *d_exp_out = nullptr;        // [exp_out_B][2][T][Z] + [Z] + [Z]: the blocking calls' outputs, pi_next and pi_0
     int exp_out_B = 0;
+    // expected travel (include/cpm_expected_travel.h, cpm_expected_travel.h): the trip weights, built on first use and stale wherever
+    // the p_destin tables (exp_aux_valid), d_dm or d_dist change
+    double *d_exp_w = nullptr;          // [2][T][Z] w_sec | w_km
+    double *d_exp_wpart = nullptr;      // [segments][2][T][Z] the destination segments' sums
+    bool exp_trip_valid = false;
+    int64_t exp_trip_builds = 0;
+    double *d_exp_trav = nullptr;       // [exp_trav_B][2][T][Z] + [exp_trav_B][2]: the blocking calls' seconds | km and totals
+    int exp_trav_B = 0;
+    double *d_exp_tpart = nullptr;      // [exp_tpart_B][chunks][2] the chunks' sums of k_exp_travel, added in order by k_exp_travel_total
+    int exp_tpart_B = 0;
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -347,6 +359,7 @@ int32_t build_rows(cpm_ctx *c, bool with_cdf)
     const bool cdf = with_cdf || !pack;
     c->have_cdf = false;
     c->exp_aux_valid = false;
+    c->exp_trip_valid = false;
     c->cdf_full = false;
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     if (!c->d_ckpt) HIP_TRY(hipMalloc(&c->d_ckpt, sizeof(double) * static_cast<size_t>(rows) * cpm::ckpt_count(static_cast<int>(c->Z))));
@@ -612,6 +625,7 @@ int32_t build_p_dest_sparse(cpm_ctx *c, double e_dest, int32_t e_is_integer, boo
     c->have_cdf = false;
     c->cdf_full = false;
     c->exp_aux_valid = false;
+    c->exp_trip_valid = false;
     hipLaunchKernelGGL(cpm::k_ds_pdest, dim3(cpm::ds_grid(rows)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_ds_cells, c->d_ds_cnt, cpm::kDsCap,
                        rows, static_cast<int>(c->Z), e_dest, e_is_integer, nc, zq_c, g_c, c->d_hi, c->d_last, c->d_sp, c->d_sj, c->d_scnt, c->d_err);
     HIP_TRY(hipGetLastError());
@@ -637,6 +651,7 @@ int32_t pack_uploaded_rows(cpm_ctx *c, int nc)
     const int64_t rows = c->T * c->Z;
     const int zq_c = cpm::pack_zq(nc), g_c = cpm::pack_guide_bits(nc);
     c->exp_aux_valid = false;
+    c->exp_trip_valid = false;
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     int32_t rc = ensure_hi(c, static_cast<size_t>(rows) * cpm::pack_row_words(zq_c, g_c, 1));
     if (rc != CPM_OK) return rc;
@@ -1198,6 +1213,7 @@ int32_t exp_device_check()
 int32_t ensure_exp_aux(cpm_ctx *c)
 {
     if (c->exp_aux_valid) return CPM_OK;
+    c->exp_trip_valid = false;  // (the trip weights read l and r: never older than these)
     int32_t rc = ensure_dense_p(c);
     if (rc != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
@@ -1330,6 +1346,91 @@ int32_t expected_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, 
     return CPM_OK;
 }
 
+// ------------------------------------------------------------------ expected travel (include/cpm_expected_travel.h)
+// The trip weights of the installed p_destin tables, datamatrix and distance matrix in d_exp_w: once per table (enqueued on the
+// context's stream; ensure_exp_aux synchronises when it rebuilds).
+int32_t ensure_exp_trip(cpm_ctx *c)
+{
+    if (!c->have_cdf || !(c->d_p || c->sparse_tables) || !c->d_last) return fail(CPM_ERR_STATE, "expected travel: p_dest not set");
+    if (!c->have_dmat) return fail(CPM_ERR_STATE, "expected travel: datamatrix not set (cpm_set_datamatrix, cpm_createdatamatrix_* or cpm_synth_datamatrix)");
+    if (!c->have_dist) return fail(CPM_ERR_STATE, "expected travel: distance matrix not set (cpm_set_distance* or the dist of cpm_set_datamatrix)");
+    int32_t rc = ensure_exp_aux(c);  // (the row-total check; clears exp_trip_valid when it rebuilds)
+    if (rc != CPM_OK) return rc;
+    if (c->exp_trip_valid) return CPM_OK;
+    if ((rc = ensure_dense_p(c)) != CPM_OK) return rc;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t zt = static_cast<size_t>(Z) * T;
+    const int nseg = cpm::trip_segments(Z, T), seg_len = cpm::trip_segment_len(Z, nseg);
+    if (!c->d_exp_w) HIP_TRY(hipMalloc(&c->d_exp_w, sizeof(double) * 2 * zt));
+    if (!c->d_exp_wpart) HIP_TRY(hipMalloc(&c->d_exp_wpart, sizeof(double) * 2 * zt * nseg));
+    const dim3 grid(nblk(Z, cpm::kTripStrip), static_cast<unsigned>(T), static_cast<unsigned>(nseg));
+    if (Z & 1) cpm::launch(cpm::k_exp_trip<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p, c->d_dm, c->d_dist, Z, T, seg_len, c->d_exp_wpart);
+    else cpm::launch(cpm::k_exp_trip<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p, c->d_dm, c->d_dist, Z, T, seg_len, c->d_exp_wpart);
+    HIP_TRY(hipGetLastError());
+    cpm::launch(cpm::k_exp_trip_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream, c->d_exp_wpart, nseg,
+                c->d_dm, c->d_dist, c->d_last, c->d_exp_ell, c->d_exp_r, Z, T, c->d_exp_w);
+    HIP_TRY(hipGetLastError());
+    c->exp_trip_valid = true;
+    ++c->exp_trip_builds;
+    return CPM_OK;
+}
+
+// seconds | km and the totals of B fleets from their expected tensors (enqueued); either output may be nullptr
+int32_t expected_travel_enqueue(cpm_ctx *c, const double *d_expected, int B, double *d_travel, double *d_totals)
+{
+    int32_t rc = ensure_exp_trip(c);
+    if (rc != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z) * c->T;
+    const int nchunk = static_cast<int>(nblk(static_cast<int64_t>(zt), cpm::kTravelChunk));
+    if (d_totals && c->exp_tpart_B < B) {  // (hipFree waits for what still reads the old workspace)
+        dfree(c->d_exp_tpart);
+        c->exp_tpart_B = 0;
+        HIP_TRY(hipMalloc(&c->d_exp_tpart, sizeof(double) * 2 * static_cast<size_t>(B) * nchunk));
+        c->exp_tpart_B = B;
+    }
+    cpm::launch(cpm::k_exp_travel, dim3(static_cast<unsigned>(nchunk), static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream, d_expected,
+                c->d_exp_w, zt, d_travel, d_totals ? c->d_exp_tpart : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (d_totals) {
+        cpm::launch(cpm::k_exp_travel_total, dim3(static_cast<unsigned>(B)), dim3(64), 0, c->stream, c->d_exp_tpart, nchunk, d_totals);
+        HIP_TRY(hipGetLastError());
+    }
+    return CPM_OK;
+}
+
+// the blocking calls: the propagation into d_exp_out, the product into d_exp_trav, then the copies
+int32_t expected_travel_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *seconds, double *km,
+                                 double *totals)
+{
+    if (pi0)
+        for (int64_t z = 0; z < c->Z; ++z)
+            if (!std::isfinite(pi0[z]) || pi0[z] < 0.0) return fail(CPM_ERR_ARG, "expected: pi0 of zone %lld is NaN, infinite or negative", (long long)z + 1);
+    int32_t rc = ensure_exp_trip(c);  // (first: a missing datamatrix is reported before any work is enqueued)
+    if (rc != CPM_OK) return rc;
+    if ((rc = ensure_exp_out(c, B)) != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z) * c->T;
+    if (c->exp_trav_B < B || !c->d_exp_trav) {
+        dfree(c->d_exp_trav);
+        c->exp_trav_B = 0;
+        HIP_TRY(hipMalloc(&c->d_exp_trav, sizeof(double) * (static_cast<size_t>(B) * 2 * zt + static_cast<size_t>(B) * 2)));
+        c->exp_trav_B = B;
+    }
+    double *d_pi0 = c->d_exp_out + static_cast<size_t>(c->exp_out_B) * 2 * zt + c->Z;
+    double *d_tot = c->d_exp_trav + static_cast<size_t>(c->exp_trav_B) * 2 * zt;
+    if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream));
+    rc = expected_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, c->d_exp_out, nullptr);
+    if (rc != CPM_OK) return rc;
+    rc = expected_travel_enqueue(c, c->d_exp_out, B, c->d_exp_trav, d_tot);
+    if (rc != CPM_OK) return rc;
+    for (int b = 0; b < B; ++b) {
+        HIP_TRY(hipMemcpyAsync(seconds + b * zt, c->d_exp_trav + b * 2 * zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(km + b * zt, c->d_exp_trav + b * 2 * zt + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (totals) HIP_TRY(hipMemcpyAsync(totals, d_tot, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1440,6 +1541,10 @@ int32_t cpm_destroy(cpm_ctx *c)
     if (c->h_exp_bad) (void)hipHostFree(c->h_exp_bad);
     dfree(c->d_exp_ws);
     dfree(c->d_exp_out);
+    dfree(c->d_exp_w);
+    dfree(c->d_exp_wpart);
+    dfree(c->d_exp_trav);
+    dfree(c->d_exp_tpart);
     dfree(c->d_ds_cells);
     dfree(c->d_ds_cnt);
     dfree(c->d_sp);
@@ -1688,6 +1793,7 @@ int32_t cpm_set_datamatrix(cpm_ctx *c, const double *datamatrix, const double *d
     c->tts_valid = false;
     c->ds_valid = false;
     c->pdrive_mean_valid = false;
+    c->exp_trip_valid = false;
     HIP_TRY(hipMemcpyAsync(c->d_dm, datamatrix, bytes, hipMemcpyHostToDevice, c->stream));
     if (dist) HIP_TRY(hipMemcpyAsync(c->d_dist, dist, dbytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1720,6 +1826,7 @@ static int32_t datamatrix_from_device_rows(cpm_ctx *c, const double *d_raw, int6
     c->tts_valid = false;
     c->ds_valid = false;
     c->pdrive_mean_valid = false;
+    c->exp_trip_valid = false;
     HIP_TRY(hipMemsetAsync(c->d_dm, 0, sizeof(double) * cells * 2, c->stream));  // zeros(number_zones, number_zones, T, 2) (:7)
     if (n == 0) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1840,6 +1947,7 @@ int32_t cpm_set_distance_from_centroids(cpm_ctx *c, const double *centroid_lat, 
     if (!centroid_lat || !centroid_long) return fail(CPM_ERR_ARG, "null centroids");
     const size_t dbytes = sizeof(double) * c->Z * c->Z;
     if (!c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, dbytes));
+    c->exp_trip_valid = false;  // (before the first byte changes: a copy that fails half way leaves no weights behind)
     double *d_ll = nullptr;
     HIP_TRY(hipMalloc(&d_ll, sizeof(double) * 2 * c->Z));
     hipError_t e = hipMemcpyAsync(d_ll, centroid_lat, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream);
@@ -1855,6 +1963,7 @@ int32_t cpm_set_distance_from_centroids(cpm_ctx *c, const double *centroid_lat, 
     c->have_dist = true;
     c->dist_rows_valid = false;
     c->pdrive_mean_valid = false;
+    c->exp_trip_valid = false;
     return CPM_OK;
 }
 
@@ -1864,11 +1973,13 @@ int32_t cpm_set_distance(cpm_ctx *c, const double *dist)
     if (!dist) return fail(CPM_ERR_ARG, "null dist");
     const size_t dbytes = sizeof(double) * c->Z * c->Z;
     if (!c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, dbytes));
+    c->exp_trip_valid = false;  // (before the first byte changes: a copy that fails half way leaves no weights behind)
     HIP_TRY(hipMemcpyAsync(c->d_dist, dist, dbytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_dist = true;
     c->dist_rows_valid = false;
     c->pdrive_mean_valid = false;
+    c->exp_trip_valid = false;
     return CPM_OK;
 }
 
@@ -2024,6 +2135,7 @@ int32_t cpm_synth_datamatrix(cpm_ctx *c, uint64_t table_seed, double density)
     c->tts_valid = false;
     c->ds_valid = false;
     c->pdrive_mean_valid = false;
+    c->exp_trip_valid = false;
     hipLaunchKernelGGL(cpm::k_synth_datamatrix, dim3(nblk(c->Z, 256), static_cast<unsigned>(c->Z), static_cast<unsigned>(c->T)), dim3(256), 0, c->stream,
                        c->d_dm, static_cast<int>(c->Z), static_cast<int>(c->T), table_seed, density);
     hipLaunchKernelGGL(cpm::k_synth_dist, dim3(nblk(c->Z, 256), static_cast<unsigned>(c->Z)), dim3(256), 0, c->stream, c->d_dist, static_cast<int>(c->Z),
@@ -2819,6 +2931,79 @@ int32_t cpm_expected_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double
     CTX_TRY(c);
     if (c->batch_B < 1) return fail(CPM_ERR_STATE, "expected: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
     return expected_blocking(c, pi0, flags, c->batch_B, c->d_pdrive_b, static_cast<size_t>(c->Z * c->T), parking, driving, nullptr);
+}
+
+// ------------------------------------------------------------------ expected travel (include/cpm_expected_travel.h)
+
+int32_t cpm_expected_trip_dev(cpm_ctx *c, void *d_w)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!d_w) return fail(CPM_ERR_ARG, "expected_trip_dev: null d_w");
+    CTX_TRY(c);
+    if ((rc = ensure_exp_trip(c)) != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(d_w, c->d_exp_w, sizeof(double) * 2 * c->Z * c->T, hipMemcpyDeviceToDevice, c->stream));
+    return CPM_OK;
+}
+
+int32_t cpm_expected_trip(cpm_ctx *c, double *w_sec, double *w_km)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!w_sec || !w_km) return fail(CPM_ERR_ARG, "expected_trip: null outputs");
+    CTX_TRY(c);
+    if ((rc = ensure_exp_trip(c)) != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z) * c->T;
+    HIP_TRY(hipMemcpyAsync(w_sec, c->d_exp_w, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(w_km, c->d_exp_w + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+int32_t cpm_expected_travel_dev(cpm_ctx *c, const void *d_expected, int32_t B, void *d_travel, void *d_totals)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!d_expected) return fail(CPM_ERR_ARG, "expected_travel_dev: null d_expected");
+    if (B < 1) return fail(CPM_ERR_ARG, "expected_travel_dev: B = %d", B);
+    if (!d_travel && !d_totals) return fail(CPM_ERR_ARG, "expected_travel_dev: d_travel and d_totals are both null");
+    CTX_TRY(c);
+    return expected_travel_enqueue(c, static_cast<const double *>(d_expected), B, static_cast<double *>(d_travel), static_cast<double *>(d_totals));
+}
+
+int32_t cpm_expected_travel(cpm_ctx *c, const double *pi0, uint32_t flags, double *seconds, double *km, double *totals)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!seconds || !km) return fail(CPM_ERR_ARG, "expected_travel: null outputs");
+    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
+    return expected_travel_blocking(c, pi0, flags, 1, c->d_pdrive, 0, seconds, km, totals);
+}
+
+int32_t cpm_expected_travel_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double *seconds, double *km, double *totals)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!seconds || !km) return fail(CPM_ERR_ARG, "expected_travel_batch: null outputs");
+    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (c->batch_B < 1) return fail(CPM_ERR_STATE, "expected: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
+    return expected_travel_blocking(c, pi0, flags, c->batch_B, c->d_pdrive_b, static_cast<size_t>(c->Z * c->T), seconds, km, totals);
+}
+
+int64_t cpm_expected_trip_builds(const cpm_ctx *c)
+{
+    const int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    return c->exp_trip_builds;
 }
 
 // ------------------------------------------------------------------ batch (include/cpm_batch.h)

@@ -66,15 +66,20 @@ def parking_density_error(parking, C, measured):
     return float(err.sum() / err.size)
 
 
-def expected_objectives(parking_density, driving_density, measured_activity=None, measured_parking=None):
-    """The sweep's two noise-free objectives from Sampler.expected()'s (Z, T) densities: the functions above with the densities in
+def expected_objectives(parking_density, driving_density, measured_activity=None, measured_parking=None, seconds=None):
+    """The sweep's noise-free objectives from Sampler.expected()'s (Z, T) densities: the functions above with the densities in
     place of counts / C.  Returns dict(traffic_activity (T,), and activity_error / parking_error where the measured data is given).
-    No A_drive: the expected travel-time sum needs a second product over the datamatrix."""
+    seconds: Sampler.expected_travel()'s (Z, T) "seconds" (summed here) or its "total_seconds" (a scalar, used as it is) -- the result
+    then also holds A_drive = total / (T * 3600), the share of the day a car drives (src/averagedrivingtime.jl:10) without the
+    sampling noise; without it the result is what it was before that argument existed."""
     out = {"traffic_activity": traffic_activity(driving_density)}
     if measured_activity is not None:
         out["activity_error"] = traffic_activity_error(out["traffic_activity"], measured_activity)
     if measured_parking is not None:
         out["parking_error"] = parking_density_error(parking_density, 1, measured_parking)
+    if seconds is not None:
+        total = float(seconds) if np.ndim(seconds) == 0 else float(np.asarray(seconds, dtype=np.float64).sum())
+        out["A_drive"] = total / (np.asarray(driving_density).shape[1] * 3600.0)
     return out
 
 
@@ -181,6 +186,52 @@ class Evaluator:
         if self.device_objectives:
             return self._from_record(pt, self._record_of_host_counts(r["parking"], r["driving"], r["sum_tt_q16"]))
         return self._objectives(pt, r["parking"], r["driving"], r["sum_tt_q16"])
+
+    # -- noise-free form: the chain's mean (include/cpm_expected.h) and the expected travel (include/cpm_expected_travel.h); no cars --
+    def _expected_from_device(self, pts, ivp, batch):
+        """The installed tables' expected tensors and travel totals through the device entries: one propagation per fleet, 2 + 2*T*Z
+        words per fleet to the host.  pts: the points whose tables are installed; batch: as the batch tables."""
+        import torch
+        s = self.sampler
+        B, words = len(pts), s.expected_words()
+        dev = f"cuda:{s.device}"
+        out = torch.empty(B * words, dtype=torch.float64, device=dev)
+        tot = torch.empty(2 * B, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(s.device)
+        if batch:
+            s.expected_batch_dev(out.data_ptr(), 0, ivp)
+        else:
+            s.expected_dev(out.data_ptr(), 0, ivp)
+        s.expected_travel_dev(out.data_ptr(), B, 0, tot.data_ptr())
+        s.sync()
+        both = out.cpu().numpy().reshape(B, 2, s.T, s.Z)
+        totals = tot.cpu().numpy().reshape(B, 2)
+        outs = []
+        for b, pt in enumerate(pts):
+            parking, driving = both[b, 0].T, both[b, 1].T          # Julia order (Z, T): views
+            r = {"e_drive": pt.e_drive, "p_min": pt.p_min, "p_max": pt.p_max, "e_dest": float(pt.e_dest)}
+            r.update(expected_objectives(parking, driving, self.measured_activity, self.measured_parking, seconds=float(totals[b, 0])))
+            r.update(total_seconds=float(totals[b, 0]), total_km=float(totals[b, 1]), parking=parking, driving=driving)
+            outs.append(r)
+        return outs
+
+    def evaluate_expected(self, pt, ivp=True):
+        """One point without sampling noise: installs its tables and returns the objectives of the chain's mean -- traffic_activity,
+        activity_error / parking_error where the measured data is given, and A_drive from the expected travel-time sum.  ivp: the day
+        starts from the uniform placement carried through hours 0 .. T-2, the expected form of the post-IVP state evaluate() samples
+        from.  `parking` / `driving` are densities (counts / C in the mean).  Needs no cars."""
+        self._install(pt)
+        return self._expected_from_device([pt], ivp, False)[0]
+
+    def evaluate_expected_batch(self, pts, ivp=True):
+        """The same for points that share e_dest, as the fleets of ONE batched propagation (build_p_drive_batch, expected_batch_dev,
+        expected_travel_dev): a list of evaluate_expected()'s dicts, point for point and bit for bit."""
+        pts = list(pts)
+        if len({e_dest_key(pt.e_dest) for pt in pts}) != 1:
+            raise ValueError("evaluate_expected_batch: the points of a batch share e_dest")
+        self._install_dest(pts[0].e_dest)
+        self.sampler.build_p_drive_batch([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts])
+        return self._expected_from_device(pts, ivp, True)
 
     # -- device objectives: the record of include/cpm_objectives.h in the place of the count tensor --
     def _from_record(self, pt, rec):

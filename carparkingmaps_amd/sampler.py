@@ -587,6 +587,58 @@ class Sampler:
         _lib.check(self._L.cpm_expected_batch_dev(self._h, C.c_void_p(int(d_pi0_ptr)) if d_pi0_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
                                                   C.c_void_p(int(d_out_ptr)) if d_out_ptr else None))
 
+    # -- expected travel time and distance (include/cpm_expected_travel.h): the trip weights of the tables, times the driving density --
+    def expected_trip(self):
+        """(w_sec, w_km), each (Z, T) float64 F-order: the expected seconds and kilometres of ONE trip that starts in zone o in hour
+        t, from the installed p_destin tables, datamatrix and distance matrix alone.  Cached in the context until one of them changes."""
+        w_sec = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        w_km = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        _lib.check(self._L.cpm_expected_trip(self._h, _vp(w_sec), _vp(w_km)))
+        return w_sec, w_km
+
+    def expected_trip_builds(self):
+        """How often this context has built the trip weights."""
+        n = int(self._L.cpm_expected_trip_builds(self._h))
+        if n < 0:
+            _lib.check(n)
+        return n
+
+    def expected_travel(self, pi0=None, ivp=False):
+        """The expected travel of a fleet, blocking: dict(seconds, km: (Z, T) float64 F-order, the driving density of expected() times
+        the trip weights; total_seconds, total_km; A_drive = total_seconds / (T * 3600), the noise-free share of the day a car
+        drives).  C * seconds[z, t] is the expected travel-time sum of the cars that leave z in hour t of resample(travel=True)."""
+        a = self._pi0(pi0)
+        seconds = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        km = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        totals = np.zeros(2, dtype=np.float64)
+        _lib.check(self._L.cpm_expected_travel(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(seconds), _vp(km), _vp(totals)))
+        return dict(seconds=seconds, km=km, total_seconds=float(totals[0]), total_km=float(totals[1]),
+                    A_drive=float(totals[0]) / (self.T * 3600.0))
+
+    def expected_travel_batch(self, pi0=None, ivp=False):
+        """The same for every fleet of the installed batch tables: seconds, km (Z, T, B) and total_seconds, total_km, A_drive (B,);
+        fleet b bit for bit expected_travel() with p_drive[:, :, b] installed."""
+        a = self._pi0(pi0)
+        B = self.get_info(_lib.CPM_INFO_BATCH)
+        seconds = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
+        km = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
+        totals = np.zeros((B, 2), dtype=np.float64)
+        _lib.check(self._L.cpm_expected_travel_batch(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(seconds), _vp(km), _vp(totals)))
+        return dict(seconds=seconds, km=km, total_seconds=totals[:, 0].copy(), total_km=totals[:, 1].copy(),
+                    A_drive=totals[:, 0] / (self.T * 3600.0))
+
+    def expected_trip_dev(self, d_w_ptr):
+        """Enqueue on the context's stream: d_w_ptr = device address of float64[2][T][Z], w_sec then w_km."""
+        _lib.check(self._L.cpm_expected_trip_dev(self._h, C.c_void_p(int(d_w_ptr)) if d_w_ptr else None))
+
+    def expected_travel_dev(self, d_expected_ptr, B, d_travel_ptr=0, d_totals_ptr=0):
+        """Enqueue on the context's stream: d_expected_ptr = device address of float64[B][expected_words()] as expected_dev /
+        expected_batch_dev wrote it (only the driving halves are read); d_travel_ptr = device address of float64[B][2][T][Z], seconds
+        then km, or 0; d_totals_ptr = device address of float64[B][2] or 0.  Not both 0."""
+        _lib.check(self._L.cpm_expected_travel_dev(self._h, C.c_void_p(int(d_expected_ptr)) if d_expected_ptr else None, int(B),
+                                                   C.c_void_p(int(d_travel_ptr)) if d_travel_ptr else None,
+                                                   C.c_void_p(int(d_totals_ptr)) if d_totals_ptr else None))
+
     def last_kernel_ms(self):
         buf = (C.c_float * 8192)()
         n = C.c_int32(0)
