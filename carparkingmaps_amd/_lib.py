@@ -60,6 +60,9 @@ CPM_EXPECT_IVP = 1  # flags of the expected calls: start the day from pi0 carrie
 EXPECTED_TRAVEL_SYMBOLS = ["cpm_expected_trip_dev", "cpm_expected_trip", "cpm_expected_travel_dev", "cpm_expected_travel",
                            "cpm_expected_travel_batch", "cpm_expected_trip_builds"]
 
+# every symbol include/cpm_expected_grad.h declares (checked by tests/test_expected_grad.py); a header and a list of its own, likewise
+EXPECTED_GRAD_SYMBOLS = ["cpm_expected_grad_dev", "cpm_expected_grad"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -109,6 +112,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_objectives.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_travel.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -206,8 +210,10 @@ def load():
     L.cpm_expected_travel.argtypes = [vp, vp, u32, vp, vp, vp]
     L.cpm_expected_travel_batch.argtypes = [vp, vp, u32, vp, vp, vp]
     L.cpm_expected_trip_builds.argtypes = [vp]
+    L.cpm_expected_grad_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    L.cpm_expected_grad.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
-                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS):
+                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

@@ -22,6 +22,7 @@
 #include "../../include/cpm_objectives.h"
 #include "../../include/cpm_expected.h"
 #include "../../include/cpm_expected_travel.h"
+#include "../../include/cpm_expected_grad.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -39,6 +40,7 @@
 #include "cpm_objectives.h"
 #include "cpm_expected.h"
 #include "cpm_expected_travel.h"
+#include "cpm_expected_grad.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
 
@@ -252,6 +254,9 @@ struct cpm_ctx {
     int exp_trav_B = 0;
     double *d_exp_tpart = nullptr;      // [exp_tpart_B][chunks][2] the chunks' sums of k_exp_travel, added in order by k_exp_travel_total
     int exp_tpart_B = 0;
+    // the adjoint of the expected densities (include/cpm_expected_grad.h, cpm_expected_grad.h)
+    double *d_exp_gws = nullptr;        // [N + 4 + segments][Zs]: pi_s of the N = 2T - 1 operators, x ping and pong, mu ping and pong, the segments' sums
+    double *d_exp_gio = nullptr;        // [2][T][Z] + [Z] + [T][Z] + [Z] + [Z]: the blocking call's cotangents, G_next, grad_p_drive, grad_pi0 and pi_0
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -1431,6 +1436,88 @@ int32_t expected_travel_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, 
     return CPM_OK;
 }
 
+// ------------------------------------------------------------------ adjoint of the expected densities (include/cpm_expected_grad.h)
+// The forward propagation with the kernels of expected_enqueue (B = 1; pi_s of every operator kept, operator N - 1 not applied: nothing
+// reads pi_N), then the N backward operators: enqueued on the context's stream.  cot: [2][T][Z]; gnext, grad_pi0: [Z] or nullptr;
+// grad_pd: [T][Z].
+int32_t expected_grad_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, const double *cot, const double *gnext, double *grad_pd, double *grad_pi0)
+{
+    if (!c->have_cdf || !(c->d_p || c->sparse_tables) || !c->d_last) return fail(CPM_ERR_STATE, "expected: p_dest not set");
+    int32_t rc = ensure_exp_aux(c);
+    if (rc != CPM_OK) return rc;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
+    const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
+    const int most = 2 * T - 1;   // operators under CPM_EXPECT_IVP: the workspace is sized once
+    if (!c->d_exp_gws) HIP_TRY(hipMalloc(&c->d_exp_gws, sizeof(double) * static_cast<size_t>(most + 4 + nseg) * Zs));
+    double *ws_pi = c->d_exp_gws;
+    double *ws_x[2] = {ws_pi + static_cast<size_t>(most) * Zs, ws_pi + static_cast<size_t>(most + 1) * Zs};
+    double *ws_mu[2] = {ws_pi + static_cast<size_t>(most + 2) * Zs, ws_pi + static_cast<size_t>(most + 3) * Zs};
+    double *part = ws_pi + static_cast<size_t>(most + 4) * Zs;
+    const double *pd = c->d_pdrive;
+    const size_t zt = static_cast<size_t>(Z) * T;
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
+    auto hour_of = [pre](int s) { return s < pre ? s : s - pre; };
+
+    cpm::launch(cpm::k_exp_init, dim3(nblk(Z, cpm::kExpBlock), 1u), dim3(cpm::kExpBlock), 0, c->stream, d_pi0, pd, static_cast<size_t>(0), Z, Zs, ws_pi,
+                ws_x[0], static_cast<double *>(nullptr), static_cast<double *>(nullptr), static_cast<size_t>(0));
+    HIP_TRY(hipGetLastError());
+    for (int s = 0; s + 1 < steps; ++s) {
+        const int t = hour_of(s), t_next = hour_of(s + 1);
+        launch_exp_hour<1>(c, t, pd + static_cast<size_t>(t) * Z, pd + static_cast<size_t>(t_next) * Z, 0, ws_pi + static_cast<size_t>(s) * Zs, ws_x[s & 1],
+                           ws_pi + static_cast<size_t>(s + 1) * Zs, ws_x[(s + 1) & 1], nullptr, nullptr, 0, Zs, 1);
+        HIP_TRY(hipGetLastError());
+    }
+
+    const double *mu = gnext;  // (nullptr: zero by construction, the product of the last operator is skipped)
+    for (int s = steps - 1; s >= 0; --s) {
+        const int t = hour_of(s), j = s - pre;
+        const size_t row = static_cast<size_t>(t) * Z;
+        if (mu) {
+            const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg));
+            if (Z & 1) cpm::launch(cpm::k_exp_grad_u<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, mu, Z, Zs, seg_len, part);
+            else cpm::launch(cpm::k_exp_grad_u<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, mu, Z, Zs, seg_len, part);
+            HIP_TRY(hipGetLastError());
+        }
+        double *mu_out = (s == 0 && grad_pi0) ? grad_pi0 : ws_mu[s & 1];
+        const double *gp = j >= 0 ? cot + static_cast<size_t>(j) * Z : nullptr;
+        const double *gd = j >= 0 ? cot + zt + static_cast<size_t>(j) * Z : nullptr;
+        cpm::launch(cpm::k_exp_grad_finish, dim3(nblk(Z, cpm::kFinishBlock)), dim3(cpm::kFinishBlock), 0, c->stream, part, nseg, Zs, c->d_last + row,
+                    c->d_exp_ell + row, c->d_exp_r + row, pd + row, ws_pi + static_cast<size_t>(s) * Zs, mu, gp, gd, Z, s < pre ? 1 : 0, mu_out,
+                    grad_pd + row);
+        HIP_TRY(hipGetLastError());
+        mu = mu_out;
+    }
+    return CPM_OK;
+}
+
+int32_t expected_grad_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                               double *grad_pd, double *grad_pi0)
+{
+    const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T);
+    if (pi0)
+        for (size_t z = 0; z < Z; ++z)
+            if (!std::isfinite(pi0[z]) || pi0[z] < 0.0) return fail(CPM_ERR_ARG, "expected: pi0 of zone %lld is NaN, infinite or negative", (long long)z + 1);
+    for (size_t i = 0; i < zt; ++i)
+        if (!std::isfinite(g_parking[i]) || !std::isfinite(g_driving[i]))
+            return fail(CPM_ERR_ARG, "expected_grad: the cotangent of zone %lld, hour %lld is not finite", (long long)(i % Z) + 1, (long long)(i / Z) + 1);
+    if (g_next)
+        for (size_t z = 0; z < Z; ++z)
+            if (!std::isfinite(g_next[z])) return fail(CPM_ERR_ARG, "expected_grad: g_next of zone %lld is not finite", (long long)z + 1);
+    if (!c->d_exp_gio) HIP_TRY(hipMalloc(&c->d_exp_gio, sizeof(double) * (3 * zt + 3 * Z)));
+    double *d_cot = c->d_exp_gio, *d_gnext = d_cot + 2 * zt, *d_grad = d_gnext + Z, *d_gpi0 = d_grad + zt, *d_pi0 = d_gpi0 + Z;
+    HIP_TRY(hipMemcpyAsync(d_cot, g_parking, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_cot + zt, g_driving, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+    if (g_next) HIP_TRY(hipMemcpyAsync(d_gnext, g_next, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    int32_t rc = expected_grad_enqueue(c, pi0 ? d_pi0 : nullptr, flags, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr);
+    if (rc != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(grad_pd, d_grad, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    if (grad_pi0) HIP_TRY(hipMemcpyAsync(grad_pi0, d_gpi0, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1545,6 +1632,8 @@ int32_t cpm_destroy(cpm_ctx *c)
     dfree(c->d_exp_wpart);
     dfree(c->d_exp_trav);
     dfree(c->d_exp_tpart);
+    dfree(c->d_exp_gws);
+    dfree(c->d_exp_gio);
     dfree(c->d_ds_cells);
     dfree(c->d_ds_cnt);
     dfree(c->d_sp);
@@ -3004,6 +3093,37 @@ int64_t cpm_expected_trip_builds(const cpm_ctx *c)
     if (rc != CPM_OK) return rc;
     if (!c) return fail(CPM_ERR_ARG, "null context");
     return c->exp_trip_builds;
+}
+
+// ------------------------------------------------------------------ adjoint of the expected densities (include/cpm_expected_grad.h)
+
+int32_t cpm_expected_grad_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext, void *d_grad_p_drive,
+                              void *d_grad_pi0)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_grad_dev: null d_cotangent");
+    if (!d_grad_p_drive) return fail(CPM_ERR_ARG, "expected_grad_dev: null d_grad_p_drive");
+    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
+    return expected_grad_enqueue(c, static_cast<const double *>(d_pi0), flags, static_cast<const double *>(d_cotangent), static_cast<const double *>(d_gnext),
+                                 static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0));
+}
+
+int32_t cpm_expected_grad(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                          double *grad_p_drive, double *grad_pi0)
+{
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_grad: null cotangents");
+    if (!grad_p_drive) return fail(CPM_ERR_ARG, "expected_grad: null grad_p_drive");
+    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
+    return expected_grad_blocking(c, pi0, flags, g_parking, g_driving, g_next, grad_p_drive, grad_pi0);
 }
 
 // ------------------------------------------------------------------ batch (include/cpm_batch.h)

@@ -83,6 +83,69 @@ def expected_objectives(parking_density, driving_density, measured_activity=None
     return out
 
 
+# ------------------------------------------------------------------ host cotangents of the noise-free objectives (for Sampler.expected_grad)
+def _minmax_mse_grad(v, m, axis):
+    """d/dv of mean over `axis` of ((v - lo) / (hi - lo) - m)^2, lo / hi the minimum / maximum of v along `axis` (the first one where
+    several tie): the direct term, and the terms through lo and hi at the argmin and the argmax.  Slices with hi == lo give 0."""
+    v, m = np.asarray(v, dtype=np.float64), np.asarray(m, dtype=np.float64)
+    n = v.shape[axis]
+    imin, imax = np.expand_dims(v.argmin(axis=axis), axis), np.expand_dims(v.argmax(axis=axis), axis)
+    lo, hi = np.take_along_axis(v, imin, axis), np.take_along_axis(v, imax, axis)
+    rng = hi - lo
+    ok = rng != 0
+    safe = np.where(ok, rng, 1.0)
+    vn = (v - lo) / safe
+    e = 2.0 * (vn - m) / n                                    # d / d(vn)
+    g = e / safe
+    np.put_along_axis(g, imin, np.take_along_axis(g, imin, axis) - (e * (1.0 - vn)).sum(axis=axis, keepdims=True) / safe, axis)
+    np.put_along_axis(g, imax, np.take_along_axis(g, imax, axis) - (e * vn).sum(axis=axis, keepdims=True) / safe, axis)
+    return np.where(ok, g, 0.0)
+
+
+def traffic_activity_error_grad(driving, measured):
+    """(Z, T): the derivative of traffic_activity_error(traffic_activity(driving), measured) with respect to driving[z, t] -- the same
+    for every zone of an hour, since the activity reads the hours' sums -- with the min-max normalisation's terms at the argmin and the
+    argmax hour.  The cotangent g_driving of Sampler.expected_grad for the objective "activity_error"."""
+    d = np.asarray(driving, dtype=np.float64)
+    g = _minmax_mse_grad(d.sum(axis=0), measured, 0)
+    return np.asfortranarray(np.broadcast_to(g[None, :], d.shape))
+
+
+def parking_density_error_grad(parking, measured):
+    """(Z, T): the derivative of parking_density_error(parking, 1, measured) with respect to the density parking[z, t]: per valid zone
+    the min-max normalised error's derivative, with its argmin and argmax terms, over the number of valid zones; 0 for a zone that is
+    not valid (unmeasured or flat).  The cotangent g_parking of Sampler.expected_grad for the objective "parking_error"."""
+    p = np.asarray(parking, dtype=np.float64)
+    m = np.asarray(measured, dtype=np.float64)
+    valid = (m.sum(axis=1) != 0) & (p.max(axis=1) != p.min(axis=1))
+    if not valid.any():
+        return np.zeros(p.shape, order="F")
+    g = _minmax_mse_grad(p, m, 1) / float(valid.sum())
+    return np.asfortranarray(np.where(valid[:, None], g, 0.0))
+
+
+def a_drive_grad(w_sec):
+    """(Z, T): the derivative of the noise-free A_drive = sum(driving * w_sec) / (T * 3600) with respect to driving[z, t], from
+    Sampler.expected_trip()'s w_sec.  The cotangent g_driving of Sampler.expected_grad for the objective "A_drive"."""
+    w = np.asarray(w_sec, dtype=np.float64)
+    return np.asfortranarray(w / (w.shape[1] * 3600.0))
+
+
+def p_drive_param_grads(grad_p_drive, s, p_min, p_max, e_drive):
+    """(d_p_min, d_p_max, d_e_drive): the chain rule through p_drive = p_min + (p_max - p_min) * s^e_drive (createpdrive.jl:22-33), s the
+    table build_p_drive(0, 1, 1) returns.  The sums run over the entries with grad_p_drive != 0 only: an entry whose p_drive is not
+    strictly inside (0, 1) has gradient 0 (include/cpm_expected_grad.h), whatever s holds there (NaN included).  d(s^e)/de is
+    s^e * ln s, and 0 at s = 0."""
+    g = np.asarray(grad_p_drive, dtype=np.float64)
+    s = np.asarray(s, dtype=np.float64)
+    on = g != 0
+    g, s = g[on], s[on]
+    with np.errstate(all="ignore"):
+        se = np.power(s, float(e_drive))
+        sel = np.where(s > 0, se * np.log(np.where(s > 0, s, 1.0)), 0.0)
+    return (float(np.sum(g * (1.0 - se))), float(np.sum(g * se)), float(np.sum(g * (float(p_max) - float(p_min)) * sel)))
+
+
 def parking_density_zone_errors(parking, C, measured):
     """The definition of include/cpm_objectives.h on the host, one IEEE f64 operation per step and in its order: (err (Z,) float64
     with -1.0 for a zone that is not valid, valid (Z,) bool).  A zone is valid when its measured row, added in hour order, is != 0 and
@@ -151,6 +214,7 @@ class Evaluator:
     device_objectives: bool = False   # reduce the counts on the device (include/cpm_objectives.h): the host reads 4 + 2*T words per point
     _e_dest: object = field(default=None, repr=False)
     _pipe: object = field(default=None, repr=False)
+    _s_table: object = field(default=None, repr=False)   # build_p_drive(0, 1, 1): the datamatrix's own table, for expected_gradient
 
     def __post_init__(self):
         if self.measured_parking is not None:   # Julia order, like the count tensors: the error is evaluated hour-major on contiguous rows
@@ -232,6 +296,33 @@ class Evaluator:
         self._install_dest(pts[0].e_dest)
         self.sampler.build_p_drive_batch([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts])
         return self._expected_from_device(pts, ivp, True)
+
+    def expected_gradient(self, pt, objective, ivp=True):
+        """The gradient of one noise-free objective of evaluate_expected(pt, ivp) -- "activity_error", "parking_error" or "A_drive" -- by
+        one backward pass (Sampler.expected_grad): dict(objective, value, grad_p_drive (Z, T), grad_pi0 (Z,), d_p_min, d_p_max,
+        d_e_drive).  The parameter derivatives are the chain rule through p_drive = p_min + (p_max - p_min) * s^e_drive with
+        s = build_p_drive(0, 1, 1), cached here (it depends on the datamatrix alone); pt's own tables are installed when this returns."""
+        if objective not in ("activity_error", "parking_error", "A_drive"):
+            raise ValueError(f"expected_gradient: unknown objective {objective!r}")
+        s = self.sampler
+        if self._s_table is None:
+            self._s_table = s.build_p_drive(0.0, 1.0, 1.0)
+        r = self.evaluate_expected(pt, ivp)                       # (installs pt's tables: the table above is replaced)
+        zero = np.zeros((s.Z, s.T), order="F")
+        if objective == "activity_error":
+            if self.measured_activity is None:
+                raise ValueError("expected_gradient: activity_error needs measured_activity")
+            gp, gd = zero, traffic_activity_error_grad(r["driving"], self.measured_activity)
+        elif objective == "parking_error":
+            if self.measured_parking is None:
+                raise ValueError("expected_gradient: parking_error needs measured_parking")
+            gp, gd = parking_density_error_grad(r["parking"], self.measured_parking), zero
+        else:
+            gp, gd = zero, a_drive_grad(s.expected_trip()[0])
+        g = s.expected_grad(gp, gd, ivp=ivp)
+        d_min, d_max, d_e = p_drive_param_grads(g["grad_p_drive"], self._s_table, pt.p_min, pt.p_max, pt.e_drive)
+        return dict(objective=objective, value=r[objective], grad_p_drive=g["grad_p_drive"], grad_pi0=g["grad_pi0"],
+                    d_p_min=d_min, d_p_max=d_max, d_e_drive=d_e)
 
     # -- device objectives: the record of include/cpm_objectives.h in the place of the count tensor --
     def _from_record(self, pt, rec):

@@ -639,6 +639,29 @@ class Sampler:
                                                    C.c_void_p(int(d_travel_ptr)) if d_travel_ptr else None,
                                                    C.c_void_p(int(d_totals_ptr)) if d_totals_ptr else None))
 
+    # -- the adjoint of the expected densities (include/cpm_expected_grad.h): gradients for p_drive and pi0 in one backward pass --
+    def expected_grad(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None):
+        """The gradient of L = <g_parking, parking> + <g_driving, driving> + <g_next, pi_next> over expected()'s outputs at the installed
+        tables, blocking: dict(grad_p_drive (Z, T) float64 F-order, grad_pi0 (Z,)).  g_parking / g_driving: (Z, T) cotangents, i.e. the
+        derivative of an objective with respect to expected()'s densities; g_next: (Z,) or None (zeros).  grad_p_drive is exactly 0
+        wherever the installed p_drive is not strictly inside (0, 1).  pi0, ivp: as for expected()."""
+        a = self._pi0(pi0)
+        gp = np.asfortranarray(_f64(g_parking, (self.Z, self.T)))
+        gd = np.asfortranarray(_f64(g_driving, (self.Z, self.T)))
+        gn = None if g_next is None else np.ascontiguousarray(_f64(g_next, (self.Z,)))
+        grad = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        grad_pi0 = np.zeros(self.Z, dtype=np.float64)
+        _lib.check(self._L.cpm_expected_grad(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0)))
+        return dict(grad_p_drive=grad, grad_pi0=grad_pi0)
+
+    def expected_grad_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0):
+        """Enqueue on the context's stream: d_cotangent_ptr = device address of float64[2][T][Z] (g_parking, then g_driving, laid out
+        like expected_dev's tensor); d_grad_p_drive_ptr = device address of float64[T][Z]; d_pi0_ptr / d_gnext_ptr = device address of
+        float64[Z] or 0 (uniform / zeros); d_grad_pi0_ptr = device address of float64[Z] or 0 (not wanted)."""
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        _lib.check(self._L.cpm_expected_grad_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr),
+                                                 p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr)))
+
     def last_kernel_ms(self):
         buf = (C.c_float * 8192)()
         n = C.c_int32(0)
