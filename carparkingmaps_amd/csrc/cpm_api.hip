@@ -41,6 +41,7 @@
 #include "cpm_expected.h"
 #include "cpm_expected_travel.h"
 #include "cpm_expected_grad.h"
+#include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
 
@@ -83,6 +84,25 @@ void dfree(T *&p)
     p = nullptr;
 }
 
+// The owners of the context's allocations (cpm_buf.h): freed by their destructors, grown by reserve(), whose hipError_t goes through
+// HIP_TRY like that of any other call.
+struct DevAlloc {
+    using error = hipError_t;
+    static constexpr error ok = hipSuccess;
+    static error alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void *p) { (void)hipFree(p); }
+};
+struct PinnedAlloc {
+    using error = hipError_t;
+    static constexpr error ok = hipSuccess;
+    static error alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes); }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+template <typename T>
+using DevBuf = cpm::Buf<T, DevAlloc>;
+template <typename T>
+using PinnedBuf = cpm::Buf<T, PinnedAlloc>;
+
 inline unsigned nblk(int64_t n, int b) { return static_cast<unsigned>((n + b - 1) / b); }
 
 }  // namespace
@@ -96,96 +116,90 @@ struct cpm_ctx {
     hipStream_t stream = nullptr;      // what the context enqueues on: the caller's (cpm_set_stream) or own_stream
     bool have_stream = false;
     // tables
+    // (d_pdrive / d_thr and d_last / d_ckpt are plain pointers, freed by cpm_destroy: FleetTable points the first two into the batch
+    //  tables for a step and ensure_full_cdf nulls the other two around one launch -- an owner is never re-pointed)
     double *d_pdrive = nullptr;  // [T][Z]
-    double *d_p = nullptr;       // [T][Z dest][Z origin] p_destin as the reference lays it out (cpm_set_p_dest, cpm_build_p_dest, the synthetic
+    DevBuf<double> d_p;          // [T][Z dest][Z origin] p_destin as the reference lays it out (cpm_set_p_dest, cpm_build_p_dest, the synthetic
                                  // tables).  Resident: the row tables below are derived from it in one pass (k_build_rows), ties walk it
                                  // (search_exact_ckpt)
-    double *d_cdf = nullptr;     // [T][Z][Zp] canonical f64 CDF rows: built on first need (ensure_full_cdf) -- the car and exact-layout
+    DevBuf<double> d_cdf;        // [T][Z][Zp] canonical f64 CDF rows: built on first need (ensure_full_cdf) -- the car and exact-layout
     bool cdf_full = false;       // kernels and cpm_get_cdf_row read them, the grouped path never does
-    uint32_t *d_hi = nullptr;    // [T][Z][RW] row packs: guide + high words of the CDF (cpm_grouped.h)
+    DevBuf<uint32_t> d_hi;       // [T][Z][RW] row packs: guide + high words of the CDF (cpm_grouped.h)
     double *d_last = nullptr;    // [T][Z] row totals
     double *d_ckpt = nullptr;    // [T][nck][Z] every 32nd value of the running sums (exact fallback of the grouped path)
     long long *d_thr = nullptr;  // [T][Z] Bernoulli thresholds of p_drive (k_build_thr), rebuilt whenever p_drive changes
     int Zq = 0;
-    double *d_dm = nullptr;      // [2][T][Z][Z] (reference layout)
-    double *d_dist = nullptr;    // [Z][Z]
-    double2 *d_tt = nullptr;          // [T][Z][Z] (mean, std) origin-major: what the grouped path's travel kernel gathers from (cpm_grouped.h)
+    DevBuf<double> d_dm;         // [2][T][Z][Z] (reference layout)
+    DevBuf<double> d_dist;       // [Z][Z]
+    DevBuf<double2> d_tt;             // [T][Z][Z] (mean, std) origin-major: what the grouped path's travel kernel gathers from (cpm_grouped.h)
     bool tt_valid = false;
     // the same as sparse rows (cpm_grouped.h, k_tts_*), when the largest row fits LDS: what the travel kernel stages per (origin, hour)
-    uint2 *d_tts_words = nullptr;
-    uint32_t *d_tts_off = nullptr;
-    cpm::TravelCell *d_tts_cells = nullptr;
-    size_t tts_cells_cap = 0, tts_lds = 0;
+    DevBuf<uint2> d_tts_words;
+    DevBuf<uint32_t> d_tts_off;
+    DevBuf<cpm::TravelCell> d_tts_cells;
+    size_t tts_lds = 0;
     bool tts_valid = false;
     bool tts_fixed = false;  // the travel rows are those of the compact dataset: fixed stride kDsCap, counts in d_ds_cnt
     // the current datamatrix as compact rows (cpm_dataset.h: ONE sweep of it; valid until it changes), when it is sparse enough
-    cpm::DsCell *d_ds_cells = nullptr;  // [T*Z][kDsCap] cells of every (hour, origin), sorted by destination
-    uint32_t *d_ds_cnt = nullptr;       // [T*Z] cells per row; then {longest row, a row outgrew its capacity}
-    uint32_t *h_ds_stats = nullptr;     // pinned twin of those two words
+    DevBuf<cpm::DsCell> d_ds_cells;     // [T*Z][kDsCap] cells of every (hour, origin), sorted by destination
+    DevBuf<uint32_t> d_ds_cnt;          // [T*Z] cells per row; then {longest row, a row outgrew its capacity}
+    PinnedBuf<uint32_t> h_ds_stats;     // pinned twin of those two words
     bool ds_valid = false;              // the rows describe the current datamatrix (ds_ok: and are usable)
     bool ds_ok = false;
     int ds_max = 0;                     // longest row
     // ... and the p_destin tables built from them (k_ds_pdest): sparse packs in d_hi, what a tie walks in these three (owned by the
     // TABLE: they stay whole when the next dataset's cells arrive)
-    double *d_sp = nullptr;             // [T*Z][kDsCap] normalised p of every row's cells
-    uint32_t *d_sj = nullptr;           // ... their destinations
-    uint32_t *d_scnt = nullptr;         // [T*Z] cells per row
+    DevBuf<double> d_sp;                // [T*Z][kDsCap] normalised p of every row's cells
+    DevBuf<uint32_t> d_sj;              // ... their destinations
+    DevBuf<uint32_t> d_scnt;            // [T*Z] cells per row
     bool sparse_tables = false;         // the installed p_destin tables are of that kind: d_p holds p_destin only when p_dense_valid
     bool p_dense_valid = false;
     bool tables_uploaded = false;       // ... or from an uploaded p_destin (cpm_upload.h, CPM_OPT_SPARSE_UPLOAD): the three arrays are all they come from
     bool sparse_upload = false;         // CPM_OPT_SPARSE_UPLOAD: cpm_set_p_dest tries the sparse route
-    uint32_t *d_up_stats = nullptr;     // {longest row, a row outgrew kDsCap} of k_up_compact, and their pinned twin
-    uint32_t *h_up_stats = nullptr;
+    DevBuf<uint32_t> d_up_stats;        // {longest row, a row outgrew kDsCap} of k_up_compact, and their pinned twin
+    PinnedBuf<uint32_t> h_up_stats;
     double tab_e_dest = 2.0;            // the exponent they were built with (cpm_refresh_tables)
     int tab_e_int = 1;
-    size_t hi_words_alloc = 0;          // words d_hi was allocated for
     int pk_G = 0, pk_Zc = 0;            // geometry of the packs in d_hi (with Zq): guide bits, entries in front of the pad
-    double *d_pdrive_mean = nullptr;  // [T][Z] mean_sum of createpdrive (src/createpdrive.jl:10-21): depends on datamatrix and dist only,
+    DevBuf<double> d_pdrive_mean;     // [T][Z] mean_sum of createpdrive (src/createpdrive.jl:10-21): depends on datamatrix and dist only,
     bool pdrive_mean_valid = false;   // so the model-selection sweep (p_min, p_max, e_drive vary) computes it once
     bool have_pdrive = false, have_cdf = false, have_dmat = false, have_dist = false;
     bool have_dm() const { return have_dmat && have_dist; }
     // cars
     int64_t C_total = 0, cpz = 0, n = 0;
     cpm::CarIndex cars{0, 1};     // local car i = global car cars.begin + i * cars.stride
-    uint32_t *d_zone0 = nullptr;  // [n] current zones
-    uint32_t *d_ztmp = nullptr;   // [n] ping-pong for the IVP
-    uint32_t *d_rec = nullptr;    // [T][n]
-    int32_t *d_flows = nullptr;   // [T][Z][Z] OD trip counts of the blocking cpm_resample_flows (allocated by its first call)
+    DevBuf<uint32_t> d_zone0;     // [n] current zones
+    DevBuf<uint32_t> d_ztmp;      // [n] ping-pong for the IVP
+    DevBuf<uint32_t> d_rec;       // [T][n]
+    DevBuf<int32_t> d_flows;      // [T][Z][Z] OD trip counts of the blocking cpm_resample_flows (allocated by its first call)
     // the same counts as compressed sparse rows (include/cpm_flows_csr.h): the blocking call's arrays, allocated by its first call
-    int64_t *d_csr_row_ptr = nullptr;  // [T*Z + 1]
-    int32_t *d_csr_dest = nullptr;     // [csr_cap]
-    int32_t *d_csr_count = nullptr;    // [csr_cap]
-    int64_t csr_cap = 0;
+    DevBuf<int64_t> d_csr_row_ptr;     // [T*Z + 1]
+    DevBuf<int32_t> d_csr_dest;        // [d_csr_dest.cap]
+    DevBuf<int32_t> d_csr_count;       // ... as many
     int64_t csr_nnz = -1;              // what the last blocking call reported (-1: there was none)
-    int32_t *d_flows_hour = nullptr;   // [Z*Z + 4] one hour's dense block: how the per-car families reach the CSR form
+    DevBuf<int32_t> d_flows_hour;      // [Z*Z + 4] one hour's dense block: how the per-car families reach the CSR form
     // parking stays (include/cpm_stays.h): the per-car side array of every stays call, and the blocking call's arrays
-    uint32_t *d_stay_last = nullptr;   // [stay_last_cap] since << 24 | zone (csrc/cpm_stays.h)
-    int64_t stay_last_cap = 0;
-    int32_t *d_stays = nullptr;        // [T][Z][T]
-    int32_t *d_stay_parked = nullptr;  // [Z][T]
+    DevBuf<uint32_t> d_stay_last;      // [>= n] since << 24 | zone (csrc/cpm_stays.h)
+    DevBuf<int32_t> d_stays;           // [T][Z][T]
+    DevBuf<int32_t> d_stay_parked;     // [Z][T]
     // charge (include/cpm_charge.h): the per-car side array of every charge call, and the blocking call's arrays
-    uint2 *d_ebat = nullptr;           // [ebat_cap] {since << 24 | zone, Wh} (csrc/cpm_charge.h)
-    int64_t ebat_cap = 0;
-    double *d_dist_rows = nullptr;     // [Z][Z] the distance matrix origin-major, built on first use, stale wherever d_dist is replaced
+    DevBuf<uint2> d_ebat;              // [>= n] {since << 24 | zone, Wh} (csrc/cpm_charge.h)
+    DevBuf<double> d_dist_rows;        // [Z][Z] the distance matrix origin-major, built on first use, stale wherever d_dist is replaced
     bool dist_rows_valid = false;
-    int64_t *d_chg_load = nullptr;     // [2][Z][T] charge | used
-    int32_t *d_chg_short = nullptr;    // [Z][T]
-    uint32_t *d_chg_zone_power = nullptr;  // [Z]
-    uint32_t *d_chg_soc = nullptr;     // [2][chg_soc_cap] soc_in | soc_out
-    int64_t chg_soc_cap = 0;
+    DevBuf<int64_t> d_chg_load;        // [2][Z][T] charge | used
+    DevBuf<int32_t> d_chg_short;       // [Z][T]
+    DevBuf<uint32_t> d_chg_zone_power;     // [Z]
+    DevBuf<uint32_t> d_chg_soc;        // [2][cap / 2] soc_in | soc_out
     // per-car day records (include/cpm_paths.h): the blocking call's array, kept from its first use, and the columns
     // cpm_paths_expand_dev writes where the caller wants no matrix
-    uint32_t *d_paths = nullptr;       // [T][n]
-    int64_t paths_cap = 0;
-    char *d_expand_cols = nullptr;     // [5][n] 8-byte words
-    int64_t expand_cap = 0;
-    int64_t rec_cap = 0;
+    DevBuf<uint32_t> d_paths;          // [T][n]
+    DevBuf<char> d_expand_cols;        // [5][n] 8-byte words
     bool have_state = false;
     // results
-    int64_t *d_counts = nullptr;  // [2*T*Z + 2]
-    int64_t *h_counts = nullptr;  // pinned twin: the blocking calls bring the whole tensor (status word included) over in one copy
-    int *d_err = nullptr;
-    int *h_err = nullptr;         // pinned twin of the validation flag
+    DevBuf<int64_t> d_counts;     // [2*T*Z + 2]
+    PinnedBuf<int64_t> h_counts;  // pinned twin: the blocking calls bring the whole tensor (status word included) over in one copy
+    DevBuf<int> d_err;
+    PinnedBuf<int> h_err;         // pinned twin of the validation flag
     // zone-bucket paths
     cpm::ExactWork zx;
     cpm::GroupedWork zg;
@@ -193,7 +207,7 @@ struct cpm_ctx {
     // absorb: the status word of every grouped step is copied to pinned host memory behind the step and looked at, without
     // waiting, when the next step is enqueued (the overflowed step itself is flagged in its own status word).
     bool grouped_overflowed = false;
-    long long *h_status = nullptr;      // pinned [2]: status word, largest heavy bucket of the step (GroupedWork::maxn)
+    PinnedBuf<long long> h_status;      // pinned [2]: status word, largest heavy bucket of the step (GroupedWork::maxn)
     hipEvent_t status_ev = nullptr;
     bool status_pending = false;
     // An IVP enqueued on the grouped layout writes the new state beside the old one; it is committed (or repeated) by
@@ -202,7 +216,7 @@ struct cpm_ctx {
     uint64_t ivp_seed = 0;
     int ivp_form = -1;                  // the hour form of the pending IVP attempt (GroupedWork::last_form behind its grouped_run)
     cpm::LaunchCells ivp_cells;         // ... and what its launch helpers launched (GroupedWork::last_cells), likewise
-    long long *h_ivp_status = nullptr;  // pinned [2], likewise
+    PinnedBuf<long long> h_ivp_status;  // pinned [2], likewise
     // what produced the results of the most recent step (CPM_INFO_LAST_KERNEL / _LAST_FORM), and the step attempts the library ran,
     // discarded and ran again so far (CPM_INFO_STEPS_REPEATED)
     int last_kernel = 0;
@@ -212,51 +226,45 @@ struct cpm_ctx {
     int last_hour = 0;                  // CPM_INFO_LAST_HOUR: 1 when hour T of the most recent step was a count-only launch (cpm_count.h)
     cpm::LaunchCells last_cells;        // CPM_INFO_CELL_*: the instantiations the most recent step launched, per role (all 0: none of these launchers ran)
     // batch tables and workspace (include/cpm_batch.h, cpm_batch.h)
-    int batch_B = 0, batch_alloc = 0;
-    double *d_pdrive_b = nullptr;       // [B][T][Z] the fleets' p_drive tables
-    long long *d_thr_b = nullptr;       // [B][T][Z] their Bernoulli thresholds
+    int batch_B = 0;
+    DevBuf<double> d_pdrive_b;          // [B][T][Z] the fleets' p_drive tables
+    DevBuf<long long> d_thr_b;          // [B][T][Z] their Bernoulli thresholds
     cpm::BatchWork zb;
-    int64_t *d_bcounts = nullptr;       // [B][2*T*Z + 2] the blocking batch call's count tensors, and their pinned twin
-    int64_t *h_bcounts = nullptr;
-    int bcounts_cap = 0;
+    DevBuf<int64_t> d_bcounts;          // [B][2*T*Z + 2] the blocking batch call's count tensors, and their pinned twin
+    PinnedBuf<int64_t> h_bcounts;
     // the asynchronous batch step's status words, ORed into one word and copied to pinned memory behind the step; looked at, without
     // waiting, when the next batch step is enqueued (as status_ev / h_status for the single path)
-    unsigned long long *d_bstatus = nullptr;
-    unsigned long long *h_bstatus = nullptr;
+    DevBuf<unsigned long long> d_bstatus;
+    PinnedBuf<unsigned long long> h_bstatus;
     hipEvent_t bstatus_ev = nullptr;
     bool bstatus_pending = false;
     // the sweep's objectives (include/cpm_objectives.h, cpm_objectives.h)
-    double *d_measured = nullptr;       // [T][Z] measured parking densities, and per zone whether its row sums to != 0
-    int *d_meas_flag = nullptr;         // [Z]
+    DevBuf<double> d_measured;          // [T][Z] measured parking densities, and per zone whether its row sums to != 0
+    DevBuf<int> d_meas_flag;            // [Z]
     bool have_measured = false;
-    double *d_obj_part = nullptr;       // [obj_ws_B][ceil(Z/256)] the workgroups' partial sums of the zone errors ...
-    int *d_obj_part_n = nullptr;        // ... and their counts of valid zones
-    int obj_ws_B = 0;
+    DevBuf<double> d_obj_part;          // [B][ceil(Z/256)] the workgroups' partial sums of the zone errors ...
+    DevBuf<int> d_obj_part_n;           // ... and their counts of valid zones
     // expected densities (include/cpm_expected.h, cpm_expected.h): per-table arrays, built on first use and stale wherever d_last is rebuilt
-    int *d_exp_ell = nullptr;           // [T][Z] last destination with p > 0 (Z: a zero row)
-    double *d_exp_r = nullptr;          // [T][Z] max(0, 1 - last)
-    int *d_exp_start = nullptr;         // [T][Z + 1] where each destination's origins begin in ...
-    int *d_exp_list = nullptr;          // [T][Z] ... the origins sorted by (ell, origin)
-    unsigned long long *d_exp_bad = nullptr;  // the first row whose total exceeds 1, and its pinned twin
-    unsigned long long *h_exp_bad = nullptr;
+    DevBuf<int> d_exp_ell;              // [T][Z] last destination with p > 0 (Z: a zero row)
+    DevBuf<double> d_exp_r;             // [T][Z] max(0, 1 - last)
+    DevBuf<int> d_exp_start;            // [T][Z + 1] where each destination's origins begin in ...
+    DevBuf<int> d_exp_list;             // [T][Z] ... the origins sorted by (ell, origin)
+    DevBuf<unsigned long long> d_exp_bad;     // the first row whose total exceeds 1, and its pinned twin
+    PinnedBuf<unsigned long long> h_exp_bad;
     bool exp_aux_valid = false;
-    double *d_exp_ws = nullptr;         // [4][exp_ws_B][Zs] pi and x, ping and pong
-    int exp_ws_B = 0;
-    double *d_exp_out = nullptr;        // [exp_out_B][2][T][Z] + [Z] + [Z]: the blocking calls' outputs, pi_next and pi_0
-    int exp_out_B = 0;
+    DevBuf<double> d_exp_ws;            // [4][cap / 4] pi and x, ping and pong, of as many fleets ([Zs] each) as it was last grown for
+    DevBuf<double> d_exp_out;           // [B][2][T][Z] + [Z] + [Z]: the blocking calls' outputs; pi_next and pi_0 end the allocation (exp_out_tail)
     // expected travel (include/cpm_expected_travel.h, cpm_expected_travel.h): the trip weights, built on first use and stale wherever
     // the p_destin tables (exp_aux_valid), d_dm or d_dist change
-    double *d_exp_w = nullptr;          // [2][T][Z] w_sec | w_km
-    double *d_exp_wpart = nullptr;      // [segments][2][T][Z] the destination segments' sums
+    DevBuf<double> d_exp_w;             // [2][T][Z] w_sec | w_km
+    DevBuf<double> d_exp_wpart;         // [segments][2][T][Z] the destination segments' sums
     bool exp_trip_valid = false;
     int64_t exp_trip_builds = 0;
-    double *d_exp_trav = nullptr;       // [exp_trav_B][2][T][Z] + [exp_trav_B][2]: the blocking calls' seconds | km and totals
-    int exp_trav_B = 0;
-    double *d_exp_tpart = nullptr;      // [exp_tpart_B][chunks][2] the chunks' sums of k_exp_travel, added in order by k_exp_travel_total
-    int exp_tpart_B = 0;
+    DevBuf<double> d_exp_trav;          // [B][2][T][Z] + [B][2]: the blocking calls' seconds | km and totals, B = cap / (2 T Z + 2)
+    DevBuf<double> d_exp_tpart;         // [B][chunks][2] the chunks' sums of k_exp_travel, added in order by k_exp_travel_total
     // the adjoint of the expected densities (include/cpm_expected_grad.h, cpm_expected_grad.h)
-    double *d_exp_gws = nullptr;        // [N + 4 + segments][Zs]: pi_s of the N = 2T - 1 operators, x ping and pong, mu ping and pong, the segments' sums
-    double *d_exp_gio = nullptr;        // [2][T][Z] + [Z] + [T][Z] + [Z] + [Z]: the blocking call's cotangents, G_next, grad_p_drive, grad_pi0 and pi_0
+    DevBuf<double> d_exp_gws;           // [N + 4 + segments][Zs]: pi_s of the N = 2T - 1 operators, x ping and pong, mu ping and pong, the segments' sums
+    DevBuf<double> d_exp_gio;           // [2][T][Z] + [Z] + [T][Z] + [Z] + [Z]: the blocking call's cotangents, G_next, grad_p_drive, grad_pi0 and pi_0
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -287,25 +295,20 @@ namespace {
 int32_t ensure_cars(cpm_ctx *c, int64_t n)
 {
     if (n == c->n && c->d_zone0) return CPM_OK;
-    dfree(c->d_zone0);
-    dfree(c->d_ztmp);
-    dfree(c->d_rec);
-    c->rec_cap = 0;
+    c->d_zone0.release();  // (exact-size, not grow-only: a smaller fleet gives the memory back, the per-car record with it)
+    c->d_ztmp.release();
+    c->d_rec.release();
     c->n = n;
     if (n > 0) {
-        HIP_TRY(hipMalloc(&c->d_zone0, sizeof(uint32_t) * n));
-        HIP_TRY(hipMalloc(&c->d_ztmp, sizeof(uint32_t) * n));
+        HIP_TRY(c->d_zone0.reserve(static_cast<size_t>(n)));
+        HIP_TRY(c->d_ztmp.reserve(static_cast<size_t>(n)));
     }
     return CPM_OK;
 }
 
 int32_t ensure_rec(cpm_ctx *c)
 {
-    int64_t need = c->n * c->T;
-    if (c->rec_cap >= need && c->d_rec) return CPM_OK;
-    dfree(c->d_rec);
-    HIP_TRY(hipMalloc(&c->d_rec, sizeof(uint32_t) * std::max<int64_t>(need, 1)));
-    c->rec_cap = need;
+    HIP_TRY(c->d_rec.reserve(static_cast<size_t>(c->n * c->T)));
     return CPM_OK;
 }
 
@@ -338,19 +341,15 @@ hipError_t launch_build_rows(cpm_ctx *c)
     const hipError_t e = cpm::lds_opt_in<cpm::k_build_rows<CDF, PACK>>(cpm::kRowLds);  // (two 64 x 65 f64 tiles)
     if (e != hipSuccess) return e;
     dim3 grid(nblk(c->Z, cpm::kRowTile), static_cast<unsigned>(c->T));
-    hipLaunchKernelGGL((cpm::k_build_rows<CDF, PACK>), grid, dim3(cpm::kRowBlock), cpm::kRowLds, c->stream, c->d_p, CDF ? c->d_cdf : nullptr,
-                       PACK ? c->d_hi : nullptr, c->d_last, c->d_ckpt, static_cast<int>(c->Z), c->Zp, cpm::pack_zq(static_cast<int>(c->Z)),
+    hipLaunchKernelGGL((cpm::k_build_rows<CDF, PACK>), grid, dim3(cpm::kRowBlock), cpm::kRowLds, c->stream, c->d_p, CDF ? c->d_cdf.get() : nullptr,
+                       PACK ? c->d_hi.get() : nullptr, c->d_last, c->d_ckpt, static_cast<int>(c->Z), c->Zp, cpm::pack_zq(static_cast<int>(c->Z)),
                        cpm::pack_guide_bits(static_cast<int>(c->Z)), c->d_err);
     return hipGetLastError();
 }
 
 int32_t ensure_hi(cpm_ctx *c, size_t words)
 {
-    if (c->d_hi && c->hi_words_alloc >= words) return CPM_OK;
-    dfree(c->d_hi);
-    c->hi_words_alloc = 0;
-    HIP_TRY(hipMalloc(&c->d_hi, sizeof(uint32_t) * std::max<size_t>(words, 1)));
-    c->hi_words_alloc = words;
+    HIP_TRY(c->d_hi.reserve(words));
     return CPM_OK;
 }
 
@@ -378,7 +377,7 @@ int32_t build_rows(cpm_ctx *c, bool with_cdf)
         int32_t rc_hi = ensure_hi(c, static_cast<size_t>(rows) * cpm::pack_row_words(c->Zq, c->pk_G));
         if (rc_hi != CPM_OK) return rc_hi;
     }
-    if (cdf && !c->d_cdf) HIP_TRY(hipMalloc(&c->d_cdf, sizeof(double) * static_cast<size_t>(rows) * c->Zp));
+    if (cdf) HIP_TRY(c->d_cdf.reserve(static_cast<size_t>(rows) * c->Zp));
     hipError_t e_rows;
     if (cdf && pack) e_rows = launch_build_rows<true, true>(c);
     else if (cdf) e_rows = launch_build_rows<true, false>(c);
@@ -397,7 +396,7 @@ int32_t ensure_dense_p(cpm_ctx *c)
 {
     if (!c->sparse_tables || c->p_dense_valid) return CPM_OK;
     const size_t bytes = sizeof(double) * c->Z * c->Z * c->T;
-    if (!c->d_p) HIP_TRY(hipMalloc(&c->d_p, bytes));
+    HIP_TRY(c->d_p.reserve(bytes / sizeof(double)));
     HIP_TRY(hipMemsetAsync(c->d_p, 0, bytes, c->stream));
     hipLaunchKernelGGL(cpm::k_ds_dense_p, dim3(cpm::ds_grid(c->T * c->Z)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_sp, c->d_sj, c->d_scnt,
                        cpm::kDsCap, c->T * c->Z, static_cast<int>(c->Z), c->d_p);
@@ -415,7 +414,7 @@ int32_t ensure_full_cdf(cpm_ctx *c)
         int32_t rc_p = ensure_dense_p(c);
         if (rc_p != CPM_OK) return rc_p;
     }
-    if (!c->d_cdf) HIP_TRY(hipMalloc(&c->d_cdf, sizeof(double) * static_cast<size_t>(c->T * c->Z) * c->Zp));
+    HIP_TRY(c->d_cdf.reserve(static_cast<size_t>(c->T * c->Z) * c->Zp));
     double *keep_last = c->d_last, *keep_ckpt = c->d_ckpt;  // (already built: this pass writes the CDF rows only)
     c->d_last = nullptr;
     c->d_ckpt = nullptr;
@@ -528,7 +527,7 @@ int32_t launch_step_car(cpm_ctx *c, const uint32_t *zin, uint32_t *out, int t, u
     dim3 grid(nblk(c->n, 256)), block(256);
     if (travel)
         cpm::launch(cpm::k_step_car<true>, grid, block, 0, c->stream, zin, out, pd, cdf, static_cast<int>(c->Z),
-                           c->Zp, c->n, c->cars, step, seed, c->d_dm, static_cast<int>(c->T), t, tt_sum);
+                           c->Zp, c->n, c->cars, step, seed, c->d_dm.get(), static_cast<int>(c->T), t, tt_sum);
     else
         cpm::launch(cpm::k_step_car<false>, grid, block, 0, c->stream, zin, out, pd, cdf, static_cast<int>(c->Z),
                            c->Zp, c->n, c->cars, step, seed, nullptr, static_cast<int>(c->T), t, nullptr);
@@ -573,9 +572,9 @@ int32_t ensure_dataset(cpm_ctx *c)
     }
     const int64_t rows = c->T * c->Z;
     const int W = static_cast<int>((c->Z + 31) / 32);
-    if (!c->d_ds_cells) HIP_TRY(hipMalloc(&c->d_ds_cells, sizeof(cpm::DsCell) * static_cast<size_t>(rows) * cpm::kDsCap));
-    if (!c->d_ds_cnt) HIP_TRY(hipMalloc(&c->d_ds_cnt, sizeof(uint32_t) * static_cast<size_t>(rows + 2)));
-    if (!c->h_ds_stats) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_ds_stats), 2 * sizeof(uint32_t)));
+    HIP_TRY(c->d_ds_cells.reserve(static_cast<size_t>(rows) * cpm::kDsCap));
+    HIP_TRY(c->d_ds_cnt.reserve(static_cast<size_t>(rows + 2)));
+    HIP_TRY(c->h_ds_stats.reserve(2));
     HIP_TRY(hipMemsetAsync(c->d_ds_cnt, 0, sizeof(uint32_t) * static_cast<size_t>(rows + 2), c->stream));
     hipLaunchKernelGGL(cpm::k_ds_cells, dim3(nblk(c->Z, 64), nblk(c->Z, cpm::kDsJB)), dim3(256), 0, c->stream, c->d_dm, c->d_ds_cells, c->d_ds_cnt,
                        static_cast<int>(c->Z), cpm::kDsCap, c->d_ds_cnt + rows);
@@ -587,13 +586,8 @@ int32_t ensure_dataset(cpm_ctx *c)
     const int zq_c = cpm::pack_zq(c->ds_max), g_c = cpm::pack_guide_bits(c->ds_max);
     const int dense_words = cpm::pack_row_words(cpm::pack_zq(static_cast<int>(c->Z)), cpm::pack_guide_bits(static_cast<int>(c->Z)));
     if (c->h_ds_stats[1] != 0 || 10 * cpm::pack_row_words(zq_c, g_c, 1) > 6 * dense_words) return CPM_OK;  // dense: the builders of cpm_tables.h
-    if (!c->d_tts_words) HIP_TRY(hipMalloc(&c->d_tts_words, sizeof(uint2) * static_cast<size_t>(rows) * W));
-    if (c->tts_cells_cap < static_cast<size_t>(rows) * cpm::kDsCap) {
-        dfree(c->d_tts_cells);
-        c->tts_cells_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_tts_cells, sizeof(cpm::TravelCell) * static_cast<size_t>(rows) * cpm::kDsCap));
-        c->tts_cells_cap = static_cast<size_t>(rows) * cpm::kDsCap;
-    }
+    HIP_TRY(c->d_tts_words.reserve(static_cast<size_t>(rows) * W));
+    HIP_TRY(c->d_tts_cells.reserve(static_cast<size_t>(rows) * cpm::kDsCap));
     const size_t lds_sort = sizeof(uint32_t) * 2 * W * cpm::kDsRows;
     hipLaunchKernelGGL(cpm::k_ds_sort, dim3(cpm::ds_grid(rows)), dim3(cpm::kDsThreads * cpm::kDsRows), lds_sort, c->stream, c->d_ds_cells, c->d_ds_cnt, cpm::kDsCap,
                        rows, static_cast<int>(c->Z), c->d_tts_words, W, c->d_tts_cells);
@@ -606,7 +600,7 @@ int32_t ensure_dataset(cpm_ctx *c)
         c->tts_valid = true;
         c->tts_fixed = true;
         c->tt_valid = true;
-        dfree(c->d_tt);  // (a dense table left over from a datamatrix whose rows did not fit)
+        c->d_tt.release();  // (a dense table left over from a datamatrix whose rows did not fit)
     }
     return CPM_OK;
 }
@@ -621,9 +615,9 @@ int32_t build_p_dest_sparse(cpm_ctx *c, double e_dest, int32_t e_is_integer, boo
     if (rc != CPM_OK || !c->ds_ok) return rc;
     const int64_t rows = c->T * c->Z;
     const int nc = c->ds_max, zq_c = cpm::pack_zq(nc), g_c = cpm::pack_guide_bits(nc);
-    if (!c->d_sp) HIP_TRY(hipMalloc(&c->d_sp, sizeof(double) * static_cast<size_t>(rows) * cpm::kDsCap));
-    if (!c->d_sj) HIP_TRY(hipMalloc(&c->d_sj, sizeof(uint32_t) * static_cast<size_t>(rows) * cpm::kDsCap));
-    if (!c->d_scnt) HIP_TRY(hipMalloc(&c->d_scnt, sizeof(uint32_t) * static_cast<size_t>(rows)));
+    HIP_TRY(c->d_sp.reserve(static_cast<size_t>(rows) * cpm::kDsCap));
+    HIP_TRY(c->d_sj.reserve(static_cast<size_t>(rows) * cpm::kDsCap));
+    HIP_TRY(c->d_scnt.reserve(static_cast<size_t>(rows)));
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     rc = ensure_hi(c, static_cast<size_t>(rows) * cpm::pack_row_words(zq_c, g_c, 1));
     if (rc != CPM_OK) return rc;
@@ -661,8 +655,8 @@ int32_t pack_uploaded_rows(cpm_ctx *c, int nc)
     int32_t rc = ensure_hi(c, static_cast<size_t>(rows) * cpm::pack_row_words(zq_c, g_c, 1));
     if (rc != CPM_OK) return rc;
     prof_begin(c, CPM_PROFILE_UPLOAD);
-    cpm::launch(cpm::k_up_pack, dim3(cpm::ds_grid(rows)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_sp, c->d_sj, c->d_scnt, cpm::kDsCap, rows, nc,
-                zq_c, g_c, c->d_hi, c->d_last);
+    cpm::launch(cpm::k_up_pack, dim3(cpm::ds_grid(rows)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_sp.get(), c->d_sj.get(), c->d_scnt.get(),
+                cpm::kDsCap, rows, nc, zq_c, g_c, c->d_hi.get(), c->d_last);
     prof_end(c, CPM_PROFILE_UPLOAD);
     HIP_TRY(hipGetLastError());
     c->Zq = zq_c;
@@ -680,17 +674,17 @@ int32_t upload_p_dest_sparse(cpm_ctx *c, bool *done)
     *done = false;
     if (!cpm::pack_row_fits(static_cast<int>(c->Z))) return CPM_OK;
     const int64_t rows = c->T * c->Z;
-    if (!c->d_sp) HIP_TRY(hipMalloc(&c->d_sp, sizeof(double) * static_cast<size_t>(rows) * cpm::kDsCap));
-    if (!c->d_sj) HIP_TRY(hipMalloc(&c->d_sj, sizeof(uint32_t) * static_cast<size_t>(rows) * cpm::kDsCap));
-    if (!c->d_scnt) HIP_TRY(hipMalloc(&c->d_scnt, sizeof(uint32_t) * static_cast<size_t>(rows)));
-    if (!c->d_up_stats) HIP_TRY(hipMalloc(&c->d_up_stats, 2 * sizeof(uint32_t)));
-    if (!c->h_up_stats) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_up_stats), 2 * sizeof(uint32_t)));
+    HIP_TRY(c->d_sp.reserve(static_cast<size_t>(rows) * cpm::kDsCap));
+    HIP_TRY(c->d_sj.reserve(static_cast<size_t>(rows) * cpm::kDsCap));
+    HIP_TRY(c->d_scnt.reserve(static_cast<size_t>(rows)));
+    HIP_TRY(c->d_up_stats.reserve(2));
+    HIP_TRY(c->h_up_stats.reserve(2));
     c->sparse_tables = false;  // (the compact rows of whatever table was installed are gone from here on)
     c->tables_uploaded = false;
     HIP_TRY(hipMemsetAsync(c->d_up_stats, 0, 2 * sizeof(uint32_t), c->stream));
     prof_begin(c, CPM_PROFILE_UPLOAD);
-    cpm::launch(cpm::k_up_compact, dim3(nblk(c->Z, 64), static_cast<unsigned>(c->T)), dim3(64), 0, c->stream, c->d_p, c->d_sp, c->d_sj, c->d_scnt,
-                static_cast<int>(c->Z), cpm::kDsCap, c->d_up_stats, c->d_err);
+    cpm::launch(cpm::k_up_compact, dim3(nblk(c->Z, 64), static_cast<unsigned>(c->T)), dim3(64), 0, c->stream, c->d_p.get(), c->d_sp.get(), c->d_sj.get(),
+                c->d_scnt.get(), static_cast<int>(c->Z), cpm::kDsCap, c->d_up_stats.get(), c->d_err.get());
     prof_end(c, CPM_PROFILE_UPLOAD);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_up_stats, c->d_up_stats, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -721,21 +715,13 @@ int32_t build_sparse_travel_rows(cpm_ctx *c)
     c->tts_fixed = false;
     const int64_t rows = c->T * c->Z;
     const int W = static_cast<int>((c->Z + 31) / 32);
-    if (!c->d_tts_words) HIP_TRY(hipMalloc(&c->d_tts_words, sizeof(uint2) * static_cast<size_t>(rows) * W));
-    if (!c->d_tts_off) HIP_TRY(hipMalloc(&c->d_tts_off, sizeof(uint32_t) * static_cast<size_t>(rows + 1)));
-    uint32_t *d_count = nullptr;
-    HIP_TRY(hipMalloc(&d_count, sizeof(uint32_t) * static_cast<size_t>(rows) + 16));
-    struct Scratch {
-        uint32_t *&p;
-        ~Scratch() { dfree(p); }
-    } scratch{d_count};
-    uint32_t *d_max = d_count + rows;                                            // (+ total: 8 B behind it, 8-aligned or not: read as bytes)
-    unsigned long long *d_total = nullptr;
-    HIP_TRY(hipMalloc(&d_total, sizeof(unsigned long long)));
-    struct Scratch2 {
-        unsigned long long *&p;
-        ~Scratch2() { dfree(p); }
-    } scratch2{d_total};
+    HIP_TRY(c->d_tts_words.reserve(static_cast<size_t>(rows) * W));
+    HIP_TRY(c->d_tts_off.reserve(static_cast<size_t>(rows + 1)));
+    DevBuf<uint32_t> d_count;  // (scratch of this call: the rows' counts, then the largest of them)
+    HIP_TRY(d_count.reserve(static_cast<size_t>(rows) + 4));
+    uint32_t *d_max = d_count + rows;
+    DevBuf<unsigned long long> d_total;
+    HIP_TRY(d_total.reserve(1));
     const dim3 tgrid(nblk(c->Z, 64), static_cast<unsigned>(c->T), cpm::kTtsSplit);
     hipLaunchKernelGGL(cpm::k_tts_bits, tgrid, dim3(64), 0, c->stream, c->d_dm, c->d_tts_words, static_cast<int>(c->Z), static_cast<int>(c->T), W);
     hipLaunchKernelGGL(cpm::k_tts_prefix, dim3(nblk(rows, 256)), dim3(256), 0, c->stream, c->d_tts_words, d_count, rows, W);
@@ -748,18 +734,13 @@ int32_t build_sparse_travel_rows(cpm_ctx *c)
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t lds = ((static_cast<size_t>(W) * sizeof(uint2) + 15) & ~static_cast<size_t>(15)) + static_cast<size_t>(h_max) * sizeof(cpm::TravelCell);
     if (lds > 32 * 1024 || h_total >= (1ull << 32)) return CPM_OK;  // dense rows: the travel kernel gathers from the dense table
-    if (h_total > c->tts_cells_cap) {
-        dfree(c->d_tts_cells);
-        c->tts_cells_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_tts_cells, sizeof(cpm::TravelCell) * std::max<size_t>(h_total, 1)));
-        c->tts_cells_cap = h_total;
-    }
+    HIP_TRY(c->d_tts_cells.reserve(h_total));
     hipLaunchKernelGGL(cpm::k_tts_cells, tgrid, dim3(64), 0, c->stream, c->d_dm, c->d_tts_words, c->d_tts_off, c->d_tts_cells,
                        static_cast<int>(c->Z), static_cast<int>(c->T), W);
     HIP_TRY(hipGetLastError());
     c->tts_lds = lds;
     c->tts_valid = true;
-    dfree(c->d_tt);  // (a dense table left over from a datamatrix whose rows did not fit)
+    c->d_tt.release();  // (a dense table left over from a datamatrix whose rows did not fit)
     return CPM_OK;
 }
 
@@ -790,7 +771,7 @@ int32_t ensure_travel_tables(cpm_ctx *c)
         if (rc_tts != CPM_OK) return rc_tts;
         if (!c->tts_valid) {
             const size_t cells = static_cast<size_t>(c->Z) * c->Z * c->T;
-            if (!c->d_tt) HIP_TRY(hipMalloc(&c->d_tt, sizeof(double2) * cells));
+            HIP_TRY(c->d_tt.reserve(cells));
             hipLaunchKernelGGL(cpm::k_build_travel_table, dim3(nblk(c->Z, cpm::kTtTile), nblk(c->Z, cpm::kTtTile), static_cast<unsigned>(c->T)),
                                dim3(cpm::kTtTile * 8), 0, c->stream, c->d_dm, c->d_tt, static_cast<int>(c->Z), static_cast<int>(c->T));
             HIP_TRY(hipGetLastError());
@@ -857,29 +838,17 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
     }
     if (c->n == 0) return CPM_OK;
     if (cd.any()) {  // the side array: every car where the day began with its initial charge, at the start of every attempt
-        if (c->ebat_cap < c->n) {
-            dfree(c->d_ebat);
-            c->d_ebat = nullptr;
-            c->ebat_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_ebat, sizeof(uint2) * static_cast<size_t>(c->n)));
-            c->ebat_cap = c->n;
-        }
+        HIP_TRY(c->d_ebat.reserve(static_cast<size_t>(c->n)));
         cd.ebat = c->d_ebat;
         // the origin's distances: a row of the context's origin-major copy of the distance matrix, built once per matrix
-        if (!c->d_dist_rows) HIP_TRY(hipMalloc(&c->d_dist_rows, sizeof(double) * static_cast<size_t>(c->Z) * c->Z));
+        HIP_TRY(c->d_dist_rows.reserve(static_cast<size_t>(c->Z) * c->Z));
         if (!c->dist_rows_valid) HIP_TRY(cpm::charge_launch_dist_rows(c->stream, c->d_dist, static_cast<int>(c->Z), c->d_dist_rows));
         c->dist_rows_valid = true;
         cd.dist = c->d_dist_rows;
         HIP_TRY(cpm::charge_launch_init(c->stream, c->d_zone0, c->n, static_cast<int>(c->Z), static_cast<int>(c->T), cd));
     }
     if (sd.any()) {  // the side array: every car "here since the day began", at the start of every attempt
-        if (c->stay_last_cap < c->n) {
-            dfree(c->d_stay_last);
-            c->d_stay_last = nullptr;
-            c->stay_last_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_stay_last, sizeof(uint32_t) * static_cast<size_t>(c->n)));
-            c->stay_last_cap = c->n;
-        }
+        HIP_TRY(c->d_stay_last.reserve(static_cast<size_t>(c->n)));
         sd.last = c->d_stay_last;
         HIP_TRY(hipMemsetAsync(sd.last, 0, sizeof(uint32_t) * static_cast<size_t>(c->n), c->stream));
     }
@@ -891,7 +860,7 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
         return CPM_OK;
     };
     if (fd.csr() && kernel != CPM_KERNEL_ZONE_GROUPED) {  // (k_flows_cars adds to a dense hour block, k_flows_csr_from_dense takes it apart)
-        if (!c->d_flows_hour) HIP_TRY(hipMalloc(&c->d_flows_hour, sizeof(int32_t) * (static_cast<size_t>(c->Z) * c->Z + 4)));
+        HIP_TRY(c->d_flows_hour.reserve(static_cast<size_t>(c->Z) * c->Z + 4));
         fd.hour_block = c->d_flows_hour;
     }
     unsigned long long *tt_sum = reinterpret_cast<unsigned long long *>(d_counts) + 2 * c->T * c->Z;
@@ -968,7 +937,7 @@ int32_t ivp_exact(cpm_ctx *c, uint64_t seed)
     for (int t = 0; t < c->T - 1; ++t) {
         int32_t rc = launch_step_car(c, c->d_zone0, c->d_ztmp, t, static_cast<uint32_t>(t), seed, false, nullptr);
         if (rc != CPM_OK) return rc;
-        std::swap(c->d_zone0, c->d_ztmp);  // flag bit is masked off by every reader
+        c->d_zone0.swap(c->d_ztmp);  // flag bit is masked off by every reader
     }
     return CPM_OK;
 }
@@ -998,7 +967,7 @@ int32_t finish_ivp(cpm_ctx *c)
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->zg.set_parts(static_cast<uint32_t>(c->h_ivp_status[1]), static_cast<uint32_t>(c->h_ivp_status[1] >> 32));
     auto commit = [&]() -> int32_t {
-        std::swap(c->d_zone0, c->d_ztmp);
+        c->d_zone0.swap(c->d_ztmp);
         c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
         c->last_form = c->ivp_form;
         c->last_batch_fleets = 0;
@@ -1085,11 +1054,39 @@ int32_t resample_blocking(cpm_ctx *c, uint64_t seed, uint32_t flags, cpm::SideDe
     return rc;
 }
 
+// The kernel choice is overridden for one blocking call only, whichever way the call ends: by the call itself (cpm_resample's compat
+// route takes the per-car kernel) or by resample_blocking's fallback to a layout that cannot overflow.
+struct KernelGuard {
+    cpm_ctx *c;
+    int saved;
+    explicit KernelGuard(cpm_ctx *c_) : c(c_), saved(c_->kernel) {}
+    KernelGuard(const KernelGuard &) = delete;
+    ~KernelGuard() { c->kernel = saved; }
+};
+
+// What every blocking resample call does between its argument checks and its own buffers: the guard, then the pending IVP -- committed
+// with the caller's kernel choice, not with an override the call applies behind this.  rc: finish_ivp's.
+struct BlockingCall {
+    KernelGuard guard;
+    int32_t rc;
+    explicit BlockingCall(cpm_ctx *c) : guard(c), rc(finish_ivp(c)) {}
+};
+
+// fleet b's count tensor from h (c->h_counts unless the batch call names a block of its own) into the caller's arrays
+void copy_counts(const cpm_ctx *c, int64_t *parking, int64_t *driving, int64_t *sum_tt_q16, int b = 0, const int64_t *h = nullptr)
+{
+    if (!h) h = c->h_counts;
+    const size_t zt = static_cast<size_t>(c->Z * c->T);
+    std::memcpy(parking + b * zt, h, sizeof(int64_t) * zt);
+    std::memcpy(driving + b * zt, h + zt, sizeof(int64_t) * zt);
+    if (sum_tt_q16) sum_tt_q16[b] = h[2 * zt];
+}
+
 // mean_sum of createpdrive (src/createpdrive.jl:10-21), once per datamatrix / distance matrix: from the dataset's compact rows, or the
 // Z x Z x T pass over the datamatrix
 int32_t ensure_pdrive_mean(cpm_ctx *c)
 {
-    if (!c->d_pdrive_mean) HIP_TRY(hipMalloc(&c->d_pdrive_mean, sizeof(double) * c->Z * c->T));
+    HIP_TRY(c->d_pdrive_mean.reserve(static_cast<size_t>(c->Z * c->T)));
     if (c->pdrive_mean_valid) return CPM_OK;
     int32_t rc_ds = ensure_dataset(c);
     if (rc_ds != CPM_OK) return rc_ds;
@@ -1108,16 +1105,12 @@ int32_t ensure_pdrive_mean(cpm_ctx *c)
 // ------------------------------------------------------------------ batch (include/cpm_batch.h)
 int32_t ensure_batch_tables(cpm_ctx *c, int B)
 {
-    if (c->batch_alloc >= B && c->d_pdrive_b) return CPM_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (the tables in use by steps in flight are replaced)
-    dfree(c->d_pdrive_b);
-    dfree(c->d_thr_b);
-    c->batch_alloc = 0;
-    c->batch_B = 0;
     const size_t cells = static_cast<size_t>(B) * c->T * c->Z;
-    HIP_TRY(hipMalloc(&c->d_pdrive_b, sizeof(double) * cells));
-    HIP_TRY(hipMalloc(&c->d_thr_b, sizeof(long long) * cells));
-    c->batch_alloc = B;
+    if (c->d_pdrive_b.fits(cells) && c->d_thr_b.fits(cells)) return CPM_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the tables in use by steps in flight are replaced)
+    c->batch_B = 0;
+    HIP_TRY(c->d_pdrive_b.reserve(cells));
+    HIP_TRY(c->d_thr_b.reserve(cells));
     return CPM_OK;
 }
 
@@ -1223,19 +1216,20 @@ int32_t ensure_exp_aux(cpm_ctx *c)
     if (rc != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const size_t rows = static_cast<size_t>(Z) * T;
-    if (!c->d_exp_ell) HIP_TRY(hipMalloc(&c->d_exp_ell, sizeof(int) * rows));
-    if (!c->d_exp_r) HIP_TRY(hipMalloc(&c->d_exp_r, sizeof(double) * rows));
-    if (!c->d_exp_start) HIP_TRY(hipMalloc(&c->d_exp_start, sizeof(int) * (rows + T)));
-    if (!c->d_exp_list) HIP_TRY(hipMalloc(&c->d_exp_list, sizeof(int) * rows));
-    if (!c->d_exp_bad) HIP_TRY(hipMalloc(&c->d_exp_bad, sizeof(unsigned long long)));
-    if (!c->h_exp_bad) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_exp_bad), sizeof(unsigned long long)));
+    HIP_TRY(c->d_exp_ell.reserve(rows));
+    HIP_TRY(c->d_exp_r.reserve(rows));
+    HIP_TRY(c->d_exp_start.reserve(rows + T));
+    HIP_TRY(c->d_exp_list.reserve(rows));
+    HIP_TRY(c->d_exp_bad.reserve(1));
+    HIP_TRY(c->h_exp_bad.reserve(1));
     HIP_TRY(hipMemsetAsync(c->d_exp_bad, 0xff, sizeof(unsigned long long), c->stream));
     const dim3 grid(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T));
-    cpm::launch(cpm::k_exp_aux, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p, c->d_last, Z, c->d_exp_ell, c->d_exp_r, c->d_exp_bad);
+    cpm::launch(cpm::k_exp_aux, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p.get(), c->d_last, Z, c->d_exp_ell.get(), c->d_exp_r.get(),
+                c->d_exp_bad.get());
     HIP_TRY(hipGetLastError());
     const size_t lds = sizeof(int) * static_cast<size_t>(Z);
     HIP_TRY(cpm::lds_opt_in<cpm::k_exp_lists>(lds));
-    cpm::launch(cpm::k_exp_lists, grid, dim3(cpm::kExpBlock), lds, c->stream, c->d_exp_ell, Z, c->d_exp_start, c->d_exp_list);
+    cpm::launch(cpm::k_exp_lists, grid, dim3(cpm::kExpBlock), lds, c->stream, c->d_exp_ell.get(), Z, c->d_exp_start.get(), c->d_exp_list.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_exp_bad, c->d_exp_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1244,6 +1238,13 @@ int32_t ensure_exp_aux(cpm_ctx *c)
         return fail(CPM_ERR_TABLE, "expected: the row total of hour %llu, origin %llu exceeds 1: not the sampler's law (include/cpm_expected.h)",
                     bad / static_cast<unsigned long long>(Z) + 1, bad % static_cast<unsigned long long>(Z) + 1);
     c->exp_aux_valid = true;
+    return CPM_OK;
+}
+
+// the installed p_destin tables are there for the propagation to read (what: the family that asks, as its error text names it)
+int32_t exp_tables_ready(const cpm_ctx *c, const char *what)
+{
+    if (!c->have_cdf || !(c->d_p || c->sparse_tables) || !c->d_last) return fail(CPM_ERR_STATE, "%s: p_dest not set", what);
     return CPM_OK;
 }
 
@@ -1262,18 +1263,13 @@ void launch_exp_hour(cpm_ctx *c, int t, const double *q_cur, const double *q_nex
 // out: [B][2][T][Z].  pi_next: [Z] or nullptr (B = 1).
 int32_t expected_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *out, double *pi_next)
 {
-    if (!c->have_cdf || !(c->d_p || c->sparse_tables) || !c->d_last) return fail(CPM_ERR_STATE, "expected: p_dest not set");
-    int32_t rc = ensure_exp_aux(c);
+    int32_t rc = exp_tables_ready(c, "expected");
     if (rc != CPM_OK) return rc;
+    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;  // (every fleet's vector starts on a 16-byte line)
-    if (c->exp_ws_B < B) {  // (hipFree waits for what still reads the old workspace)
-        dfree(c->d_exp_ws);
-        c->exp_ws_B = 0;
-        HIP_TRY(hipMalloc(&c->d_exp_ws, sizeof(double) * 4 * static_cast<size_t>(B) * Zs));
-        c->exp_ws_B = B;
-    }
-    const size_t half = static_cast<size_t>(c->exp_ws_B) * Zs;
+    HIP_TRY(c->d_exp_ws.reserve(4 * static_cast<size_t>(B) * Zs));  // (a grow frees first: hipFree waits for what still reads the old workspace)
+    const size_t half = c->d_exp_ws.cap / 4;                         // (the fleets it was last grown for, [Zs] each)
     double *ws_pi[2] = {c->d_exp_ws, c->d_exp_ws + half};
     double *ws_x[2] = {c->d_exp_ws + 2 * half, c->d_exp_ws + 3 * half};
     const size_t zt = static_cast<size_t>(Z) * T, out_stride = 2 * zt;
@@ -1318,27 +1314,62 @@ int32_t exp_flags_check(uint32_t flags)
     return CPM_OK;
 }
 
-// the blocking calls' device arrays: outputs of B fleets, then pi_next [Z], then pi_0 [Z]
-int32_t ensure_exp_out(cpm_ctx *c, int B)
+// What every entry of the expected family begins with, in front of its own null-argument checks ...
+int32_t exp_enter(const cpm_ctx *c)
 {
-    if (c->exp_out_B >= B && c->d_exp_out) return CPM_OK;
-    dfree(c->d_exp_out);
-    c->exp_out_B = 0;
-    HIP_TRY(hipMalloc(&c->d_exp_out, sizeof(double) * (static_cast<size_t>(B) * 2 * c->Z * c->T + 2 * c->Z)));
-    c->exp_out_B = B;
+    int32_t rc = exp_device_check();
+    if (rc != CPM_OK) return rc;
+    if (!c) return fail(CPM_ERR_ARG, "null context");
+    return CPM_OK;
+}
+
+// ... and, behind them, what the entries that read p_drive tables go on with: the flags, the context's device and stream, and the
+// tables themselves -- the context's own p_drive (B = 1) or the batch tables, Z * T words apart.
+struct ExpTables {
+    int B = 1;
+    const double *pd = nullptr;
+    size_t q_stride = 0;
+};
+int32_t exp_tables(cpm_ctx *c, uint32_t flags, bool batch, ExpTables &tb)
+{
+    int32_t rc = exp_flags_check(flags);
+    if (rc != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (batch) {
+        if (c->batch_B < 1) return fail(CPM_ERR_STATE, "expected: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
+        tb = ExpTables{c->batch_B, c->d_pdrive_b, static_cast<size_t>(c->Z * c->T)};
+    } else {
+        if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
+        tb = ExpTables{1, c->d_pdrive, 0};
+    }
+    return CPM_OK;
+}
+
+int32_t check_pi0(const cpm_ctx *c, const double *pi0)
+{
+    if (pi0)
+        for (int64_t z = 0; z < c->Z; ++z)
+            if (!std::isfinite(pi0[z]) || pi0[z] < 0.0) return fail(CPM_ERR_ARG, "expected: pi0 of zone %lld is NaN, infinite or negative", (long long)z + 1);
+    return CPM_OK;
+}
+
+// the blocking calls' device arrays: outputs of B fleets; *tail: pi_next [Z], then pi_0 [Z], which end the allocation
+int32_t ensure_exp_out(cpm_ctx *c, int B, double **tail)
+{
+    HIP_TRY(c->d_exp_out.reserve(static_cast<size_t>(B) * 2 * c->Z * c->T + 2 * c->Z));
+    *tail = c->d_exp_out + (c->d_exp_out.cap - 2 * static_cast<size_t>(c->Z));
     return CPM_OK;
 }
 
 int32_t expected_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *parking, double *driving,
                           double *pi_next)
 {
-    if (pi0)
-        for (int64_t z = 0; z < c->Z; ++z)
-            if (!std::isfinite(pi0[z]) || pi0[z] < 0.0) return fail(CPM_ERR_ARG, "expected: pi0 of zone %lld is NaN, infinite or negative", (long long)z + 1);
-    int32_t rc = ensure_exp_out(c, B);
+    int32_t rc = check_pi0(c, pi0);
     if (rc != CPM_OK) return rc;
+    double *d_next = nullptr;
+    if ((rc = ensure_exp_out(c, B, &d_next)) != CPM_OK) return rc;
     const size_t zt = static_cast<size_t>(c->Z) * c->T;
-    double *d_next = c->d_exp_out + static_cast<size_t>(c->exp_out_B) * 2 * zt, *d_pi0 = d_next + c->Z;
+    double *d_pi0 = d_next + c->Z;
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream));
     rc = expected_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, c->d_exp_out, pi_next ? d_next : nullptr);
     if (rc != CPM_OK) return rc;
@@ -1356,24 +1387,26 @@ int32_t expected_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, 
 // context's stream; ensure_exp_aux synchronises when it rebuilds).
 int32_t ensure_exp_trip(cpm_ctx *c)
 {
-    if (!c->have_cdf || !(c->d_p || c->sparse_tables) || !c->d_last) return fail(CPM_ERR_STATE, "expected travel: p_dest not set");
+    int32_t rc = exp_tables_ready(c, "expected travel");
+    if (rc != CPM_OK) return rc;
     if (!c->have_dmat) return fail(CPM_ERR_STATE, "expected travel: datamatrix not set (cpm_set_datamatrix, cpm_createdatamatrix_* or cpm_synth_datamatrix)");
     if (!c->have_dist) return fail(CPM_ERR_STATE, "expected travel: distance matrix not set (cpm_set_distance* or the dist of cpm_set_datamatrix)");
-    int32_t rc = ensure_exp_aux(c);  // (the row-total check; clears exp_trip_valid when it rebuilds)
-    if (rc != CPM_OK) return rc;
+    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;  // (the row-total check; clears exp_trip_valid when it rebuilds)
     if (c->exp_trip_valid) return CPM_OK;
     if ((rc = ensure_dense_p(c)) != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const size_t zt = static_cast<size_t>(Z) * T;
     const int nseg = cpm::trip_segments(Z, T), seg_len = cpm::trip_segment_len(Z, nseg);
-    if (!c->d_exp_w) HIP_TRY(hipMalloc(&c->d_exp_w, sizeof(double) * 2 * zt));
-    if (!c->d_exp_wpart) HIP_TRY(hipMalloc(&c->d_exp_wpart, sizeof(double) * 2 * zt * nseg));
+    HIP_TRY(c->d_exp_w.reserve(2 * zt));
+    HIP_TRY(c->d_exp_wpart.reserve(2 * zt * nseg));
     const dim3 grid(nblk(Z, cpm::kTripStrip), static_cast<unsigned>(T), static_cast<unsigned>(nseg));
-    if (Z & 1) cpm::launch(cpm::k_exp_trip<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p, c->d_dm, c->d_dist, Z, T, seg_len, c->d_exp_wpart);
-    else cpm::launch(cpm::k_exp_trip<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p, c->d_dm, c->d_dist, Z, T, seg_len, c->d_exp_wpart);
+    if (Z & 1) cpm::launch(cpm::k_exp_trip<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p.get(), c->d_dm.get(), c->d_dist.get(), Z, T, seg_len,
+                           c->d_exp_wpart.get());
+    else cpm::launch(cpm::k_exp_trip<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p.get(), c->d_dm.get(), c->d_dist.get(), Z, T, seg_len,
+                           c->d_exp_wpart.get());
     HIP_TRY(hipGetLastError());
-    cpm::launch(cpm::k_exp_trip_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream, c->d_exp_wpart, nseg,
-                c->d_dm, c->d_dist, c->d_last, c->d_exp_ell, c->d_exp_r, Z, T, c->d_exp_w);
+    cpm::launch(cpm::k_exp_trip_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream, c->d_exp_wpart.get(),
+                nseg, c->d_dm.get(), c->d_dist.get(), c->d_last, c->d_exp_ell.get(), c->d_exp_r.get(), Z, T, c->d_exp_w.get());
     HIP_TRY(hipGetLastError());
     c->exp_trip_valid = true;
     ++c->exp_trip_builds;
@@ -1387,17 +1420,12 @@ int32_t expected_travel_enqueue(cpm_ctx *c, const double *d_expected, int B, dou
     if (rc != CPM_OK) return rc;
     const size_t zt = static_cast<size_t>(c->Z) * c->T;
     const int nchunk = static_cast<int>(nblk(static_cast<int64_t>(zt), cpm::kTravelChunk));
-    if (d_totals && c->exp_tpart_B < B) {  // (hipFree waits for what still reads the old workspace)
-        dfree(c->d_exp_tpart);
-        c->exp_tpart_B = 0;
-        HIP_TRY(hipMalloc(&c->d_exp_tpart, sizeof(double) * 2 * static_cast<size_t>(B) * nchunk));
-        c->exp_tpart_B = B;
-    }
+    if (d_totals) HIP_TRY(c->d_exp_tpart.reserve(2 * static_cast<size_t>(B) * nchunk));  // (a grow frees first: hipFree waits for its readers)
     cpm::launch(cpm::k_exp_travel, dim3(static_cast<unsigned>(nchunk), static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream, d_expected,
-                c->d_exp_w, zt, d_travel, d_totals ? c->d_exp_tpart : nullptr);
+                c->d_exp_w.get(), zt, d_travel, d_totals ? c->d_exp_tpart.get() : nullptr);
     HIP_TRY(hipGetLastError());
     if (d_totals) {
-        cpm::launch(cpm::k_exp_travel_total, dim3(static_cast<unsigned>(B)), dim3(64), 0, c->stream, c->d_exp_tpart, nchunk, d_totals);
+        cpm::launch(cpm::k_exp_travel_total, dim3(static_cast<unsigned>(B)), dim3(64), 0, c->stream, c->d_exp_tpart.get(), nchunk, d_totals);
         HIP_TRY(hipGetLastError());
     }
     return CPM_OK;
@@ -1407,21 +1435,15 @@ int32_t expected_travel_enqueue(cpm_ctx *c, const double *d_expected, int B, dou
 int32_t expected_travel_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *seconds, double *km,
                                  double *totals)
 {
-    if (pi0)
-        for (int64_t z = 0; z < c->Z; ++z)
-            if (!std::isfinite(pi0[z]) || pi0[z] < 0.0) return fail(CPM_ERR_ARG, "expected: pi0 of zone %lld is NaN, infinite or negative", (long long)z + 1);
-    int32_t rc = ensure_exp_trip(c);  // (first: a missing datamatrix is reported before any work is enqueued)
+    int32_t rc = check_pi0(c, pi0);
     if (rc != CPM_OK) return rc;
-    if ((rc = ensure_exp_out(c, B)) != CPM_OK) return rc;
+    if ((rc = ensure_exp_trip(c)) != CPM_OK) return rc;  // (first: a missing datamatrix is reported before any work is enqueued)
+    double *d_next = nullptr;
+    if ((rc = ensure_exp_out(c, B, &d_next)) != CPM_OK) return rc;
     const size_t zt = static_cast<size_t>(c->Z) * c->T;
-    if (c->exp_trav_B < B || !c->d_exp_trav) {
-        dfree(c->d_exp_trav);
-        c->exp_trav_B = 0;
-        HIP_TRY(hipMalloc(&c->d_exp_trav, sizeof(double) * (static_cast<size_t>(B) * 2 * zt + static_cast<size_t>(B) * 2)));
-        c->exp_trav_B = B;
-    }
-    double *d_pi0 = c->d_exp_out + static_cast<size_t>(c->exp_out_B) * 2 * zt + c->Z;
-    double *d_tot = c->d_exp_trav + static_cast<size_t>(c->exp_trav_B) * 2 * zt;
+    HIP_TRY(c->d_exp_trav.reserve(static_cast<size_t>(B) * (2 * zt + 2)));
+    double *d_pi0 = d_next + c->Z;
+    double *d_tot = c->d_exp_trav + c->d_exp_trav.cap / (2 * zt + 2) * 2 * zt;  // (behind the tensors of the fleets it was last grown for)
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream));
     rc = expected_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, c->d_exp_out, nullptr);
     if (rc != CPM_OK) return rc;
@@ -1442,14 +1464,14 @@ int32_t expected_travel_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, 
 // grad_pd: [T][Z].
 int32_t expected_grad_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, const double *cot, const double *gnext, double *grad_pd, double *grad_pi0)
 {
-    if (!c->have_cdf || !(c->d_p || c->sparse_tables) || !c->d_last) return fail(CPM_ERR_STATE, "expected: p_dest not set");
-    int32_t rc = ensure_exp_aux(c);
+    int32_t rc = exp_tables_ready(c, "expected");
     if (rc != CPM_OK) return rc;
+    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
     const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
     const int most = 2 * T - 1;   // operators under CPM_EXPECT_IVP: the workspace is sized once
-    if (!c->d_exp_gws) HIP_TRY(hipMalloc(&c->d_exp_gws, sizeof(double) * static_cast<size_t>(most + 4 + nseg) * Zs));
+    HIP_TRY(c->d_exp_gws.reserve(static_cast<size_t>(most + 4 + nseg) * Zs));
     double *ws_pi = c->d_exp_gws;
     double *ws_x[2] = {ws_pi + static_cast<size_t>(most) * Zs, ws_pi + static_cast<size_t>(most + 1) * Zs};
     double *ws_mu[2] = {ws_pi + static_cast<size_t>(most + 2) * Zs, ws_pi + static_cast<size_t>(most + 3) * Zs};
@@ -1495,22 +1517,21 @@ int32_t expected_grad_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, co
                                double *grad_pd, double *grad_pi0)
 {
     const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T);
-    if (pi0)
-        for (size_t z = 0; z < Z; ++z)
-            if (!std::isfinite(pi0[z]) || pi0[z] < 0.0) return fail(CPM_ERR_ARG, "expected: pi0 of zone %lld is NaN, infinite or negative", (long long)z + 1);
+    int32_t rc = check_pi0(c, pi0);
+    if (rc != CPM_OK) return rc;
     for (size_t i = 0; i < zt; ++i)
         if (!std::isfinite(g_parking[i]) || !std::isfinite(g_driving[i]))
             return fail(CPM_ERR_ARG, "expected_grad: the cotangent of zone %lld, hour %lld is not finite", (long long)(i % Z) + 1, (long long)(i / Z) + 1);
     if (g_next)
         for (size_t z = 0; z < Z; ++z)
             if (!std::isfinite(g_next[z])) return fail(CPM_ERR_ARG, "expected_grad: g_next of zone %lld is not finite", (long long)z + 1);
-    if (!c->d_exp_gio) HIP_TRY(hipMalloc(&c->d_exp_gio, sizeof(double) * (3 * zt + 3 * Z)));
+    HIP_TRY(c->d_exp_gio.reserve(3 * zt + 3 * Z));
     double *d_cot = c->d_exp_gio, *d_gnext = d_cot + 2 * zt, *d_grad = d_gnext + Z, *d_gpi0 = d_grad + zt, *d_pi0 = d_gpi0 + Z;
     HIP_TRY(hipMemcpyAsync(d_cot, g_parking, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_cot + zt, g_driving, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
     if (g_next) HIP_TRY(hipMemcpyAsync(d_gnext, g_next, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
-    int32_t rc = expected_grad_enqueue(c, pi0 ? d_pi0 : nullptr, flags, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr);
+    rc = expected_grad_enqueue(c, pi0 ? d_pi0 : nullptr, flags, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr);
     if (rc != CPM_OK) return rc;
     HIP_TRY(hipMemcpyAsync(grad_pd, d_grad, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
     if (grad_pi0) HIP_TRY(hipMemcpyAsync(grad_pi0, d_gpi0, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
@@ -1570,15 +1591,15 @@ int32_t cpm_create(cpm_ctx **ctx_out, int64_t Z, int64_t T, int32_t device_id)
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, device_id) == hipSuccess) c->cu_count = p.multiProcessorCount;
     if (c->cu_count <= 0) c->cu_count = 256;
-    hipError_t e = hipMalloc(&c->d_err, sizeof(int));
+    hipError_t e = c->d_err.reserve(1);
     if (e == hipSuccess) e = hipMemset(c->d_err, 0, sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&c->h_err), sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&c->d_counts, sizeof(int64_t) * static_cast<size_t>(2 * T * Z + 2));
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&c->h_counts), sizeof(int64_t) * static_cast<size_t>(2 * T * Z + 2));
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&c->h_status), 2 * sizeof(long long));
+    if (e == hipSuccess) e = c->h_err.reserve(1);
+    if (e == hipSuccess) e = c->d_counts.reserve(static_cast<size_t>(2 * T * Z + 2));
+    if (e == hipSuccess) e = c->h_counts.reserve(static_cast<size_t>(2 * T * Z + 2));
+    if (e == hipSuccess) e = c->h_status.reserve(2);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->status_ev, hipEventDisableTiming);
     if (e == hipSuccess) c->h_status[0] = c->h_status[1] = 0;
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&c->h_ivp_status), 2 * sizeof(long long));
+    if (e == hipSuccess) e = c->h_ivp_status.reserve(2);
     if (e == hipSuccess) c->h_ivp_status[0] = c->h_ivp_status[1] = 0;
     if (e != hipSuccess) {
         cpm_destroy(c);
@@ -1598,85 +1619,18 @@ int32_t cpm_destroy(cpm_ctx *c)
     if (!c) return CPM_OK;
     (void)hipSetDevice(c->device);
     if (c->have_stream) (void)hipStreamSynchronize(c->stream);
-    dfree(c->d_pdrive);
-    dfree(c->d_cdf);
-    dfree(c->d_p);
-    dfree(c->d_ckpt);
-    dfree(c->d_hi);
-    dfree(c->d_last);
+    dfree(c->d_pdrive);  // the four that are re-pointed for a step or a launch, hence plain pointers (see cpm_ctx)
     dfree(c->d_thr);
-    dfree(c->d_dm);
-    dfree(c->d_dist);
-    dfree(c->d_pdrive_mean);
-    dfree(c->d_pdrive_b);
-    dfree(c->d_thr_b);
-    dfree(c->d_bcounts);
-    if (c->h_bcounts) (void)hipHostFree(c->h_bcounts);
-    dfree(c->d_bstatus);
-    if (c->h_bstatus) (void)hipHostFree(c->h_bstatus);
-    if (c->bstatus_ev) (void)hipEventDestroy(c->bstatus_ev);
+    dfree(c->d_last);
+    dfree(c->d_ckpt);
     c->zb.release();
-    dfree(c->d_measured);
-    dfree(c->d_meas_flag);
-    dfree(c->d_obj_part);
-    dfree(c->d_obj_part_n);
-    dfree(c->d_exp_ell);
-    dfree(c->d_exp_r);
-    dfree(c->d_exp_start);
-    dfree(c->d_exp_list);
-    dfree(c->d_exp_bad);
-    if (c->h_exp_bad) (void)hipHostFree(c->h_exp_bad);
-    dfree(c->d_exp_ws);
-    dfree(c->d_exp_out);
-    dfree(c->d_exp_w);
-    dfree(c->d_exp_wpart);
-    dfree(c->d_exp_trav);
-    dfree(c->d_exp_tpart);
-    dfree(c->d_exp_gws);
-    dfree(c->d_exp_gio);
-    dfree(c->d_ds_cells);
-    dfree(c->d_ds_cnt);
-    dfree(c->d_sp);
-    dfree(c->d_sj);
-    dfree(c->d_scnt);
-    dfree(c->d_up_stats);
-    if (c->h_up_stats) (void)hipHostFree(c->h_up_stats);
-    if (c->h_ds_stats) (void)hipHostFree(c->h_ds_stats);
-    dfree(c->d_tt);
-    dfree(c->d_tts_words);
-    dfree(c->d_tts_off);
-    dfree(c->d_tts_cells);
-    dfree(c->d_zone0);
-    dfree(c->d_ztmp);
-    dfree(c->d_rec);
-    dfree(c->d_flows);
-    dfree(c->d_csr_row_ptr);
-    dfree(c->d_csr_dest);
-    dfree(c->d_csr_count);
-    dfree(c->d_flows_hour);
-    dfree(c->d_stay_last);
-    dfree(c->d_stays);
-    dfree(c->d_paths);
-    dfree(c->d_expand_cols);
-    dfree(c->d_stay_parked);
-    dfree(c->d_ebat);
-    dfree(c->d_dist_rows);
-    dfree(c->d_chg_load);
-    dfree(c->d_chg_short);
-    dfree(c->d_chg_zone_power);
-    dfree(c->d_chg_soc);
-    dfree(c->d_counts);
-    dfree(c->d_err);
     c->zx.release();
     c->zg.release();
-    if (c->h_err) (void)hipHostFree(c->h_err);
-    if (c->h_status) (void)hipHostFree(c->h_status);
-    if (c->h_counts) (void)hipHostFree(c->h_counts);
-    if (c->h_ivp_status) (void)hipHostFree(c->h_ivp_status);
+    if (c->bstatus_ev) (void)hipEventDestroy(c->bstatus_ev);
     if (c->status_ev) (void)hipEventDestroy(c->status_ev);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;  // (every DevBuf / PinnedBuf member frees what it owns)
     return CPM_OK;
 }
 
@@ -1854,7 +1808,7 @@ int32_t cpm_set_p_dest(cpm_ctx *c, const double *p_dest)
     }
     if (!p_dest) return fail(CPM_ERR_ARG, "null p_dest");
     size_t bytes = sizeof(double) * c->Z * c->Z * c->T;
-    if (!c->d_p) HIP_TRY(hipMalloc(&c->d_p, bytes));
+    HIP_TRY(c->d_p.reserve(bytes / sizeof(double)));
     c->have_cdf = false;
     HIP_TRY(hipMemcpyAsync(c->d_p, p_dest, bytes, hipMemcpyHostToDevice, c->stream));
     if (c->sparse_upload) {  // sparse row packs where the table qualifies (cpm_upload.h)
@@ -1875,8 +1829,8 @@ int32_t cpm_set_datamatrix(cpm_ctx *c, const double *datamatrix, const double *d
     if (!datamatrix) return fail(CPM_ERR_ARG, "null datamatrix");
     size_t bytes = sizeof(double) * c->Z * c->Z * c->T * 2;
     size_t dbytes = sizeof(double) * c->Z * c->Z;
-    if (!c->d_dm) HIP_TRY(hipMalloc(&c->d_dm, bytes));
-    if (dist && !c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, dbytes));
+    HIP_TRY(c->d_dm.reserve(bytes / sizeof(double)));
+    if (dist) HIP_TRY(c->d_dist.reserve(dbytes / sizeof(double)));
     c->have_dmat = false;
     c->tt_valid = false;
     c->tts_valid = false;
@@ -1909,7 +1863,7 @@ static std::string read_csv_noexcept(const char *path, cpm::CsvRows &rows)
 static int32_t datamatrix_from_device_rows(cpm_ctx *c, const double *d_raw, int64_t n)
 {
     const size_t cells = static_cast<size_t>(c->Z) * c->Z * c->T;
-    if (!c->d_dm) HIP_TRY(hipMalloc(&c->d_dm, sizeof(double) * cells * 2));
+    HIP_TRY(c->d_dm.reserve(cells * 2));
     c->have_dmat = false;
     c->tt_valid = false;
     c->tts_valid = false;
@@ -1922,8 +1876,8 @@ static int32_t datamatrix_from_device_rows(cpm_ctx *c, const double *d_raw, int6
         c->have_dmat = true;
         return CPM_OK;
     }
-    uint32_t *d_owner = nullptr;
-    HIP_TRY(hipMalloc(&d_owner, sizeof(uint32_t) * cells));
+    DevBuf<uint32_t> d_owner;  // (scratch of this call: freed when it returns, behind the wait below)
+    HIP_TRY(d_owner.reserve(cells));
     hipError_t e = hipMemsetAsync(d_owner, 0, sizeof(uint32_t) * cells, c->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(cpm::k_dm_owner, dim3(nblk(n, 256)), dim3(256), 0, c->stream, d_raw, n, static_cast<int>(c->Z),
@@ -1936,7 +1890,6 @@ static int32_t datamatrix_from_device_rows(cpm_ctx *c, const double *d_raw, int6
                                                         "(reference: InexactError / BoundsError)", CPM_ERR_ARG)
                                    : fail(CPM_ERR_HIP, "createdatamatrix: %s", hipGetErrorString(e));
     (void)hipStreamSynchronize(c->stream);
-    dfree(d_owner);
     if (rc == CPM_OK) c->have_dmat = true;
     return rc;
 }
@@ -1975,18 +1928,13 @@ int32_t cpm_createdatamatrix_rows(cpm_ctx *c, int64_t n_rows, const double *rawd
         if (rc_ivp != CPM_OK) return rc_ivp;
     }
     if (n_rows < 0 || n_rows >= (int64_t(1) << 32) - 1 || (n_rows > 0 && !rawdata)) return fail(CPM_ERR_ARG, "createdatamatrix: bad row list");
-    double *d_raw = nullptr;
+    DevBuf<double> d_raw;  // (scratch of this call; datamatrix_from_device_rows waits for the stream before it returns)
     if (n_rows > 0) {
-        HIP_TRY(hipMalloc(&d_raw, sizeof(double) * 5 * n_rows));
+        HIP_TRY(d_raw.reserve(5 * static_cast<size_t>(n_rows)));
         hipError_t e = hipMemcpyAsync(d_raw, rawdata, sizeof(double) * 5 * n_rows, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) {
-            dfree(d_raw);
-            return fail(CPM_ERR_HIP, "createdatamatrix: upload: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(CPM_ERR_HIP, "createdatamatrix: upload: %s", hipGetErrorString(e));
     }
-    int32_t rc = datamatrix_from_device_rows(c, d_raw, n_rows);
-    dfree(d_raw);
-    return rc;
+    return datamatrix_from_device_rows(c, d_raw, n_rows);
 }
 
 int32_t cpm_createdatamatrix_csv(cpm_ctx *c, const char *path_to_csv_data, int64_t *n_rows_out)
@@ -2002,22 +1950,19 @@ int32_t cpm_createdatamatrix_csv(cpm_ctx *c, const char *path_to_csv_data, int64
     if (!err.empty()) return fail(CPM_ERR_ARG, "createdatamatrix: %s", err.c_str());
     if (n_rows_out) *n_rows_out = rows.n;
     if (rows.n >= (int64_t(1) << 32) - 1) return fail(CPM_ERR_ARG, "createdatamatrix: too many rows");
-    double *d_raw = nullptr;
+    DevBuf<double> d_raw;  // (scratch of this call; datamatrix_from_device_rows waits for the stream before it returns)
     if (rows.n > 0) {
-        HIP_TRY(hipMalloc(&d_raw, sizeof(double) * 5 * rows.n));
+        HIP_TRY(d_raw.reserve(5 * static_cast<size_t>(rows.n)));
         for (int k = 0; k < 5; ++k) {
             hipError_t e = hipMemcpyAsync(d_raw + static_cast<size_t>(k) * rows.n, rows.col[k].data(), sizeof(double) * rows.n,
                                           hipMemcpyHostToDevice, c->stream);
             if (e != hipSuccess) {
                 (void)hipStreamSynchronize(c->stream);
-                dfree(d_raw);
                 return fail(CPM_ERR_HIP, "createdatamatrix: upload: %s", hipGetErrorString(e));
             }
         }
     }
-    int32_t rc = datamatrix_from_device_rows(c, d_raw, rows.n);
-    dfree(d_raw);
-    return rc;
+    return datamatrix_from_device_rows(c, d_raw, rows.n);
 }
 
 int32_t cpm_get_datamatrix(cpm_ctx *c, double *datamatrix_out)
@@ -2035,7 +1980,7 @@ int32_t cpm_set_distance_from_centroids(cpm_ctx *c, const double *centroid_lat, 
     CTX_TRY(c);
     if (!centroid_lat || !centroid_long) return fail(CPM_ERR_ARG, "null centroids");
     const size_t dbytes = sizeof(double) * c->Z * c->Z;
-    if (!c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, dbytes));
+    HIP_TRY(c->d_dist.reserve(dbytes / sizeof(double)));
     c->exp_trip_valid = false;  // (before the first byte changes: a copy that fails half way leaves no weights behind)
     double *d_ll = nullptr;
     HIP_TRY(hipMalloc(&d_ll, sizeof(double) * 2 * c->Z));
@@ -2061,7 +2006,7 @@ int32_t cpm_set_distance(cpm_ctx *c, const double *dist)
     CTX_TRY(c);
     if (!dist) return fail(CPM_ERR_ARG, "null dist");
     const size_t dbytes = sizeof(double) * c->Z * c->Z;
-    if (!c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, dbytes));
+    HIP_TRY(c->d_dist.reserve(dbytes / sizeof(double)));
     c->exp_trip_valid = false;  // (before the first byte changes: a copy that fails half way leaves no weights behind)
     HIP_TRY(hipMemcpyAsync(c->d_dist, dist, dbytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2135,7 +2080,7 @@ int32_t cpm_build_p_dest(cpm_ctx *c, double e_dest, int32_t e_is_integer, double
     }
     // createpdestin's array in the reference's layout: weights, then normalised in place.  It stays with the context (a sweep calls
     // this entry once per e_dest value: no allocation on that path); the row tables are derived from it in one more pass.
-    if (!c->d_p) HIP_TRY(hipMalloc(&c->d_p, bytes));
+    HIP_TRY(c->d_p.reserve(bytes / sizeof(double)));
     c->have_cdf = false;
     dim3 g1(nblk(c->Z, 256), static_cast<unsigned>(c->Z));
     if (c->T == 24)
@@ -2199,7 +2144,7 @@ int32_t cpm_synth_tables_skewed(cpm_ctx *c, uint64_t table_seed, int64_t skew_q)
         if (rc_thr != CPM_OK) return rc_thr;
     }
     c->have_pdrive = true;
-    if (!c->d_p) HIP_TRY(hipMalloc(&c->d_p, sizeof(double) * c->Z * c->Z * c->T));
+    HIP_TRY(c->d_p.reserve(static_cast<size_t>(c->Z * c->Z * c->T)));
     c->have_cdf = false;
     dim3 grid(nblk(c->Z, 64), static_cast<unsigned>(c->T));
     hipLaunchKernelGGL(cpm::k_synth_p_dest, grid, dim3(64), 0, c->stream, c->d_p, static_cast<int>(c->Z), table_seed, skew_q);
@@ -2216,8 +2161,8 @@ int32_t cpm_synth_datamatrix(cpm_ctx *c, uint64_t table_seed, double density)
     }
     if (!(density >= 0.0 && density <= 1.0)) return fail(CPM_ERR_ARG, "synth_datamatrix: density %g", density);
     const size_t cells = static_cast<size_t>(c->Z) * c->Z * c->T;
-    if (!c->d_dm) HIP_TRY(hipMalloc(&c->d_dm, sizeof(double) * cells * 2));
-    if (!c->d_dist) HIP_TRY(hipMalloc(&c->d_dist, sizeof(double) * c->Z * c->Z));
+    HIP_TRY(c->d_dm.reserve(cells * 2));
+    HIP_TRY(c->d_dist.reserve(static_cast<size_t>(c->Z * c->Z)));
     c->have_dmat = c->have_dist = false;
     c->dist_rows_valid = false;
     c->tt_valid = false;
@@ -2378,22 +2323,12 @@ int32_t cpm_resample(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking
     CTX_TRY(c);
     if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
     bool compat = state_out || trans_out;
-    struct KernelGuard {  // the kernel choice is overridden for this call only, whichever way the call ends
-        cpm_ctx *c;
-        int saved;
-        ~KernelGuard() { c->kernel = saved; }
-    } kernel_guard{c, c->kernel};
-    {   // a pending IVP is committed with the caller's kernel choice, not with the override below
-        int32_t rc_ivp = finish_ivp(c);
-        if (rc_ivp != CPM_OK) return rc_ivp;
-    }
+    BlockingCall call(c);
+    if (call.rc != CPM_OK) return call.rc;
     if (compat) c->kernel = CPM_KERNEL_CAR;  // the per-hour records of every car are kept by this path
     int32_t rc = resample_blocking(c, seed, flags);
     if (rc != CPM_OK) return rc;
-    const size_t zt = static_cast<size_t>(c->Z * c->T);
-    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
-    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
-    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    copy_counts(c, parking, driving, sum_tt_q16);
     if (compat && c->n > 0) {
         // one hour column at a time: state[:,t] and trans[:,t,1..4] are contiguous runs of C values
         int64_t n = c->n;
@@ -2407,7 +2342,7 @@ int32_t cpm_resample(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *parking
             const uint32_t *zsrc = (t == 0) ? c->d_zone0 : c->d_rec + static_cast<size_t>(t - 1) * n;
             hipLaunchKernelGGL(cpm::k_export_hour, dim3(nblk(n, 256)), dim3(256), 0, c->stream, zsrc,
                                c->d_rec + static_cast<size_t>(t) * n, n, c->cars, d_state, d_f, d_f + n, d_f + 2 * n,
-                               d_f + 3 * n, travel ? c->d_dm : nullptr, c->d_dist, static_cast<int>(c->Z),
+                               d_f + 3 * n, travel ? c->d_dm.get() : nullptr, c->d_dist, static_cast<int>(c->Z),
                                static_cast<int>(c->T), t, static_cast<uint32_t>(c->T - 1 + t), seed);
             e = hipGetLastError();
             if (e == hipSuccess && state_out)
@@ -2439,25 +2374,15 @@ int32_t cpm_resample_flows(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     CTX_TRY(c);
     if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
     if (!flows_out) return fail(CPM_ERR_ARG, "null flows_out");
-    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
-        cpm_ctx *c;
-        int saved;
-        ~KernelGuard() { c->kernel = saved; }
-    } kernel_guard{c, c->kernel};
-    {
-        int32_t rc_ivp = finish_ivp(c);
-        if (rc_ivp != CPM_OK) return rc_ivp;
-    }
+    BlockingCall call(c);
+    if (call.rc != CPM_OK) return call.rc;
     const size_t cells = static_cast<size_t>(c->T) * c->Z * c->Z;
-    if (!c->d_flows) HIP_TRY(hipMalloc(&c->d_flows, sizeof(int32_t) * std::max<size_t>(cells, 1)));
+    HIP_TRY(c->d_flows.reserve(cells));
     cpm::SideDest side;
     side.flows.dense = c->d_flows;
     int32_t rc = resample_blocking(c, seed, flags, side);
     if (rc != CPM_OK) return rc;
-    const size_t zt = static_cast<size_t>(c->Z * c->T);
-    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
-    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
-    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    copy_counts(c, parking, driving, sum_tt_q16);
     // (the flows of the attempt whose counts were fetched: every attempt writes the whole array, and the last one enqueued is the one returned)
     HIP_TRY(hipMemcpyAsync(flows_out, c->d_flows, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2484,26 +2409,17 @@ int32_t cpm_resample_stays(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
     if (!stays_out) return fail(CPM_ERR_ARG, "null stays_out");
     if (!parked_out) return fail(CPM_ERR_ARG, "null parked_out");
-    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
-        cpm_ctx *c;
-        int saved;
-        ~KernelGuard() { c->kernel = saved; }
-    } kernel_guard{c, c->kernel};
-    {
-        int32_t rc_ivp = finish_ivp(c);
-        if (rc_ivp != CPM_OK) return rc_ivp;
-    }
+    BlockingCall call(c);
+    if (call.rc != CPM_OK) return call.rc;
     const size_t zt = static_cast<size_t>(c->Z * c->T), cells = zt * static_cast<size_t>(c->T);
-    if (!c->d_stays) HIP_TRY(hipMalloc(&c->d_stays, sizeof(int32_t) * std::max<size_t>(cells, 1)));
-    if (!c->d_stay_parked) HIP_TRY(hipMalloc(&c->d_stay_parked, sizeof(int32_t) * std::max<size_t>(zt, 1)));
+    HIP_TRY(c->d_stays.reserve(cells));
+    HIP_TRY(c->d_stay_parked.reserve(zt));
     cpm::SideDest side;
     side.stays.stays = c->d_stays;
     side.stays.parked = c->d_stay_parked;
     int32_t rc = resample_blocking(c, seed, flags, side);
     if (rc != CPM_OK) return rc;
-    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
-    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
-    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    copy_counts(c, parking, driving, sum_tt_q16);
     // (the stays of the attempt whose counts were fetched: every attempt resets the side array and writes both arrays whole, and the
     //  last one enqueued is the one returned)
     HIP_TRY(hipMemcpyAsync(stays_out, c->d_stays, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
@@ -2561,27 +2477,15 @@ int32_t cpm_resample_charge(cpm_ctx *c, uint64_t seed, uint32_t flags, const cpm
         int32_t rc_p = charge_dest(params, cd);
         if (rc_p != CPM_OK) return rc_p;
     }
-    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
-        cpm_ctx *c;
-        int saved;
-        ~KernelGuard() { c->kernel = saved; }
-    } kernel_guard{c, c->kernel};
-    {
-        int32_t rc_ivp = finish_ivp(c);
-        if (rc_ivp != CPM_OK) return rc_ivp;
-    }
+    BlockingCall call(c);
+    if (call.rc != CPM_OK) return call.rc;
     const size_t zt = static_cast<size_t>(c->Z * c->T), n = static_cast<size_t>(c->n);
-    if (!c->d_chg_load) HIP_TRY(hipMalloc(&c->d_chg_load, sizeof(int64_t) * 2 * std::max<size_t>(zt, 1)));
-    if (!c->d_chg_short) HIP_TRY(hipMalloc(&c->d_chg_short, sizeof(int32_t) * std::max<size_t>(zt, 1)));
-    if (!c->d_chg_zone_power) HIP_TRY(hipMalloc(&c->d_chg_zone_power, sizeof(uint32_t) * std::max<size_t>(c->Z, 1)));
-    if (c->chg_soc_cap < c->n || !c->d_chg_soc) {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (a _dev step in flight may not read it, but nothing is freed under the stream)
-        dfree(c->d_chg_soc);
-        c->d_chg_soc = nullptr;
-        c->chg_soc_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_chg_soc, sizeof(uint32_t) * 2 * std::max<size_t>(n, 1)));
-        c->chg_soc_cap = std::max<int64_t>(c->n, 1);
-    }
+    HIP_TRY(c->d_chg_load.reserve(2 * zt));
+    HIP_TRY(c->d_chg_short.reserve(zt));
+    HIP_TRY(c->d_chg_zone_power.reserve(static_cast<size_t>(c->Z)));
+    const size_t soc_words = 2 * std::max<size_t>(n, 1);  // soc_in | soc_out: an even count, so that the halves of a grown array stay apart
+    if (!c->d_chg_soc.fits(soc_words)) HIP_TRY(hipStreamSynchronize(c->stream));  // (a _dev step in flight may not read it, but nothing is freed under the stream)
+    HIP_TRY(c->d_chg_soc.reserve(soc_words));
     // the caller's host arrays to the device (pageable memory: the copies have left the host when the calls return)
     if (cd.zone_power) {
         HIP_TRY(hipMemcpyAsync(c->d_chg_zone_power, cd.zone_power, sizeof(uint32_t) * c->Z, hipMemcpyHostToDevice, c->stream));
@@ -2594,12 +2498,10 @@ int32_t cpm_resample_charge(cpm_ctx *c, uint64_t seed, uint32_t flags, const cpm
     cd.charge = c->d_chg_load;
     cd.used = c->d_chg_load + zt;
     cd.shrt = c->d_chg_short;
-    cd.soc = soc_out ? c->d_chg_soc + c->chg_soc_cap : nullptr;
+    cd.soc = soc_out ? c->d_chg_soc + c->d_chg_soc.cap / 2 : nullptr;
     int32_t rc = resample_blocking(c, seed, flags, side);
     if (rc != CPM_OK) return rc;
-    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
-    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
-    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    copy_counts(c, parking, driving, sum_tt_q16);
     // (the arrays of the attempt whose counts were fetched: every attempt fills the side array anew and writes every array whole, and
     //  the last one enqueued is the one returned)
     HIP_TRY(hipMemcpyAsync(charge_out, cd.charge, sizeof(int64_t) * zt, hipMemcpyDeviceToHost, c->stream));
@@ -2626,31 +2528,15 @@ int32_t cpm_resample_paths(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *p
     CTX_TRY(c);
     if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
     if (!paths_out) return fail(CPM_ERR_ARG, "null paths_out");
-    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
-        cpm_ctx *c;
-        int saved;
-        ~KernelGuard() { c->kernel = saved; }
-    } kernel_guard{c, c->kernel};
-    {
-        int32_t rc_ivp = finish_ivp(c);
-        if (rc_ivp != CPM_OK) return rc_ivp;
-    }
+    BlockingCall call(c);
+    if (call.rc != CPM_OK) return call.rc;
     const int64_t words = c->T * c->n;
-    if (c->paths_cap < words || !c->d_paths) {  // kept from the first use (until the fleet grows)
-        dfree(c->d_paths);
-        c->d_paths = nullptr;
-        c->paths_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_paths, sizeof(uint32_t) * static_cast<size_t>(std::max<int64_t>(words, 1))));
-        c->paths_cap = words;
-    }
+    HIP_TRY(c->d_paths.reserve(static_cast<size_t>(words)));  // kept from the first use (until the fleet grows)
     cpm::SideDest side;
     side.paths.paths = c->d_paths;
     int32_t rc = resample_blocking(c, seed, flags, side);
     if (rc != CPM_OK) return rc;
-    const size_t zt = static_cast<size_t>(c->Z * c->T);
-    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
-    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
-    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    copy_counts(c, parking, driving, sum_tt_q16);
     // (the record of the attempt whose counts were fetched: every attempt writes every word, and the last one enqueued is the one returned)
     if (words > 0) {
         HIP_TRY(hipMemcpyAsync(paths_out, c->d_paths, sizeof(uint32_t) * static_cast<size_t>(words), hipMemcpyDeviceToHost, c->stream));
@@ -2677,15 +2563,9 @@ int32_t cpm_paths_expand_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, const vo
     int64_t *spare_state = nullptr;
     double *spare_f = nullptr;
     if (!d_state || !d_trans) {  // (the kernel writes all five columns: those nobody asked for go to the context's own)
-        if (c->expand_cap < n || !c->d_expand_cols) {
-            dfree(c->d_expand_cols);
-            c->d_expand_cols = nullptr;
-            c->expand_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_expand_cols, static_cast<size_t>(n) * 8 * 5));
-            c->expand_cap = n;
-        }
-        spare_state = reinterpret_cast<int64_t *>(c->d_expand_cols);
-        spare_f = reinterpret_cast<double *>(c->d_expand_cols) + n;
+        HIP_TRY(c->d_expand_cols.reserve(static_cast<size_t>(n) * 8 * 5));
+        spare_state = reinterpret_cast<int64_t *>(c->d_expand_cols.get());
+        spare_f = reinterpret_cast<double *>(c->d_expand_cols.get()) + n;
     }
     const uint32_t *rec = static_cast<const uint32_t *>(d_paths);
     const size_t tn = static_cast<size_t>(c->T) * n;
@@ -2695,7 +2575,7 @@ int32_t cpm_paths_expand_dev(cpm_ctx *c, uint64_t seed, uint32_t flags, const vo
         double *f = d_trans ? static_cast<double *>(d_trans) + static_cast<size_t>(t) * n : spare_f;
         const size_t col = d_trans ? tn : static_cast<size_t>(n);
         hipLaunchKernelGGL(cpm::k_export_hour, dim3(nblk(n, 256)), dim3(256), 0, c->stream, zsrc, rec + static_cast<size_t>(t) * n, n, c->cars, state_col, f,
-                           f + col, f + 2 * col, f + 3 * col, travel ? c->d_dm : nullptr, c->d_dist, static_cast<int>(c->Z), static_cast<int>(c->T), t,
+                           f + col, f + 2 * col, f + 3 * col, travel ? c->d_dm.get() : nullptr, c->d_dist, static_cast<int>(c->Z), static_cast<int>(c->T), t,
                            static_cast<uint32_t>(c->T - 1 + t), seed);
         HIP_TRY(hipGetLastError());
     }
@@ -2724,29 +2604,17 @@ int32_t cpm_resample_flows_csr(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_
     CTX_TRY(c);
     if (!parking || !driving) return fail(CPM_ERR_ARG, "null count outputs");
     if (!row_ptr_out || !nnz_out) return fail(CPM_ERR_ARG, "null row_ptr_out / nnz_out");
-    struct KernelGuard {  // a fallback's kernel override is for this call only, whichever way the call ends (as cpm_resample)
-        cpm_ctx *c;
-        int saved;
-        ~KernelGuard() { c->kernel = saved; }
-    } kernel_guard{c, c->kernel};
-    {
-        int32_t rc_ivp = finish_ivp(c);
-        if (rc_ivp != CPM_OK) return rc_ivp;
-    }
+    BlockingCall call(c);
+    if (call.rc != CPM_OK) return call.rc;
     c->csr_nnz = -1;
     const size_t zt = static_cast<size_t>(c->Z * c->T);
-    if (!c->d_csr_row_ptr) HIP_TRY(hipMalloc(&c->d_csr_row_ptr, sizeof(int64_t) * (zt + 1)));
+    HIP_TRY(c->d_csr_row_ptr.reserve(zt + 1));
     // T * min(n, Z * Z) entries always suffice.  The arrays start at that bound, or at 1 GiB for the two where the bound is larger;
     // a step that needs more tells by row_ptr[T * Z], which is exact whatever the capacity, and is run again on arrays of that size.
+    auto csr_cap = [&] { return static_cast<int64_t>(c->d_csr_count.cap); };  // (both arrays: grown together, the second one last)
     auto ensure_entries = [&](int64_t want) -> int32_t {
-        if (want <= c->csr_cap) return CPM_OK;
-        dfree(c->d_csr_dest);
-        dfree(c->d_csr_count);
-        c->d_csr_dest = c->d_csr_count = nullptr;
-        c->csr_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_csr_dest, sizeof(int32_t) * static_cast<size_t>(want)));
-        HIP_TRY(hipMalloc(&c->d_csr_count, sizeof(int32_t) * static_cast<size_t>(want)));
-        c->csr_cap = want;
+        HIP_TRY(c->d_csr_dest.reserve(static_cast<size_t>(want)));
+        HIP_TRY(c->d_csr_count.reserve(static_cast<size_t>(want)));
         return CPM_OK;
     };
     const int64_t bound = static_cast<int64_t>(c->T) * std::min<int64_t>(c->n, static_cast<int64_t>(c->Z) * c->Z);
@@ -2757,7 +2625,7 @@ int32_t cpm_resample_flows_csr(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_
         side.flows.row_ptr = c->d_csr_row_ptr;
         side.flows.dest = c->d_csr_dest;
         side.flows.count = c->d_csr_count;
-        side.flows.cap = c->csr_cap;
+        side.flows.cap = csr_cap();
         rc = resample_blocking(c, seed, flags, side);
         if (rc != CPM_OK) return rc;
         // (the rows of the attempt whose counts were fetched: every attempt writes all of row_ptr, and the last one enqueued is the one returned)
@@ -2765,14 +2633,12 @@ int32_t cpm_resample_flows_csr(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_
         HIP_TRY(hipStreamSynchronize(c->stream));
         const int64_t nnz = row_ptr_out[zt];
         if (nnz < 0 || nnz > bound) return fail(CPM_ERR_HIP, "flows (csr): %lld entries reported, at most %lld possible", (long long)nnz, (long long)bound);
-        if (nnz <= c->csr_cap) break;
+        if (nnz <= csr_cap()) break;
         if (attempt > 0) return fail(CPM_ERR_HIP, "flows (csr): %lld entries after a run that reported fewer", (long long)nnz);
         rc = ensure_entries(nnz);  // (the step is a pure function of seed and state: the repeat needs exactly as many)
         if (rc != CPM_OK) return rc;
     }
-    std::memcpy(parking, c->h_counts, sizeof(int64_t) * zt);
-    std::memcpy(driving, c->h_counts + zt, sizeof(int64_t) * zt);
-    if (sum_tt_q16) *sum_tt_q16 = c->h_counts[2 * zt];
+    copy_counts(c, parking, driving, sum_tt_q16);
     c->csr_nnz = row_ptr_out[zt];
     *nnz_out = c->csr_nnz;
     return CPM_OK;
@@ -2928,8 +2794,8 @@ int32_t cpm_set_measured(cpm_ctx *c, const double *measured)
     for (size_t i = 0; i < cells; ++i)
         if (!std::isfinite(measured[i]))
             return fail(CPM_ERR_ARG, "set_measured: entry (zone %lld, hour %lld) is not finite", (long long)(i % c->Z) + 1, (long long)(i / c->Z) + 1);
-    if (!c->d_measured) HIP_TRY(hipMalloc(&c->d_measured, sizeof(double) * cells));
-    if (!c->d_meas_flag) HIP_TRY(hipMalloc(&c->d_meas_flag, sizeof(int) * static_cast<size_t>(c->Z)));
+    HIP_TRY(c->d_measured.reserve(cells));
+    HIP_TRY(c->d_meas_flag.reserve(static_cast<size_t>(c->Z)));
     // (Z x T column-major IS [T][Z]: the layout the kernels read, Z contiguous like the count tensor)
     HIP_TRY(hipMemcpyAsync(c->d_measured, measured, sizeof(double) * cells, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(cpm::k_measured_flag, dim3(nblk(c->Z, cpm::kObjBlock)), dim3(cpm::kObjBlock), 0, c->stream, c->d_measured, c->d_meas_flag,
@@ -2949,20 +2815,14 @@ int32_t cpm_objectives_dev(cpm_ctx *c, const void *d_counts, int32_t B, int64_t 
     if (n_cars < 1) return fail(CPM_ERR_ARG, "objectives: n_cars = %lld", (long long)n_cars);
     CTX_TRY(c);
     const unsigned nb = nblk(c->Z, cpm::kObjBlock);
-    if (c->obj_ws_B < B) {  // (hipFree waits for what still reads the old workspace)
-        dfree(c->d_obj_part);
-        dfree(c->d_obj_part_n);
-        c->obj_ws_B = 0;
-        HIP_TRY(hipMalloc(&c->d_obj_part, sizeof(double) * nb * static_cast<size_t>(B)));
-        HIP_TRY(hipMalloc(&c->d_obj_part_n, sizeof(int) * nb * static_cast<size_t>(B)));
-        c->obj_ws_B = B;
-    }
+    HIP_TRY(c->d_obj_part.reserve(nb * static_cast<size_t>(B)));  // (a grow frees first: hipFree waits for what still reads the old workspace)
+    HIP_TRY(c->d_obj_part_n.reserve(nb * static_cast<size_t>(B)));
     const int T = static_cast<int>(c->T);
     unsigned long long *obj = static_cast<unsigned long long *>(d_obj);
     // the hour sums are accumulated with atomics: the records start from zero
     HIP_TRY(hipMemsetAsync(obj, 0, sizeof(unsigned long long) * static_cast<size_t>(B) * static_cast<size_t>(cpm::kObjHead + 2 * T), c->stream));
     hipLaunchKernelGGL(cpm::k_obj_zones, dim3(nb, static_cast<unsigned>(B)), dim3(cpm::kObjBlock), 0, c->stream, static_cast<const long long *>(d_counts),
-                       c->have_measured ? c->d_measured : nullptr, c->have_measured ? c->d_meas_flag : nullptr, static_cast<long long>(n_cars),
+                       c->have_measured ? c->d_measured.get() : nullptr, c->have_measured ? c->d_meas_flag.get() : nullptr, static_cast<long long>(n_cars),
                        static_cast<int>(c->Z), T, obj, static_cast<double *>(d_zone_err), c->d_obj_part, c->d_obj_part_n);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cpm::k_obj_final, dim3(static_cast<unsigned>(B)), dim3(64), 0, c->stream, static_cast<const long long *>(d_counts), c->d_obj_part,
@@ -2975,60 +2835,51 @@ int32_t cpm_objectives_dev(cpm_ctx *c, const void *d_counts, int32_t B, int64_t 
 
 int32_t cpm_expected_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, void *d_out, void *d_pi_next)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!d_out) return fail(CPM_ERR_ARG, "expected_dev: null d_out");
-    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
-    CTX_TRY(c);
-    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
-    return expected_enqueue(c, static_cast<const double *>(d_pi0), flags, 1, c->d_pdrive, 0, static_cast<double *>(d_out), static_cast<double *>(d_pi_next));
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    return expected_enqueue(c, static_cast<const double *>(d_pi0), flags, tb.B, tb.pd, tb.q_stride, static_cast<double *>(d_out),
+                            static_cast<double *>(d_pi_next));
 }
 
 int32_t cpm_expected_batch_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, void *d_out)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!d_out) return fail(CPM_ERR_ARG, "expected_batch_dev: null d_out");
-    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
-    CTX_TRY(c);
-    if (c->batch_B < 1) return fail(CPM_ERR_STATE, "expected: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
-    return expected_enqueue(c, static_cast<const double *>(d_pi0), flags, c->batch_B, c->d_pdrive_b, static_cast<size_t>(c->Z * c->T),
-                            static_cast<double *>(d_out), nullptr);
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    return expected_enqueue(c, static_cast<const double *>(d_pi0), flags, tb.B, tb.pd, tb.q_stride, static_cast<double *>(d_out), nullptr);
 }
 
 int32_t cpm_expected(cpm_ctx *c, const double *pi0, uint32_t flags, double *parking, double *driving, double *pi_next)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!parking || !driving) return fail(CPM_ERR_ARG, "expected: null density outputs");
-    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
-    CTX_TRY(c);
-    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
-    return expected_blocking(c, pi0, flags, 1, c->d_pdrive, 0, parking, driving, pi_next);
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    return expected_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, parking, driving, pi_next);
 }
 
 int32_t cpm_expected_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double *parking, double *driving)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!parking || !driving) return fail(CPM_ERR_ARG, "expected_batch: null density outputs");
-    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
-    CTX_TRY(c);
-    if (c->batch_B < 1) return fail(CPM_ERR_STATE, "expected: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
-    return expected_blocking(c, pi0, flags, c->batch_B, c->d_pdrive_b, static_cast<size_t>(c->Z * c->T), parking, driving, nullptr);
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    return expected_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, parking, driving, nullptr);
 }
 
 // ------------------------------------------------------------------ expected travel (include/cpm_expected_travel.h)
 
 int32_t cpm_expected_trip_dev(cpm_ctx *c, void *d_w)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!d_w) return fail(CPM_ERR_ARG, "expected_trip_dev: null d_w");
     CTX_TRY(c);
     if ((rc = ensure_exp_trip(c)) != CPM_OK) return rc;
@@ -3038,9 +2889,8 @@ int32_t cpm_expected_trip_dev(cpm_ctx *c, void *d_w)
 
 int32_t cpm_expected_trip(cpm_ctx *c, double *w_sec, double *w_km)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!w_sec || !w_km) return fail(CPM_ERR_ARG, "expected_trip: null outputs");
     CTX_TRY(c);
     if ((rc = ensure_exp_trip(c)) != CPM_OK) return rc;
@@ -3053,9 +2903,8 @@ int32_t cpm_expected_trip(cpm_ctx *c, double *w_sec, double *w_km)
 
 int32_t cpm_expected_travel_dev(cpm_ctx *c, const void *d_expected, int32_t B, void *d_travel, void *d_totals)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!d_expected) return fail(CPM_ERR_ARG, "expected_travel_dev: null d_expected");
     if (B < 1) return fail(CPM_ERR_ARG, "expected_travel_dev: B = %d", B);
     if (!d_travel && !d_totals) return fail(CPM_ERR_ARG, "expected_travel_dev: d_travel and d_totals are both null");
@@ -3065,33 +2914,28 @@ int32_t cpm_expected_travel_dev(cpm_ctx *c, const void *d_expected, int32_t B, v
 
 int32_t cpm_expected_travel(cpm_ctx *c, const double *pi0, uint32_t flags, double *seconds, double *km, double *totals)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!seconds || !km) return fail(CPM_ERR_ARG, "expected_travel: null outputs");
-    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
-    CTX_TRY(c);
-    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
-    return expected_travel_blocking(c, pi0, flags, 1, c->d_pdrive, 0, seconds, km, totals);
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    return expected_travel_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, seconds, km, totals);
 }
 
 int32_t cpm_expected_travel_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double *seconds, double *km, double *totals)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!seconds || !km) return fail(CPM_ERR_ARG, "expected_travel_batch: null outputs");
-    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
-    CTX_TRY(c);
-    if (c->batch_B < 1) return fail(CPM_ERR_STATE, "expected: no batch tables (cpm_set_p_drive_batch / cpm_build_p_drive_batch)");
-    return expected_travel_blocking(c, pi0, flags, c->batch_B, c->d_pdrive_b, static_cast<size_t>(c->Z * c->T), seconds, km, totals);
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    return expected_travel_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, seconds, km, totals);
 }
 
 int64_t cpm_expected_trip_builds(const cpm_ctx *c)
 {
-    const int32_t rc = exp_device_check();
+    const int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     return c->exp_trip_builds;
 }
 
@@ -3100,14 +2944,12 @@ int64_t cpm_expected_trip_builds(const cpm_ctx *c)
 int32_t cpm_expected_grad_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext, void *d_grad_p_drive,
                               void *d_grad_pi0)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_grad_dev: null d_cotangent");
     if (!d_grad_p_drive) return fail(CPM_ERR_ARG, "expected_grad_dev: null d_grad_p_drive");
-    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
-    CTX_TRY(c);
-    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
     return expected_grad_enqueue(c, static_cast<const double *>(d_pi0), flags, static_cast<const double *>(d_cotangent), static_cast<const double *>(d_gnext),
                                  static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0));
 }
@@ -3115,14 +2957,12 @@ int32_t cpm_expected_grad_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, con
 int32_t cpm_expected_grad(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
                           double *grad_p_drive, double *grad_pi0)
 {
-    int32_t rc = exp_device_check();
+    int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!c) return fail(CPM_ERR_ARG, "null context");
     if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_grad: null cotangents");
     if (!grad_p_drive) return fail(CPM_ERR_ARG, "expected_grad: null grad_p_drive");
-    if ((rc = exp_flags_check(flags)) != CPM_OK) return rc;
-    CTX_TRY(c);
-    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected: p_drive not set");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
     return expected_grad_blocking(c, pi0, flags, g_parking, g_driving, g_next, grad_p_drive, grad_pi0);
 }
 
@@ -3191,24 +3031,15 @@ int32_t cpm_resample_batch(cpm_ctx *c, const uint64_t *seeds, uint32_t flags, in
         fleet.use(b);
         int32_t r = resample_blocking(c, seeds[b], flags);
         if (r != CPM_OK) return r;
-        std::memcpy(parking + b * zt, c->h_counts, sizeof(int64_t) * zt);
-        std::memcpy(driving + b * zt, c->h_counts + zt, sizeof(int64_t) * zt);
-        if (sum_tt_q16) sum_tt_q16[b] = c->h_counts[2 * zt];
+        copy_counts(c, parking, driving, sum_tt_q16, b);
         return CPM_OK;
     };
     if (!batch_grouped(c)) {  // the grouped path would not run this problem: every fleet with the context's kernel choice
         for (int b = 0; b < B && rc == CPM_OK; ++b) rc = single(b);
         return rc;
     }
-    if (c->bcounts_cap < B) {
-        dfree(c->d_bcounts);
-        if (c->h_bcounts) (void)hipHostFree(c->h_bcounts);
-        c->h_bcounts = nullptr;
-        c->bcounts_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_bcounts, sizeof(int64_t) * nwords * B));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_bcounts), sizeof(int64_t) * nwords * B));
-        c->bcounts_cap = B;
-    }
+    HIP_TRY(c->d_bcounts.reserve(nwords * B));
+    HIP_TRY(c->h_bcounts.reserve(nwords * B));
     std::vector<int32_t> todo(B);
     for (int b = 0; b < B; ++b) todo[b] = b;
     std::vector<char> by_single(B, 0);
@@ -3242,17 +3073,13 @@ int32_t cpm_resample_batch(cpm_ctx *c, const uint64_t *seeds, uint32_t flags, in
     }
     for (int b = 0; b < B; ++b) {
         if (by_single[b]) continue;
-        const int64_t *h = c->h_bcounts + b * nwords;
-        std::memcpy(parking + b * zt, h, sizeof(int64_t) * zt);
-        std::memcpy(driving + b * zt, h + zt, sizeof(int64_t) * zt);
-        if (sum_tt_q16) sum_tt_q16[b] = h[2 * zt];
+        copy_counts(c, parking, driving, sum_tt_q16, b, c->h_bcounts + b * nwords);
     }
     c->last_batch_fleets = batched;
     if (batched > 0) {
         c->last_kernel = CPM_KERNEL_ZONE_GROUPED;
         c->last_form = CPM_FORM_BATCH;
         c->last_hour = c->zb.last_hour_counted;
-    c->last_cells = c->zb.last_cells;
         c->last_cells = c->zb.last_cells;
     }
     return CPM_OK;
@@ -3283,8 +3110,8 @@ int32_t cpm_resample_batch_dev(cpm_ctx *c, const uint64_t *seeds, uint32_t flags
     rc = batch_enqueue(c, std::vector<uint64_t>(seeds, seeds + B), all, all, flags, counts);
     if (rc != CPM_OK) return rc;
     if (!c->bstatus_pending) {  // (one step's status in flight at a time: a later one is looked at when that one has been)
-        if (!c->d_bstatus) HIP_TRY(hipMalloc(&c->d_bstatus, sizeof(unsigned long long)));
-        if (!c->h_bstatus) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_bstatus), sizeof(unsigned long long)));
+        HIP_TRY(c->d_bstatus.reserve(1));
+        HIP_TRY(c->h_bstatus.reserve(1));
         if (!c->bstatus_ev) HIP_TRY(hipEventCreateWithFlags(&c->bstatus_ev, hipEventDisableTiming));
         hipLaunchKernelGGL(cpm::k_batch_status, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<const unsigned long long *>(counts), nwords, B, c->d_bstatus);
         HIP_TRY(hipGetLastError());
