@@ -63,6 +63,10 @@ EXPECTED_TRAVEL_SYMBOLS = ["cpm_expected_trip_dev", "cpm_expected_trip", "cpm_ex
 # every symbol include/cpm_expected_grad.h declares (checked by tests/test_expected_grad.py); a header and a list of its own, likewise
 EXPECTED_GRAD_SYMBOLS = ["cpm_expected_grad_dev", "cpm_expected_grad"]
 
+# every symbol include/cpm_expected_grad_dest.h declares (checked by tests/test_expected_grad_dest.py); a header and a list of its own, likewise
+EXPECTED_GRAD_DEST_SYMBOLS = ["cpm_set_p_dest_tangent", "cpm_build_p_dest_tangent", "cpm_get_p_dest_tangent", "cpm_expected_grad_dest_dev",
+                              "cpm_expected_grad_dest", "cpm_expected_trip_tangent_dev", "cpm_expected_trip_tangent"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -113,6 +117,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_travel.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad_dest.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -212,8 +217,15 @@ def load():
     L.cpm_expected_trip_builds.argtypes = [vp]
     L.cpm_expected_grad_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     L.cpm_expected_grad.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    L.cpm_set_p_dest_tangent.argtypes = [vp, vp]
+    L.cpm_build_p_dest_tangent.argtypes = [vp, vp]
+    L.cpm_get_p_dest_tangent.argtypes = [vp, vp]
+    L.cpm_expected_grad_dest_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    L.cpm_expected_grad_dest.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.cpm_expected_trip_tangent_dev.argtypes = [vp, vp]
+    L.cpm_expected_trip_tangent.argtypes = [vp, vp, vp]
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
-                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS):
+                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

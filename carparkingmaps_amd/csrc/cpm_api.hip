@@ -23,6 +23,7 @@
 #include "../../include/cpm_expected.h"
 #include "../../include/cpm_expected_travel.h"
 #include "../../include/cpm_expected_grad.h"
+#include "../../include/cpm_expected_grad_dest.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -41,6 +42,7 @@
 #include "cpm_expected.h"
 #include "cpm_expected_travel.h"
 #include "cpm_expected_grad.h"
+#include "cpm_expected_grad_dest.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -265,6 +267,15 @@ struct cpm_ctx {
     // the adjoint of the expected densities (include/cpm_expected_grad.h, cpm_expected_grad.h)
     DevBuf<double> d_exp_gws;           // [N + 4 + segments][Zs]: pi_s of the N = 2T - 1 operators, x ping and pong, mu ping and pong, the segments' sums
     DevBuf<double> d_exp_gio;           // [2][T][Z] + [Z] + [T][Z] + [Z] + [Z]: the blocking call's cotangents, G_next, grad_p_drive, grad_pi0 and pi_0
+    // the adjoint along a tangent of p_destin (include/cpm_expected_grad_dest.h, cpm_expected_grad_dest.h)
+    DevBuf<double> d_tan;               // [T][Z dest][Z origin] the tangent table, allocated by the first call that installs one
+    bool tan_valid = false;             // ... and whether it belongs to the installed p_destin tables (dropped by every call that installs them)
+    bool dest_built = false;            // the installed p_destin came from cpm_build_p_dest on the datamatrix still resident, at ...
+    double dest_built_e = 0.0;          // ... this exponent
+    int dest_built_int = 0;
+    DevBuf<double> d_tan_m;             // [T][Z] the rows' sums of p * log(x) of the dense builder
+    DevBuf<double> d_tan_w;             // [2][T][Z] the blocking trip-tangent call's dw_sec | dw_km
+    DevBuf<double> d_exp_gdio;          // [T][Z] the blocking call's grad_dest
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -291,6 +302,14 @@ static hipError_t ensure_stream(cpm_ctx *c)
 
 
 namespace {
+
+// Every call that installs p_destin tables, and every new datamatrix: the tangent table no longer belongs to the tables, and they
+// no longer come from cpm_build_p_dest on the resident datamatrix (cpm_build_p_dest says so again when it has succeeded).
+void drop_dest_tangent(cpm_ctx *c)
+{
+    c->tan_valid = false;
+    c->dest_built = false;
+}
 
 int32_t ensure_cars(cpm_ctx *c, int64_t n)
 {
@@ -1539,6 +1558,161 @@ int32_t expected_grad_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, co
     return CPM_OK;
 }
 
+// ------------------------------------------------------------------ the adjoint along a tangent of p_destin (include/cpm_expected_grad_dest.h)
+int32_t tangent_ready(const cpm_ctx *c, const char *what)
+{
+    if (!c->tan_valid || !c->d_tan)
+        return fail(CPM_ERR_STATE, "%s: no tangent of the installed p_destin tables (cpm_set_p_dest_tangent or cpm_build_p_dest_tangent)", what);
+    return CPM_OK;
+}
+
+// expected_grad_enqueue with the fused product and the finishing kernel of cpm_expected_grad_dest.h: the same forward propagation, the
+// same workspace with the segments' sums of w behind those of a.  grad_dest: [T][Z].
+int32_t expected_grad_dest_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, const double *cot, const double *gnext, double *grad_pd, double *grad_pi0,
+                                   double *grad_dest)
+{
+    int32_t rc = exp_tables_ready(c, "expected");
+    if (rc != CPM_OK) return rc;
+    if ((rc = tangent_ready(c, "expected_grad_dest")) != CPM_OK) return rc;
+    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
+    const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
+    const int most = 2 * T - 1;   // operators under CPM_EXPECT_IVP: the workspace is sized once
+    HIP_TRY(c->d_exp_gws.reserve(static_cast<size_t>(most + 4 + 2 * nseg) * Zs));
+    double *ws_pi = c->d_exp_gws;
+    double *ws_x[2] = {ws_pi + static_cast<size_t>(most) * Zs, ws_pi + static_cast<size_t>(most + 1) * Zs};
+    double *ws_mu[2] = {ws_pi + static_cast<size_t>(most + 2) * Zs, ws_pi + static_cast<size_t>(most + 3) * Zs};
+    double *part = ws_pi + static_cast<size_t>(most + 4) * Zs;
+    double *part_dp = part + static_cast<size_t>(nseg) * Zs;
+    const double *pd = c->d_pdrive;
+    const size_t zt = static_cast<size_t>(Z) * T;
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
+    auto hour_of = [pre](int s) { return s < pre ? s : s - pre; };
+
+    cpm::launch(cpm::k_exp_init, dim3(nblk(Z, cpm::kExpBlock), 1u), dim3(cpm::kExpBlock), 0, c->stream, d_pi0, pd, static_cast<size_t>(0), Z, Zs, ws_pi,
+                ws_x[0], static_cast<double *>(nullptr), static_cast<double *>(nullptr), static_cast<size_t>(0));
+    HIP_TRY(hipGetLastError());
+    for (int s = 0; s + 1 < steps; ++s) {
+        const int t = hour_of(s), t_next = hour_of(s + 1);
+        launch_exp_hour<1>(c, t, pd + static_cast<size_t>(t) * Z, pd + static_cast<size_t>(t_next) * Z, 0, ws_pi + static_cast<size_t>(s) * Zs, ws_x[s & 1],
+                           ws_pi + static_cast<size_t>(s + 1) * Zs, ws_x[(s + 1) & 1], nullptr, nullptr, 0, Zs, 1);
+        HIP_TRY(hipGetLastError());
+    }
+
+    const double *mu = gnext;  // (nullptr: zero by construction, the products of the last operator are skipped)
+    for (int s = steps - 1; s >= 0; --s) {
+        const int t = hour_of(s), j = s - pre;
+        const size_t row = static_cast<size_t>(t) * Z;
+        if (mu) {
+            const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg));
+            if (Z & 1) cpm::launch(cpm::k_exp_grad_dest_u<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, c->d_tan + row * Z, mu, Z, Zs, seg_len,
+                                   part, part_dp);
+            else cpm::launch(cpm::k_exp_grad_dest_u<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, c->d_tan + row * Z, mu, Z, Zs, seg_len,
+                             part, part_dp);
+            HIP_TRY(hipGetLastError());
+        }
+        double *mu_out = (s == 0 && grad_pi0) ? grad_pi0 : ws_mu[s & 1];
+        const double *gp = j >= 0 ? cot + static_cast<size_t>(j) * Z : nullptr;
+        const double *gd = j >= 0 ? cot + zt + static_cast<size_t>(j) * Z : nullptr;
+        cpm::launch(cpm::k_exp_grad_dest_finish, dim3(nblk(Z, cpm::kFinishBlock)), dim3(cpm::kFinishBlock), 0, c->stream, part, part_dp, nseg, Zs,
+                    c->d_last + row, c->d_exp_ell + row, c->d_exp_r + row, pd + row, ws_pi + static_cast<size_t>(s) * Zs, mu, gp, gd, Z, s < pre ? 1 : 0, mu_out,
+                    grad_pd + row, grad_dest + row);
+        HIP_TRY(hipGetLastError());
+        mu = mu_out;
+    }
+    return CPM_OK;
+}
+
+int32_t expected_grad_dest_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                                    double *grad_pd, double *grad_pi0, double *grad_dest)
+{
+    const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T);
+    int32_t rc = check_pi0(c, pi0);
+    if (rc != CPM_OK) return rc;
+    for (size_t i = 0; i < zt; ++i)
+        if (!std::isfinite(g_parking[i]) || !std::isfinite(g_driving[i]))
+            return fail(CPM_ERR_ARG, "expected_grad_dest: the cotangent of zone %lld, hour %lld is not finite", (long long)(i % Z) + 1, (long long)(i / Z) + 1);
+    if (g_next)
+        for (size_t z = 0; z < Z; ++z)
+            if (!std::isfinite(g_next[z])) return fail(CPM_ERR_ARG, "expected_grad_dest: g_next of zone %lld is not finite", (long long)z + 1);
+    HIP_TRY(c->d_exp_gio.reserve(3 * zt + 3 * Z));
+    HIP_TRY(c->d_exp_gdio.reserve(zt));
+    double *d_cot = c->d_exp_gio, *d_gnext = d_cot + 2 * zt, *d_grad = d_gnext + Z, *d_gpi0 = d_grad + zt, *d_pi0 = d_gpi0 + Z;
+    HIP_TRY(hipMemcpyAsync(d_cot, g_parking, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_cot + zt, g_driving, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+    if (g_next) HIP_TRY(hipMemcpyAsync(d_gnext, g_next, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    rc = expected_grad_dest_enqueue(c, pi0 ? d_pi0 : nullptr, flags, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr, c->d_exp_gdio);
+    if (rc != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(grad_pd, d_grad, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    if (grad_pi0) HIP_TRY(hipMemcpyAsync(grad_pi0, d_gpi0, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(grad_dest, c->d_exp_gdio, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+// d p_destin / d e_dest of the installed tables into d_tan (enqueued on the context's stream): from the compact rows when the tables
+// are the dataset route's, else from the datamatrix and the dense p_destin array.
+int32_t build_dest_tangent(cpm_ctx *c)
+{
+    if (!c->have_cdf || !c->dest_built)
+        return fail(CPM_ERR_STATE, "build_p_dest_tangent: the installed p_destin tables do not come from cpm_build_p_dest on the resident datamatrix");
+    if (!c->have_dmat) return fail(CPM_ERR_STATE, "build_p_dest_tangent: no datamatrix is resident");
+    if (!(c->dest_built_e > 0.0)) return fail(CPM_ERR_STATE, "build_p_dest_tangent: the tables were built with e_dest = %g; the tangent needs e_dest > 0", c->dest_built_e);
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t cells = static_cast<size_t>(Z) * Z * T;
+    c->tan_valid = false;
+    HIP_TRY(c->d_tan.reserve(cells));
+    if (c->sparse_tables) {
+        if (c->tables_uploaded || !c->ds_valid || !c->ds_ok)
+            return fail(CPM_ERR_STATE, "build_p_dest_tangent: the compact rows these tables were built from are gone");
+        const int64_t rows = c->T * c->Z;
+        HIP_TRY(hipMemsetAsync(c->d_tan, 0, sizeof(double) * cells, c->stream));
+        cpm::launch(cpm::k_tan_cells, dim3(nblk(rows, 64)), dim3(64), 0, c->stream, c->d_ds_cells.get(), c->d_sp.get(), c->d_sj.get(), c->d_scnt.get(),
+                    cpm::kDsCap, rows, Z, c->d_tan.get());
+        HIP_TRY(hipGetLastError());
+    } else {
+        if (!c->d_p) return fail(CPM_ERR_STATE, "build_p_dest_tangent: p_dest not set");
+        HIP_TRY(c->d_tan_m.reserve(static_cast<size_t>(Z) * T));
+        const dim3 g1(nblk(Z, 256), static_cast<unsigned>(Z));
+        if (T == 24) cpm::launch(cpm::k_tan_log<24>, g1, dim3(256), 0, c->stream, c->d_dm.get(), c->d_p.get(), c->d_tan.get(), Z, T);
+        else cpm::launch(cpm::k_tan_log<0>, g1, dim3(256), 0, c->stream, c->d_dm.get(), c->d_p.get(), c->d_tan.get(), Z, T);
+        HIP_TRY(hipGetLastError());
+        cpm::launch(cpm::k_tan_rowsum, dim3(nblk(Z, 64), static_cast<unsigned>(T)), dim3(64), 0, c->stream, c->d_p.get(), c->d_tan.get(), c->d_tan_m.get(), Z);
+        HIP_TRY(hipGetLastError());
+        cpm::launch(cpm::k_tan_final, dim3(nblk(Z, 256), nblk(Z, cpm::kDivBatch), static_cast<unsigned>(T)), dim3(256), 0, c->stream, c->d_p.get(),
+                    c->d_tan_m.get(), c->d_tan.get(), Z);
+        HIP_TRY(hipGetLastError());
+    }
+    c->tan_valid = true;
+    return CPM_OK;
+}
+
+// the tangent of the trip weights into d_dw [2][T][Z] (enqueued): k_exp_trip on the tangent table, then the segments in order
+int32_t trip_tangent_enqueue(cpm_ctx *c, double *d_dw)
+{
+    int32_t rc = exp_tables_ready(c, "expected_trip_tangent");
+    if (rc != CPM_OK) return rc;
+    if ((rc = tangent_ready(c, "expected_trip_tangent")) != CPM_OK) return rc;
+    if (!c->have_dmat) return fail(CPM_ERR_STATE, "expected_trip_tangent: datamatrix not set (cpm_set_datamatrix, cpm_createdatamatrix_* or cpm_synth_datamatrix)");
+    if (!c->have_dist) return fail(CPM_ERR_STATE, "expected_trip_tangent: distance matrix not set (cpm_set_distance* or the dist of cpm_set_datamatrix)");
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t zt = static_cast<size_t>(Z) * T;
+    const int nseg = cpm::trip_segments(Z, T), seg_len = cpm::trip_segment_len(Z, nseg);
+    HIP_TRY(c->d_exp_wpart.reserve(2 * zt * nseg));  // (scratch of the trip weights' own build: nothing reads it afterwards)
+    const dim3 grid(nblk(Z, cpm::kTripStrip), static_cast<unsigned>(T), static_cast<unsigned>(nseg));
+    if (Z & 1) cpm::launch(cpm::k_exp_trip<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(c->d_tan.get()),
+                           static_cast<const double *>(c->d_dm.get()), static_cast<const double *>(c->d_dist.get()), Z, T, seg_len, c->d_exp_wpart.get());
+    else cpm::launch(cpm::k_exp_trip<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(c->d_tan.get()),
+                     static_cast<const double *>(c->d_dm.get()), static_cast<const double *>(c->d_dist.get()), Z, T, seg_len, c->d_exp_wpart.get());
+    HIP_TRY(hipGetLastError());
+    cpm::launch(cpm::k_exp_trip_tan_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream,
+                static_cast<const double *>(c->d_exp_wpart.get()), nseg, static_cast<const double *>(c->d_last), Z, T, d_dw);
+    HIP_TRY(hipGetLastError());
+    return CPM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1810,6 +1984,7 @@ int32_t cpm_set_p_dest(cpm_ctx *c, const double *p_dest)
     size_t bytes = sizeof(double) * c->Z * c->Z * c->T;
     HIP_TRY(c->d_p.reserve(bytes / sizeof(double)));
     c->have_cdf = false;
+    drop_dest_tangent(c);
     HIP_TRY(hipMemcpyAsync(c->d_p, p_dest, bytes, hipMemcpyHostToDevice, c->stream));
     if (c->sparse_upload) {  // sparse row packs where the table qualifies (cpm_upload.h)
         bool done = false;
@@ -1835,6 +2010,7 @@ int32_t cpm_set_datamatrix(cpm_ctx *c, const double *datamatrix, const double *d
     c->tt_valid = false;
     c->tts_valid = false;
     c->ds_valid = false;
+    drop_dest_tangent(c);
     c->pdrive_mean_valid = false;
     c->exp_trip_valid = false;
     HIP_TRY(hipMemcpyAsync(c->d_dm, datamatrix, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1868,6 +2044,7 @@ static int32_t datamatrix_from_device_rows(cpm_ctx *c, const double *d_raw, int6
     c->tt_valid = false;
     c->tts_valid = false;
     c->ds_valid = false;
+    drop_dest_tangent(c);
     c->pdrive_mean_valid = false;
     c->exp_trip_valid = false;
     HIP_TRY(hipMemsetAsync(c->d_dm, 0, sizeof(double) * cells * 2, c->stream));  // zeros(number_zones, number_zones, T, 2) (:7)
@@ -2056,7 +2233,20 @@ int32_t cpm_build_p_drive(cpm_ctx *c, double p_min, double p_max, double e_drive
     return CPM_OK;
 }
 
+static int32_t build_p_dest_tables(cpm_ctx *c, double e_dest, int32_t e_is_integer, double *out);
+
 int32_t cpm_build_p_dest(cpm_ctx *c, double e_dest, int32_t e_is_integer, double *out)
+{
+    const int32_t rc = build_p_dest_tables(c, e_dest, e_is_integer, out);
+    if (rc == CPM_OK) {  // what cpm_build_p_dest_tangent differentiates (include/cpm_expected_grad_dest.h)
+        c->dest_built = true;
+        c->dest_built_e = e_dest;
+        c->dest_built_int = e_is_integer;
+    }
+    return rc;
+}
+
+static int32_t build_p_dest_tables(cpm_ctx *c, double e_dest, int32_t e_is_integer, double *out)
 {
     CTX_TRY(c);
     {   // a pending asynchronous IVP must be committed (or, after an overflow, repeated) on the tables it was enqueued with
@@ -2064,6 +2254,7 @@ int32_t cpm_build_p_dest(cpm_ctx *c, double e_dest, int32_t e_is_integer, double
         if (rc_ivp != CPM_OK) return rc_ivp;
     }
     if (!c->have_dmat) return fail(CPM_ERR_STATE, "build_p_dest: datamatrix first (cpm_set_datamatrix or cpm_createdatamatrix_*)");
+    drop_dest_tangent(c);
     size_t bytes = sizeof(double) * c->Z * c->Z * c->T;
     {   // a sparse datamatrix: everything from its compact rows (cpm_dataset.h); p_destin itself only when the caller wants the array
         bool done = false;
@@ -2146,6 +2337,7 @@ int32_t cpm_synth_tables_skewed(cpm_ctx *c, uint64_t table_seed, int64_t skew_q)
     c->have_pdrive = true;
     HIP_TRY(c->d_p.reserve(static_cast<size_t>(c->Z * c->Z * c->T)));
     c->have_cdf = false;
+    drop_dest_tangent(c);
     dim3 grid(nblk(c->Z, 64), static_cast<unsigned>(c->T));
     hipLaunchKernelGGL(cpm::k_synth_p_dest, grid, dim3(64), 0, c->stream, c->d_p, static_cast<int>(c->Z), table_seed, skew_q);
     HIP_TRY(hipGetLastError());
@@ -2168,6 +2360,7 @@ int32_t cpm_synth_datamatrix(cpm_ctx *c, uint64_t table_seed, double density)
     c->tt_valid = false;
     c->tts_valid = false;
     c->ds_valid = false;
+    drop_dest_tangent(c);
     c->pdrive_mean_valid = false;
     c->exp_trip_valid = false;
     hipLaunchKernelGGL(cpm::k_synth_datamatrix, dim3(nblk(c->Z, 256), static_cast<unsigned>(c->Z), static_cast<unsigned>(c->T)), dim3(256), 0, c->stream,
@@ -2964,6 +3157,105 @@ int32_t cpm_expected_grad(cpm_ctx *c, const double *pi0, uint32_t flags, const d
     ExpTables tb;
     if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
     return expected_grad_blocking(c, pi0, flags, g_parking, g_driving, g_next, grad_p_drive, grad_pi0);
+}
+
+// ------------------------------------------------------------------ adjoint along a tangent of p_destin (include/cpm_expected_grad_dest.h)
+
+int32_t cpm_set_p_dest_tangent(cpm_ctx *c, const double *dp)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!dp) return fail(CPM_ERR_ARG, "set_p_dest_tangent: null dp");
+    CTX_TRY(c);
+    if ((rc = exp_tables_ready(c, "set_p_dest_tangent")) != CPM_OK) return rc;
+    const size_t Z = static_cast<size_t>(c->Z), cells = Z * Z * static_cast<size_t>(c->T);
+    for (size_t i = 0; i < cells; ++i)
+        if (!std::isfinite(dp[i]))
+            return fail(CPM_ERR_ARG, "set_p_dest_tangent: the entry of origin %lld, destination %lld, hour %lld is not finite", (long long)(i % Z) + 1,
+                        (long long)(i / Z % Z) + 1, (long long)(i / (Z * Z)) + 1);
+    c->tan_valid = false;
+    HIP_TRY(c->d_tan.reserve(cells));
+    HIP_TRY(hipMemcpyAsync(c->d_tan, dp, sizeof(double) * cells, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->tan_valid = true;
+    return CPM_OK;
+}
+
+int32_t cpm_build_p_dest_tangent(cpm_ctx *c, double *out)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    CTX_TRY(c);
+    if ((rc = build_dest_tangent(c)) != CPM_OK) return rc;
+    if (out) {
+        HIP_TRY(hipMemcpyAsync(out, c->d_tan, sizeof(double) * c->Z * c->Z * c->T, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return CPM_OK;
+}
+
+int32_t cpm_get_p_dest_tangent(cpm_ctx *c, double *out)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!out) return fail(CPM_ERR_ARG, "get_p_dest_tangent: null out");
+    CTX_TRY(c);
+    if ((rc = tangent_ready(c, "get_p_dest_tangent")) != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->d_tan, sizeof(double) * c->Z * c->Z * c->T, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+int32_t cpm_expected_grad_dest_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext, void *d_grad_p_drive,
+                                   void *d_grad_pi0, void *d_grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_grad_dest_dev: null d_cotangent");
+    if (!d_grad_p_drive || !d_grad_dest) return fail(CPM_ERR_ARG, "expected_grad_dest_dev: null d_grad_p_drive or d_grad_dest");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    return expected_grad_dest_enqueue(c, static_cast<const double *>(d_pi0), flags, static_cast<const double *>(d_cotangent),
+                                      static_cast<const double *>(d_gnext), static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0),
+                                      static_cast<double *>(d_grad_dest));
+}
+
+int32_t cpm_expected_grad_dest(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                               double *grad_p_drive, double *grad_pi0, double *grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_grad_dest: null cotangents");
+    if (!grad_p_drive || !grad_dest) return fail(CPM_ERR_ARG, "expected_grad_dest: null grad_p_drive or grad_dest");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    if ((rc = exp_tables_ready(c, "expected")) != CPM_OK) return rc;  // (state is refused before a cotangent is read or copied)
+    if ((rc = tangent_ready(c, "expected_grad_dest")) != CPM_OK) return rc;
+    return expected_grad_dest_blocking(c, pi0, flags, g_parking, g_driving, g_next, grad_p_drive, grad_pi0, grad_dest);
+}
+
+int32_t cpm_expected_trip_tangent_dev(cpm_ctx *c, void *d_dw)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_dw) return fail(CPM_ERR_ARG, "expected_trip_tangent_dev: null d_dw");
+    CTX_TRY(c);
+    return trip_tangent_enqueue(c, static_cast<double *>(d_dw));
+}
+
+int32_t cpm_expected_trip_tangent(cpm_ctx *c, double *dw_sec, double *dw_km)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!dw_sec || !dw_km) return fail(CPM_ERR_ARG, "expected_trip_tangent: null outputs");
+    CTX_TRY(c);
+    const size_t zt = static_cast<size_t>(c->Z) * c->T;
+    HIP_TRY(c->d_tan_w.reserve(2 * zt));
+    if ((rc = trip_tangent_enqueue(c, c->d_tan_w)) != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(dw_sec, c->d_tan_w, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dw_km, c->d_tan_w + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
 }
 
 // ------------------------------------------------------------------ batch (include/cpm_batch.h)

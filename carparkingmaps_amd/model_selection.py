@@ -146,6 +146,18 @@ def p_drive_param_grads(grad_p_drive, s, p_min, p_max, e_drive):
     return (float(np.sum(g * (1.0 - se))), float(np.sum(g * se)), float(np.sum(g * (float(p_max) - float(p_min)) * sel)))
 
 
+def e_dest_param_grad(grad_dest, driving=None, dw_sec=None):
+    """d objective / d e_dest from Sampler.expected_grad_dest's grad_dest under the tangent d p_destin / d e_dest: its sum, the term
+    through the densities.  For "A_drive" = sum(driving * w_sec) / (T * 3600) the weights depend on p_destin too: with driving and
+    Sampler.expected_trip_tangent()'s dw_sec the direct term sum(driving * dw_sec) / (T * 3600) is added, scaled as a_drive_grad scales
+    its cotangent."""
+    d = float(np.asarray(grad_dest, dtype=np.float64).sum())
+    if dw_sec is not None:
+        w = np.asarray(dw_sec, dtype=np.float64)
+        d += float((np.asarray(driving, dtype=np.float64) * w).sum() / (w.shape[1] * 3600.0))
+    return d
+
+
 def parking_density_zone_errors(parking, C, measured):
     """The definition of include/cpm_objectives.h on the host, one IEEE f64 operation per step and in its order: (err (Z,) float64
     with -1.0 for a zone that is not valid, valid (Z,) bool).  A zone is valid when its measured row, added in hour order, is != 0 and
@@ -215,6 +227,7 @@ class Evaluator:
     _e_dest: object = field(default=None, repr=False)
     _pipe: object = field(default=None, repr=False)
     _s_table: object = field(default=None, repr=False)   # build_p_drive(0, 1, 1): the datamatrix's own table, for expected_gradient
+    _tangent: object = field(default=None, repr=False)   # the e_dest key whose d p_destin / d e_dest is installed (expected_gradient, dest=True)
 
     def __post_init__(self):
         if self.measured_parking is not None:   # Julia order, like the count tensors: the error is evaluated hour-major on contiguous rows
@@ -231,6 +244,12 @@ class Evaluator:
         if key != self._e_dest:              # the CDF and the row packs are rebuilt only when e_dest changes
             self.sampler.build_p_dest(e_dest, want=False)
             self._e_dest = key
+            self._tangent = None             # (the library drops the tangent with the tables it belonged to)
+
+    def _install_dest_tangent(self):
+        if self._tangent != self._e_dest:    # rebuilt only when e_dest changes, like the tables
+            self.sampler.build_p_dest_tangent(want=False)
+            self._tangent = self._e_dest
 
     def _objectives(self, pt, parking, driving, sum_tt_q16):
         act = traffic_activity(driving)
@@ -297,11 +316,14 @@ class Evaluator:
         self.sampler.build_p_drive_batch([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts])
         return self._expected_from_device(pts, ivp, True)
 
-    def expected_gradient(self, pt, objective, ivp=True):
+    def expected_gradient(self, pt, objective, ivp=True, dest=False):
         """The gradient of one noise-free objective of evaluate_expected(pt, ivp) -- "activity_error", "parking_error" or "A_drive" -- by
         one backward pass (Sampler.expected_grad): dict(objective, value, grad_p_drive (Z, T), grad_pi0 (Z,), d_p_min, d_p_max,
         d_e_drive).  The parameter derivatives are the chain rule through p_drive = p_min + (p_max - p_min) * s^e_drive with
-        s = build_p_drive(0, 1, 1), cached here (it depends on the datamatrix alone); pt's own tables are installed when this returns."""
+        s = build_p_drive(0, 1, 1), cached here (it depends on the datamatrix alone); pt's own tables are installed when this returns.
+        dest: the result also holds grad_dest (Z, T) and d_e_dest, from the same backward pass along d p_destin / d e_dest
+        (Sampler.build_p_dest_tangent, rebuilt only when e_dest changes; pt.e_dest > 0).  For "A_drive" d_e_dest includes the direct
+        term through the trip weights.  Without it nothing is built and the result is what it is without the argument."""
         if objective not in ("activity_error", "parking_error", "A_drive"):
             raise ValueError(f"expected_gradient: unknown objective {objective!r}")
         s = self.sampler
@@ -319,10 +341,19 @@ class Evaluator:
             gp, gd = parking_density_error_grad(r["parking"], self.measured_parking), zero
         else:
             gp, gd = zero, a_drive_grad(s.expected_trip()[0])
-        g = s.expected_grad(gp, gd, ivp=ivp)
+        if dest:
+            self._install_dest_tangent()
+            g = s.expected_grad_dest(gp, gd, ivp=ivp)
+        else:
+            g = s.expected_grad(gp, gd, ivp=ivp)
         d_min, d_max, d_e = p_drive_param_grads(g["grad_p_drive"], self._s_table, pt.p_min, pt.p_max, pt.e_drive)
-        return dict(objective=objective, value=r[objective], grad_p_drive=g["grad_p_drive"], grad_pi0=g["grad_pi0"],
-                    d_p_min=d_min, d_p_max=d_max, d_e_drive=d_e)
+        out = dict(objective=objective, value=r[objective], grad_p_drive=g["grad_p_drive"], grad_pi0=g["grad_pi0"],
+                   d_p_min=d_min, d_p_max=d_max, d_e_drive=d_e)
+        if dest:
+            direct = objective == "A_drive"
+            out["grad_dest"] = g["grad_dest"]
+            out["d_e_dest"] = e_dest_param_grad(g["grad_dest"], r["driving"] if direct else None, s.expected_trip_tangent()[0] if direct else None)
+        return out
 
     # -- device objectives: the record of include/cpm_objectives.h in the place of the count tensor --
     def _from_record(self, pt, rec):

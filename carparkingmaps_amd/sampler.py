@@ -662,6 +662,58 @@ class Sampler:
         _lib.check(self._L.cpm_expected_grad_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr),
                                                  p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr)))
 
+    # -- the adjoint along a tangent of p_destin (include/cpm_expected_grad_dest.h): the derivative for e_dest --
+    def set_p_dest_tangent(self, dp):
+        """Install a tangent of the p_destin tables: (Z, Z, T) float64 [origin, destination, hour], the layout of set_p_dest.  Every
+        call that installs p_destin tables, and every new datamatrix, drops it."""
+        a = _f64(dp, (self.Z, self.Z, self.T))
+        _lib.check(self._L.cpm_set_p_dest_tangent(self._h, _vp(a)))
+
+    def build_p_dest_tangent(self, want=False):
+        """d p_destin / d e_dest of the installed tables, built on the device from the resident datamatrix at the e_dest of the last
+        build_p_dest (which must have installed the tables, with e_dest > 0).  want: also return it, (Z, Z, T) float64 F-order."""
+        out = np.zeros((self.Z, self.Z, self.T), dtype=np.float64, order="F") if want else None
+        _lib.check(self._L.cpm_build_p_dest_tangent(self._h, _vp(out)))
+        return out
+
+    def get_p_dest_tangent(self):
+        out = np.zeros((self.Z, self.Z, self.T), dtype=np.float64, order="F")
+        _lib.check(self._L.cpm_get_p_dest_tangent(self._h, _vp(out)))
+        return out
+
+    def expected_grad_dest(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None):
+        """expected_grad() with one more output: dict(grad_p_drive, grad_pi0, grad_dest (Z, T) float64 F-order).  grad_dest[o, t] is the
+        derivative of L along the installed tangent restricted to row (o, t) of p_destin, the residual of the row held fixed;
+        grad_dest.sum() is the derivative of L along the tangent.  grad_p_drive and grad_pi0 carry expected_grad()'s bits."""
+        a = self._pi0(pi0)
+        gp = np.asfortranarray(_f64(g_parking, (self.Z, self.T)))
+        gd = np.asfortranarray(_f64(g_driving, (self.Z, self.T)))
+        gn = None if g_next is None else np.ascontiguousarray(_f64(g_next, (self.Z,)))
+        grad = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        grad_pi0 = np.zeros(self.Z, dtype=np.float64)
+        grad_dest = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        _lib.check(self._L.cpm_expected_grad_dest(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(gp), _vp(gd), _vp(gn), _vp(grad),
+                                                  _vp(grad_pi0), _vp(grad_dest)))
+        return dict(grad_p_drive=grad, grad_pi0=grad_pi0, grad_dest=grad_dest)
+
+    def expected_grad_dest_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_grad_dest_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0):
+        """Enqueue on the context's stream: the arguments of expected_grad_dev, and d_grad_dest_ptr = device address of float64[T][Z]."""
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        _lib.check(self._L.cpm_expected_grad_dest_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr),
+                                                      p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr), p(d_grad_dest_ptr)))
+
+    def expected_trip_tangent(self):
+        """(dw_sec, dw_km), each (Z, T) float64 F-order: the derivative of expected_trip()'s weights along the installed tangent, the
+        residual of every row held fixed."""
+        dw_sec = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        dw_km = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
+        _lib.check(self._L.cpm_expected_trip_tangent(self._h, _vp(dw_sec), _vp(dw_km)))
+        return dw_sec, dw_km
+
+    def expected_trip_tangent_dev(self, d_dw_ptr):
+        """Enqueue on the context's stream: d_dw_ptr = device address of float64[2][T][Z], dw_sec then dw_km."""
+        _lib.check(self._L.cpm_expected_trip_tangent_dev(self._h, C.c_void_p(int(d_dw_ptr)) if d_dw_ptr else None))
+
     def last_kernel_ms(self):
         buf = (C.c_float * 8192)()
         n = C.c_int32(0)
