@@ -67,6 +67,10 @@ EXPECTED_GRAD_SYMBOLS = ["cpm_expected_grad_dev", "cpm_expected_grad"]
 EXPECTED_GRAD_DEST_SYMBOLS = ["cpm_set_p_dest_tangent", "cpm_build_p_dest_tangent", "cpm_get_p_dest_tangent", "cpm_expected_grad_dest_dev",
                               "cpm_expected_grad_dest", "cpm_expected_trip_tangent_dev", "cpm_expected_trip_tangent"]
 
+# every symbol include/cpm_expected_grad_batch.h declares (checked by tests/test_expected_grad_batch.py); a header and a list of its own, likewise
+EXPECTED_GRAD_BATCH_SYMBOLS = ["cpm_expected_grad_batch_dev", "cpm_expected_grad_batch", "cpm_expected_grad_dest_batch_dev",
+                               "cpm_expected_grad_dest_batch"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -118,6 +122,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_travel.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad_dest.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad_batch.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -224,8 +229,12 @@ def load():
     L.cpm_expected_grad_dest.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp]
     L.cpm_expected_trip_tangent_dev.argtypes = [vp, vp]
     L.cpm_expected_trip_tangent.argtypes = [vp, vp, vp]
+    L.cpm_expected_grad_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    L.cpm_expected_grad_batch.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    L.cpm_expected_grad_dest_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    L.cpm_expected_grad_dest_batch.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp]
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
-                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS):
+                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS + EXPECTED_GRAD_BATCH_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

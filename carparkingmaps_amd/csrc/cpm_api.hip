@@ -24,6 +24,7 @@
 #include "../../include/cpm_expected_travel.h"
 #include "../../include/cpm_expected_grad.h"
 #include "../../include/cpm_expected_grad_dest.h"
+#include "../../include/cpm_expected_grad_batch.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -43,6 +44,7 @@
 #include "cpm_expected_travel.h"
 #include "cpm_expected_grad.h"
 #include "cpm_expected_grad_dest.h"
+#include "cpm_expected_grad_batch.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -1652,6 +1654,165 @@ int32_t expected_grad_dest_blocking(cpm_ctx *c, const double *pi0, uint32_t flag
     return CPM_OK;
 }
 
+// ------------------------------------------------------------------ the adjoint for the fleets of a batch (include/cpm_expected_grad_batch.h)
+// One backward product of a pass of nf > 1 fleets: the smallest instantiation that holds the pass.  dp_t: nullptr without the tangent.
+template <int NB>
+void launch_grad_u_b(cpm_ctx *c, const double *p_t, const double *dp_t, const double *mu, int Zs, int nseg, int seg_len, int nf, double *part, double *part_dp)
+{
+    const int Z = static_cast<int>(c->Z);
+    const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg)), block(cpm::kExpBlock);
+    if (dp_t) {
+        if (Z & 1) cpm::launch(cpm::k_exp_grad_dest_u_b<NB, true>, grid, block, 0, c->stream, p_t, dp_t, mu, Z, Zs, seg_len, nf, part, part_dp);
+        else cpm::launch(cpm::k_exp_grad_dest_u_b<NB, false>, grid, block, 0, c->stream, p_t, dp_t, mu, Z, Zs, seg_len, nf, part, part_dp);
+    } else {
+        if (Z & 1) cpm::launch(cpm::k_exp_grad_u_b<NB, true>, grid, block, 0, c->stream, p_t, mu, Z, Zs, seg_len, nf, part);
+        else cpm::launch(cpm::k_exp_grad_u_b<NB, false>, grid, block, 0, c->stream, p_t, mu, Z, Zs, seg_len, nf, part);
+    }
+}
+
+// expected_grad_enqueue / expected_grad_dest_enqueue for B fleets whose p_drive tables lie q_stride words apart at pd.  The forward
+// propagation is expected_enqueue's with pi_s of every operator and fleet kept; backward, operator-major with the passes of at most
+// kExpMaxNB fleets inside an operator.  cot: [B][2][T][Z]; gnext, grad_pi0: [B][Z] or nullptr; grad_pd, grad_dest: [B][T][Z];
+// grad_dest == nullptr: no tangent.  A pass of one fleet runs the B = 1 kernels.
+// d_exp_gws, in vectors of Zs words: pi [2T - 1][B], x ping and pong [B] each, mu ping and pong [B8] each (B8 = B rounded up to
+// whole passes; a pass's mu is [Zs][NB] at its first fleet's place), the segments' sums of one pass [nseg][kExpMaxNB], those of w
+// likewise.
+int32_t expected_grad_batch_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride, const double *cot,
+                                    const double *gnext, double *grad_pd, double *grad_pi0, double *grad_dest)
+{
+    int32_t rc = exp_tables_ready(c, "expected");
+    if (rc != CPM_OK) return rc;
+    if (grad_dest && (rc = tangent_ready(c, "expected_grad_dest_batch")) != CPM_OK) return rc;
+    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
+    const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
+    const int most = 2 * T - 1;   // operators under CPM_EXPECT_IVP: the workspace is sized once per B
+    const size_t nb = static_cast<size_t>(B), b8 = (nb + cpm::kExpMaxNB - 1) / cpm::kExpMaxNB * cpm::kExpMaxNB;
+    const size_t part_words = static_cast<size_t>(nseg) * cpm::kExpMaxNB * Zs;
+    HIP_TRY(c->d_exp_gws.reserve((most * nb + 2 * nb + 2 * b8) * Zs + 2 * part_words));
+    double *ws_pi = c->d_exp_gws;
+    double *ws_x[2] = {ws_pi + most * nb * Zs, ws_pi + (most + 1) * nb * Zs};
+    double *ws_mu[2] = {ws_pi + (most + 2) * nb * Zs, ws_pi + ((most + 2) * nb + b8) * Zs};
+    double *part = ws_pi + ((most + 2) * nb + 2 * b8) * Zs;
+    double *part_dp = part + part_words;
+    const size_t zt = static_cast<size_t>(Z) * T, cot_stride = 2 * zt;
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
+    auto hour_of = [pre](int s) { return s < pre ? s : s - pre; };
+
+    cpm::launch(cpm::k_exp_init, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream, d_pi0, pd, q_stride, Z, Zs, ws_pi,
+                ws_x[0], static_cast<double *>(nullptr), static_cast<double *>(nullptr), static_cast<size_t>(0));
+    HIP_TRY(hipGetLastError());
+    for (int s = 0; s + 1 < steps; ++s) {
+        const int t = hour_of(s), t_next = hour_of(s + 1);
+        for (int f0 = 0; f0 < B; f0 += cpm::kExpMaxNB) {
+            const int nf = std::min(B - f0, cpm::kExpMaxNB);
+            const size_t w0 = static_cast<size_t>(f0) * Zs;
+            using Go = void (*)(cpm_ctx *, int, const double *, const double *, size_t, const double *, const double *, double *, double *, double *, double *,
+                                size_t, int, int);
+            const Go go = nf > 4 ? Go(launch_exp_hour<8>) : nf > 2 ? Go(launch_exp_hour<4>) : nf > 1 ? Go(launch_exp_hour<2>) : Go(launch_exp_hour<1>);
+            go(c, t, pd + f0 * q_stride + static_cast<size_t>(t) * Z, pd + f0 * q_stride + static_cast<size_t>(t_next) * Z, q_stride,
+               ws_pi + static_cast<size_t>(s) * nb * Zs + w0, ws_x[s & 1] + w0, ws_pi + static_cast<size_t>(s + 1) * nb * Zs + w0, ws_x[(s + 1) & 1] + w0, nullptr,
+               nullptr, 0, Zs, nf);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+
+    bool have_mu = gnext != nullptr;  // (false: zero by construction, the products of the last operator are skipped for every fleet)
+    for (int s = steps - 1; s >= 0; --s) {
+        const int t = hour_of(s), j = s - pre;
+        const size_t row = static_cast<size_t>(t) * Z;
+        const double *p_t = c->d_p + row * Z, *dp_t = grad_dest ? c->d_tan + row * Z : nullptr;
+        const int acc = s < pre ? 1 : 0;
+        for (int f0 = 0; f0 < B; f0 += cpm::kExpMaxNB) {
+            const int nf = std::min(B - f0, cpm::kExpMaxNB);
+            const int NB = nf > 4 ? 8 : nf > 2 ? 4 : nf > 1 ? 2 : 1;
+            const size_t w0 = static_cast<size_t>(f0) * Zs;
+            const bool first = s == steps - 1;  // mu is G_next, as the caller laid it out
+            const double *mu = !have_mu ? nullptr : (first && nf == 1) ? gnext + static_cast<size_t>(f0) * Z : ws_mu[(s + 1) & 1] + w0;
+            const double *q_t = pd + f0 * q_stride + row;
+            const double *pi_s = ws_pi + static_cast<size_t>(s) * nb * Zs + w0;
+            const double *gp = j >= 0 ? cot + f0 * cot_stride + static_cast<size_t>(j) * Z : nullptr;
+            const double *gd = j >= 0 ? gp + zt : nullptr;
+            double *grad_t = grad_pd + f0 * zt + row, *dest_t = grad_dest ? grad_dest + f0 * zt + row : nullptr;
+            const bool to_pi0 = s == 0 && grad_pi0;
+            double *mu_out = to_pi0 ? grad_pi0 + static_cast<size_t>(f0) * Z : ws_mu[s & 1] + w0;
+            if (nf == 1) {  // the B = 1 kernels: mu is one vector, the segments' sums are [nseg][Zs]
+                if (mu) {
+                    const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg)), block(cpm::kExpBlock);
+                    if (dp_t) {
+                        if (Z & 1) cpm::launch(cpm::k_exp_grad_dest_u<true>, grid, block, 0, c->stream, p_t, dp_t, mu, Z, Zs, seg_len, part, part_dp);
+                        else cpm::launch(cpm::k_exp_grad_dest_u<false>, grid, block, 0, c->stream, p_t, dp_t, mu, Z, Zs, seg_len, part, part_dp);
+                    } else {
+                        if (Z & 1) cpm::launch(cpm::k_exp_grad_u<true>, grid, block, 0, c->stream, p_t, mu, Z, Zs, seg_len, part);
+                        else cpm::launch(cpm::k_exp_grad_u<false>, grid, block, 0, c->stream, p_t, mu, Z, Zs, seg_len, part);
+                    }
+                }
+                if (dest_t) cpm::launch(cpm::k_exp_grad_dest_finish, dim3(nblk(Z, cpm::kFinishBlock)), dim3(cpm::kFinishBlock), 0, c->stream, part, part_dp, nseg, Zs,
+                                        c->d_last + row, c->d_exp_ell + row, c->d_exp_r + row, q_t, pi_s, mu, gp, gd, Z, acc, mu_out, grad_t, dest_t);
+                else cpm::launch(cpm::k_exp_grad_finish, dim3(nblk(Z, cpm::kFinishBlock)), dim3(cpm::kFinishBlock), 0, c->stream, part, nseg, Zs, c->d_last + row,
+                                 c->d_exp_ell + row, c->d_exp_r + row, q_t, pi_s, mu, gp, gd, Z, acc, mu_out, grad_t);
+                continue;
+            }
+            if (mu) {
+                if (first) {
+                    double *packed = ws_mu[(s + 1) & 1] + w0;
+                    cpm::launch(cpm::k_exp_grad_pack_b, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(NB)), dim3(cpm::kExpBlock), 0, c->stream,
+                                gnext + static_cast<size_t>(f0) * Z, Z, NB, nf, packed);
+                }
+                using Go = void (*)(cpm_ctx *, const double *, const double *, const double *, int, int, int, int, double *, double *);
+                const Go go = NB == 8 ? Go(launch_grad_u_b<8>) : NB == 4 ? Go(launch_grad_u_b<4>) : Go(launch_grad_u_b<2>);
+                go(c, p_t, dp_t, mu, Zs, nseg, seg_len, nf, part, part_dp);
+            }
+            const dim3 grid(nblk(Z, cpm::kFinishBlock), static_cast<unsigned>(NB)), block(cpm::kFinishBlock);
+            const size_t mo_o = to_pi0 ? 1 : static_cast<size_t>(NB), mo_f = to_pi0 ? static_cast<size_t>(Z) : 1;
+            const int fill = to_pi0 ? 0 : 1;
+            if (dest_t) cpm::launch(cpm::k_exp_grad_dest_finish_b, grid, block, 0, c->stream, part, part_dp, nseg, Zs, c->d_last + row, c->d_exp_ell + row,
+                                    c->d_exp_r + row, q_t, q_stride, pi_s, mu, NB, gp, gd, cot_stride, Z, nf, acc, mu_out, mo_o, mo_f, fill, grad_t, dest_t, zt);
+            else cpm::launch(cpm::k_exp_grad_finish_b, grid, block, 0, c->stream, part, nseg, Zs, c->d_last + row, c->d_exp_ell + row, c->d_exp_r + row, q_t,
+                             q_stride, pi_s, mu, NB, gp, gd, cot_stride, Z, nf, acc, mu_out, mo_o, mo_f, fill, grad_t, zt);
+        }
+        HIP_TRY(hipGetLastError());
+        have_mu = true;
+    }
+    return CPM_OK;
+}
+
+// the blocking forms: d_exp_gio holds [B][2][T][Z] cotangents, [B][Z] G_next, [B][T][Z] grad_p_drive, [B][Z] grad_pi0 and pi_0 [Z];
+// d_exp_gdio [B][T][Z] grad_dest.  what: the entry, as its error text names it.
+int32_t expected_grad_batch_blocking(cpm_ctx *c, const char *what, const double *pi0, uint32_t flags, int B, const double *pd, size_t q_stride,
+                                     const double *g_parking, const double *g_driving, const double *g_next, double *grad_pd, double *grad_pi0, double *grad_dest)
+{
+    const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nb = static_cast<size_t>(B);
+    int32_t rc = check_pi0(c, pi0);
+    if (rc != CPM_OK) return rc;
+    for (size_t i = 0; i < nb * zt; ++i)
+        if (!std::isfinite(g_parking[i]) || !std::isfinite(g_driving[i]))
+            return fail(CPM_ERR_ARG, "%s: the cotangent of fleet %lld, zone %lld, hour %lld is not finite", what, (long long)(i / zt) + 1, (long long)(i % Z) + 1,
+                        (long long)(i % zt / Z) + 1);
+    if (g_next)
+        for (size_t i = 0; i < nb * Z; ++i)
+            if (!std::isfinite(g_next[i]))
+                return fail(CPM_ERR_ARG, "%s: g_next of fleet %lld, zone %lld is not finite", what, (long long)(i / Z) + 1, (long long)(i % Z) + 1);
+    HIP_TRY(c->d_exp_gio.reserve(nb * (3 * zt + 2 * Z) + Z));
+    if (grad_dest) HIP_TRY(c->d_exp_gdio.reserve(nb * zt));
+    double *d_cot = c->d_exp_gio, *d_gnext = d_cot + nb * 2 * zt, *d_grad = d_gnext + nb * Z, *d_gpi0 = d_grad + nb * zt, *d_pi0 = d_gpi0 + nb * Z;
+    for (size_t b = 0; b < nb; ++b) {
+        HIP_TRY(hipMemcpyAsync(d_cot + b * 2 * zt, g_parking + b * zt, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_cot + b * 2 * zt + zt, g_driving + b * zt, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+    }
+    if (g_next) HIP_TRY(hipMemcpyAsync(d_gnext, g_next, sizeof(double) * nb * Z, hipMemcpyHostToDevice, c->stream));
+    if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    rc = expected_grad_batch_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr,
+                                     grad_dest ? c->d_exp_gdio.get() : nullptr);
+    if (rc != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(grad_pd, d_grad, sizeof(double) * nb * zt, hipMemcpyDeviceToHost, c->stream));
+    if (grad_pi0) HIP_TRY(hipMemcpyAsync(grad_pi0, d_gpi0, sizeof(double) * nb * Z, hipMemcpyDeviceToHost, c->stream));
+    if (grad_dest) HIP_TRY(hipMemcpyAsync(grad_dest, c->d_exp_gdio, sizeof(double) * nb * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
 // d p_destin / d e_dest of the installed tables into d_tan (enqueued on the context's stream): from the compact rows when the tables
 // are the dataset route's, else from the datamatrix and the dense p_destin array.
 int32_t build_dest_tangent(cpm_ctx *c)
@@ -3232,6 +3393,63 @@ int32_t cpm_expected_grad_dest(cpm_ctx *c, const double *pi0, uint32_t flags, co
     if ((rc = exp_tables_ready(c, "expected")) != CPM_OK) return rc;  // (state is refused before a cotangent is read or copied)
     if ((rc = tangent_ready(c, "expected_grad_dest")) != CPM_OK) return rc;
     return expected_grad_dest_blocking(c, pi0, flags, g_parking, g_driving, g_next, grad_p_drive, grad_pi0, grad_dest);
+}
+
+// ------------------------------------------------------------------ the adjoint for the fleets of a batch (include/cpm_expected_grad_batch.h)
+int32_t cpm_expected_grad_batch_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext, void *d_grad_p_drive,
+                                    void *d_grad_pi0)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_grad_batch_dev: null d_cotangent");
+    if (!d_grad_p_drive) return fail(CPM_ERR_ARG, "expected_grad_batch_dev: null d_grad_p_drive");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    return expected_grad_batch_enqueue(c, static_cast<const double *>(d_pi0), flags, tb.B, tb.pd, tb.q_stride, static_cast<const double *>(d_cotangent),
+                                       static_cast<const double *>(d_gnext), static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0), nullptr);
+}
+
+int32_t cpm_expected_grad_batch(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                                double *grad_p_drive, double *grad_pi0)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_grad_batch: null cotangents");
+    if (!grad_p_drive) return fail(CPM_ERR_ARG, "expected_grad_batch: null grad_p_drive");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    if ((rc = exp_tables_ready(c, "expected")) != CPM_OK) return rc;  // (state is refused before a cotangent is read or copied)
+    return expected_grad_batch_blocking(c, "expected_grad_batch", pi0, flags, tb.B, tb.pd, tb.q_stride, g_parking, g_driving, g_next, grad_p_drive, grad_pi0,
+                                        nullptr);
+}
+
+int32_t cpm_expected_grad_dest_batch_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext, void *d_grad_p_drive,
+                                         void *d_grad_pi0, void *d_grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_grad_dest_batch_dev: null d_cotangent");
+    if (!d_grad_p_drive || !d_grad_dest) return fail(CPM_ERR_ARG, "expected_grad_dest_batch_dev: null d_grad_p_drive or d_grad_dest");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    return expected_grad_batch_enqueue(c, static_cast<const double *>(d_pi0), flags, tb.B, tb.pd, tb.q_stride, static_cast<const double *>(d_cotangent),
+                                       static_cast<const double *>(d_gnext), static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0),
+                                       static_cast<double *>(d_grad_dest));
+}
+
+int32_t cpm_expected_grad_dest_batch(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                                     double *grad_p_drive, double *grad_pi0, double *grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_grad_dest_batch: null cotangents");
+    if (!grad_p_drive || !grad_dest) return fail(CPM_ERR_ARG, "expected_grad_dest_batch: null grad_p_drive or grad_dest");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    if ((rc = exp_tables_ready(c, "expected")) != CPM_OK) return rc;  // (state is refused before a cotangent is read or copied)
+    if ((rc = tangent_ready(c, "expected_grad_dest_batch")) != CPM_OK) return rc;
+    return expected_grad_batch_blocking(c, "expected_grad_dest_batch", pi0, flags, tb.B, tb.pd, tb.q_stride, g_parking, g_driving, g_next, grad_p_drive, grad_pi0,
+                                        grad_dest);
 }
 
 int32_t cpm_expected_trip_tangent_dev(cpm_ctx *c, void *d_dw)

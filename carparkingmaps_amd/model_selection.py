@@ -355,6 +355,52 @@ class Evaluator:
             out["d_e_dest"] = e_dest_param_grad(g["grad_dest"], r["driving"] if direct else None, s.expected_trip_tangent()[0] if direct else None)
         return out
 
+    def expected_gradient_batch(self, pts, objective, ivp=True, dest=False):
+        """expected_gradient() for points that share e_dest, as the fleets of ONE batched forward propagation and ONE batched backward
+        pass (evaluate_expected_batch, Sampler.expected_grad_batch): a list of expected_gradient()'s dicts, point for point and bit for
+        bit.  The batch tables hold the points' p_drive when this returns; the context's own p_drive is the table s of the chain rule
+        only if this call had to build it."""
+        if objective not in ("activity_error", "parking_error", "A_drive"):
+            raise ValueError(f"expected_gradient_batch: unknown objective {objective!r}")
+        pts = list(pts)
+        if len({e_dest_key(pt.e_dest) for pt in pts}) != 1:
+            raise ValueError("expected_gradient_batch: the points of a batch share e_dest")
+        if objective == "activity_error" and self.measured_activity is None:
+            raise ValueError("expected_gradient_batch: activity_error needs measured_activity")
+        if objective == "parking_error" and self.measured_parking is None:
+            raise ValueError("expected_gradient_batch: parking_error needs measured_parking")
+        s = self.sampler
+        if self._s_table is None:
+            self._s_table = s.build_p_drive(0.0, 1.0, 1.0)
+        rs = self.evaluate_expected_batch(pts, ivp)
+        B = len(pts)
+        gp = np.zeros((s.Z, s.T, B), order="F")
+        gd = np.zeros((s.Z, s.T, B), order="F")
+        w_sec = s.expected_trip()[0] if objective == "A_drive" else None
+        for b, r in enumerate(rs):
+            if objective == "activity_error":
+                gd[:, :, b] = traffic_activity_error_grad(r["driving"], self.measured_activity)
+            elif objective == "parking_error":
+                gp[:, :, b] = parking_density_error_grad(r["parking"], self.measured_parking)
+            else:
+                gd[:, :, b] = a_drive_grad(w_sec)
+        if dest:
+            self._install_dest_tangent()
+        g = s.expected_grad_batch(gp, gd, ivp=ivp, dest=dest)
+        direct = dest and objective == "A_drive"
+        dw_sec = s.expected_trip_tangent()[0] if direct else None
+        outs = []
+        for b, (pt, r) in enumerate(zip(pts, rs)):
+            grad = np.asfortranarray(g["grad_p_drive"][:, :, b])
+            d_min, d_max, d_e = p_drive_param_grads(grad, self._s_table, pt.p_min, pt.p_max, pt.e_drive)
+            out = dict(objective=objective, value=r[objective], grad_p_drive=grad, grad_pi0=np.ascontiguousarray(g["grad_pi0"][:, b]),
+                       d_p_min=d_min, d_p_max=d_max, d_e_drive=d_e)
+            if dest:
+                out["grad_dest"] = np.asfortranarray(g["grad_dest"][:, :, b])
+                out["d_e_dest"] = e_dest_param_grad(out["grad_dest"], r["driving"] if direct else None, dw_sec)
+            outs.append(out)
+        return outs
+
     # -- device objectives: the record of include/cpm_objectives.h in the place of the count tensor --
     def _from_record(self, pt, rec):
         return objectives_from_record(rec, pt, self.C, self.sampler.T, self.measured_activity, self.measured_parking is not None)

@@ -702,6 +702,45 @@ class Sampler:
         _lib.check(self._L.cpm_expected_grad_dest_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr),
                                                       p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr), p(d_grad_dest_ptr)))
 
+    # -- the adjoint for the fleets of a batch (include/cpm_expected_grad_batch.h): B gradients in one pass over p_destin --
+    def expected_grad_batch(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None, dest=False):
+        """expected_grad() -- dest: expected_grad_dest() -- for every fleet of the installed batch tables, blocking.  g_parking /
+        g_driving: (Z, T, B) cotangents, fleet b's in [:, :, b]; g_next: (Z, B) or None (zeros for all fleets); pi0 is shared.  Returns
+        dict(grad_p_drive (Z, T, B) float64 F-order, grad_pi0 (Z, B)[, grad_dest (Z, T, B)]): fleet b's slices bit for bit what the
+        B = 1 call returns with p_drive[:, :, b] installed and fleet b's cotangents."""
+        a = self._pi0(pi0)
+        B = self.get_info(_lib.CPM_INFO_BATCH)
+        if B < 1:  # (the library names what is missing; it reads no array before it does)
+            B = np.asarray(g_parking).shape[-1] if np.asarray(g_parking).ndim == 3 else 1
+        gp = np.asfortranarray(_f64(g_parking, (self.Z, self.T, B)))
+        gd = np.asfortranarray(_f64(g_driving, (self.Z, self.T, B)))
+        gn = None if g_next is None else np.asfortranarray(_f64(g_next, (self.Z, B)))
+        grad = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
+        grad_pi0 = np.zeros((self.Z, B), dtype=np.float64, order="F")
+        flags = _lib.CPM_EXPECT_IVP if ivp else 0
+        if not dest:
+            _lib.check(self._L.cpm_expected_grad_batch(self._h, _vp(a), flags, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0)))
+            return dict(grad_p_drive=grad, grad_pi0=grad_pi0)
+        grad_dest = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
+        _lib.check(self._L.cpm_expected_grad_dest_batch(self._h, _vp(a), flags, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0), _vp(grad_dest)))
+        return dict(grad_p_drive=grad, grad_pi0=grad_pi0, grad_dest=grad_dest)
+
+    def expected_grad_batch_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0):
+        """Enqueue on the context's stream: d_cotangent_ptr = device address of float64[B][2][T][Z] (laid out like expected_batch_dev's
+        tensor); d_grad_p_drive_ptr = device address of float64[B][T][Z]; d_pi0_ptr = device address of float64[Z] or 0 (uniform);
+        d_gnext_ptr / d_grad_pi0_ptr = device address of float64[B][Z] or 0 (zeros / not wanted)."""
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        _lib.check(self._L.cpm_expected_grad_batch_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr),
+                                                       p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr)))
+
+    def expected_grad_dest_batch_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_grad_dest_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0,
+                                     d_grad_pi0_ptr=0):
+        """Enqueue on the context's stream: the arguments of expected_grad_batch_dev, and d_grad_dest_ptr = device address of
+        float64[B][T][Z]."""
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        _lib.check(self._L.cpm_expected_grad_dest_batch_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr),
+                                                            p(d_gnext_ptr), p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr), p(d_grad_dest_ptr)))
+
     def expected_trip_tangent(self):
         """(dw_sec, dw_km), each (Z, T) float64 F-order: the derivative of expected_trip()'s weights along the installed tangent, the
         residual of every row held fixed."""

@@ -59,7 +59,8 @@
  * where s * (Z + 8) * 2^-52 is cpm_expected.h's bound on pi_s.  An entry of grad_p_drive lies within the sum of the bounds of its
  * one or two dq terms (the + 4 of each covers the product and the addition of the two).  A word whose magnitude is 0 is 0.
  *
- * B = 1 only: the installed p_drive (cpm_set_p_drive / cpm_build_p_drive), not the batch tables.  The calls need no cars and change
+ * These calls read the installed p_drive (cpm_set_p_drive / cpm_build_p_drive); the fleets of the batch tables have
+ * cpm_expected_grad_batch.h, whose outputs carry these calls' bits fleet by fleet.  The calls need no cars and change
  * no state of the context that a later resample or cpm_expected* call reads.  They keep pi_s of all N operators in a workspace of
  * the context (N * Z words, Z rounded up to even).  The first call after the p_destin tables changed builds l, r and the residual
  * lists and synchronises the stream once, as cpm_expected_dev does.  Tables with sparse row packs are expanded to the dense array

@@ -45,7 +45,8 @@
  *
  * grad_p_drive and grad_pi0 of these calls carry the bits of cpm_expected_grad_dev on the same inputs.  No floating-point atomics;
  * the same inputs give the same bits every time; every word of the outputs is written and nothing else; no state that a later
- * cpm_expected* call or resample reads is changed.  The workspace of cpm_expected_grad grows by the segments' sums of w.  B = 1 only.
+ * cpm_expected* call or resample reads is changed.  The workspace of cpm_expected_grad grows by the segments' sums of w.  These calls read the
+ * installed p_drive; the fleets of the batch tables have cpm_expected_grad_batch.h.
  *
  * Error bound, relative to the magnitude recurrence of cpm_expected_grad.h with |dP| in place of dP: w~[o] = the sum over d of
  * |dP[t][d][o]| * mu~[d], W~_s[o] = x_s[o] * w~[o].  mu enters operator s after n - 1 = N - s - 1 backward operators: within
