@@ -55,6 +55,8 @@ OBJECTIVES_SYMBOLS = ["cpm_set_measured", "cpm_objectives_dev"]
 # every symbol include/cpm_expected.h declares (checked by tests/test_expected.py); a header and a list of its own, likewise
 EXPECTED_SYMBOLS = ["cpm_expected_dev", "cpm_expected_batch_dev", "cpm_expected", "cpm_expected_batch"]
 CPM_EXPECT_IVP = 1  # flags of the expected calls: start the day from pi0 carried through hours 0 .. T-2
+CPM_FIT_DEST = 0x100  # flag of the expected_fit calls: also dF/de_dest along the installed tangent
+CPM_FIT_WORDS = 16    # words of an expected_fit record in front of the traffic activity
 
 # every symbol include/cpm_expected_travel.h declares (checked by tests/test_expected_travel.py); a header and a list of its own, likewise
 EXPECTED_TRAVEL_SYMBOLS = ["cpm_expected_trip_dev", "cpm_expected_trip", "cpm_expected_travel_dev", "cpm_expected_travel",
@@ -70,6 +72,9 @@ EXPECTED_GRAD_DEST_SYMBOLS = ["cpm_set_p_dest_tangent", "cpm_build_p_dest_tangen
 # every symbol include/cpm_expected_grad_batch.h declares (checked by tests/test_expected_grad_batch.py); a header and a list of its own, likewise
 EXPECTED_GRAD_BATCH_SYMBOLS = ["cpm_expected_grad_batch_dev", "cpm_expected_grad_batch", "cpm_expected_grad_dest_batch_dev",
                                "cpm_expected_grad_dest_batch"]
+
+# every symbol include/cpm_expected_fit.h declares (checked by tests/test_expected_fit.py); a header and a list of its own, likewise
+EXPECTED_FIT_SYMBOLS = ["cpm_set_measured_activity", "cpm_expected_fit_dev", "cpm_expected_fit"]
 
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
@@ -123,6 +128,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad_dest.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad_batch.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_fit.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -233,8 +239,12 @@ def load():
     L.cpm_expected_grad_batch.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
     L.cpm_expected_grad_dest_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
     L.cpm_expected_grad_dest_batch.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.cpm_set_measured_activity.argtypes = [vp, vp]
+    L.cpm_expected_fit_dev.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.cpm_expected_fit.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
-                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS + EXPECTED_GRAD_BATCH_SYMBOLS):
+                 + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS + EXPECTED_GRAD_BATCH_SYMBOLS
+                 + EXPECTED_FIT_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

@@ -25,6 +25,7 @@
 #include "../../include/cpm_expected_grad.h"
 #include "../../include/cpm_expected_grad_dest.h"
 #include "../../include/cpm_expected_grad_batch.h"
+#include "../../include/cpm_expected_fit.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -45,6 +46,7 @@
 #include "cpm_expected_grad.h"
 #include "cpm_expected_grad_dest.h"
 #include "cpm_expected_grad_batch.h"
+#include "cpm_expected_fit.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -278,6 +280,15 @@ struct cpm_ctx {
     DevBuf<double> d_tan_m;             // [T][Z] the rows' sums of p * log(x) of the dense builder
     DevBuf<double> d_tan_w;             // [2][T][Z] the blocking trip-tangent call's dw_sec | dw_km
     DevBuf<double> d_exp_gdio;          // [T][Z] the blocking call's grad_dest
+    int64_t tan_gen = 0;                // tangent tables installed so far: what a cached trip-weight tangent is checked against
+    // value and gradient of the noise-free objectives (include/cpm_expected_fit.h, cpm_expected_fit.h)
+    DevBuf<double> d_act_meas;          // [T] measured traffic activity
+    bool have_act_meas = false;
+    DevBuf<double> d_fit_ws;            // the call's workspace: densities, cotangents, gradients and the O(B * (T + Z)) words (expected_fit_enqueue)
+    DevBuf<int> d_fit_int;              // [B][Z] the zones' argmin | argmax, [B][ceil(Z/256)] the workgroups' counts of valid zones
+    DevBuf<double> d_fit_dw;            // [2][T][Z] the trip weights' tangent, kept while the tangent table and the trip weights stay
+    int64_t fit_dw_gen = -1, fit_dw_builds = -1;
+    DevBuf<double> d_fit_rec;           // [B][CPM_FIT_WORDS + T] the blocking call's records
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -1677,12 +1688,19 @@ void launch_grad_u_b(cpm_ctx *c, const double *p_t, const double *dp_t, const do
 // d_exp_gws, in vectors of Zs words: pi [2T - 1][B], x ping and pong [B] each, mu ping and pong [B8] each (B8 = B rounded up to
 // whole passes; a pass's mu is [Zs][NB] at its first fleet's place), the segments' sums of one pass [nseg][kExpMaxNB], those of w
 // likewise.
-int32_t expected_grad_batch_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride, const double *cot,
-                                    const double *gnext, double *grad_pd, double *grad_pi0, double *grad_dest)
+// where the batched adjoint keeps what its two halves share: the workspace's vectors and the geometry of the segments
+struct GradBatchPlan {
+    int Zs = 0, nseg = 0, seg_len = 0;
+    size_t nb = 0;
+    double *ws_pi = nullptr, *ws_x[2] = {nullptr, nullptr}, *ws_mu[2] = {nullptr, nullptr}, *part = nullptr, *part_dp = nullptr;
+};
+
+// the checks that can refuse and the workspace of B fleets (with_dest: the call runs along the tangent)
+int32_t grad_batch_plan(cpm_ctx *c, int B, bool with_dest, GradBatchPlan &pl)
 {
     int32_t rc = exp_tables_ready(c, "expected");
     if (rc != CPM_OK) return rc;
-    if (grad_dest && (rc = tangent_ready(c, "expected_grad_dest_batch")) != CPM_OK) return rc;
+    if (with_dest && (rc = tangent_ready(c, "expected_grad_dest_batch")) != CPM_OK) return rc;
     if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
@@ -1692,11 +1710,22 @@ int32_t expected_grad_batch_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t fl
     const size_t part_words = static_cast<size_t>(nseg) * cpm::kExpMaxNB * Zs;
     HIP_TRY(c->d_exp_gws.reserve((most * nb + 2 * nb + 2 * b8) * Zs + 2 * part_words));
     double *ws_pi = c->d_exp_gws;
-    double *ws_x[2] = {ws_pi + most * nb * Zs, ws_pi + (most + 1) * nb * Zs};
-    double *ws_mu[2] = {ws_pi + (most + 2) * nb * Zs, ws_pi + ((most + 2) * nb + b8) * Zs};
-    double *part = ws_pi + ((most + 2) * nb + 2 * b8) * Zs;
-    double *part_dp = part + part_words;
-    const size_t zt = static_cast<size_t>(Z) * T, cot_stride = 2 * zt;
+    pl.Zs = Zs, pl.nseg = nseg, pl.seg_len = seg_len, pl.nb = nb;
+    pl.ws_pi = ws_pi;
+    pl.ws_x[0] = ws_pi + most * nb * Zs, pl.ws_x[1] = ws_pi + (most + 1) * nb * Zs;
+    pl.ws_mu[0] = ws_pi + (most + 2) * nb * Zs, pl.ws_mu[1] = ws_pi + ((most + 2) * nb + b8) * Zs;
+    pl.part = ws_pi + ((most + 2) * nb + 2 * b8) * Zs;
+    pl.part_dp = pl.part + part_words;
+    return CPM_OK;
+}
+
+// the forward half: expected_enqueue's kernels with pi_s of every operator and fleet kept (operator N - 1 is not applied)
+int32_t grad_batch_forward(cpm_ctx *c, const GradBatchPlan &pl, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride)
+{
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T), Zs = pl.Zs;
+    const size_t nb = pl.nb;
+    double *const ws_pi = pl.ws_pi;
+    double *const ws_x[2] = {pl.ws_x[0], pl.ws_x[1]};
     const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
     auto hour_of = [pre](int s) { return s < pre ? s : s - pre; };
 
@@ -1717,6 +1746,21 @@ int32_t expected_grad_batch_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t fl
         }
         HIP_TRY(hipGetLastError());
     }
+    return CPM_OK;
+}
+
+// the backward half: operator-major with the passes of at most kExpMaxNB fleets inside an operator
+int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags, int B, const double *pd, size_t q_stride, const double *cot,
+                            const double *gnext, double *grad_pd, double *grad_pi0, double *grad_dest)
+{
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T), Zs = pl.Zs, nseg = pl.nseg, seg_len = pl.seg_len;
+    const size_t nb = pl.nb;
+    double *const ws_pi = pl.ws_pi;
+    double *const ws_mu[2] = {pl.ws_mu[0], pl.ws_mu[1]};
+    double *const part = pl.part, *const part_dp = pl.part_dp;
+    const size_t zt = static_cast<size_t>(Z) * T, cot_stride = 2 * zt;
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
+    auto hour_of = [pre](int s) { return s < pre ? s : s - pre; };
 
     bool have_mu = gnext != nullptr;  // (false: zero by construction, the products of the last operator are skipped for every fleet)
     for (int s = steps - 1; s >= 0; --s) {
@@ -1776,6 +1820,16 @@ int32_t expected_grad_batch_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t fl
         have_mu = true;
     }
     return CPM_OK;
+}
+
+int32_t expected_grad_batch_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride, const double *cot,
+                                    const double *gnext, double *grad_pd, double *grad_pi0, double *grad_dest)
+{
+    GradBatchPlan pl;
+    int32_t rc = grad_batch_plan(c, B, grad_dest != nullptr, pl);
+    if (rc != CPM_OK) return rc;
+    if ((rc = grad_batch_forward(c, pl, d_pi0, flags, B, pd, q_stride)) != CPM_OK) return rc;
+    return grad_batch_backward(c, pl, flags, B, pd, q_stride, cot, gnext, grad_pd, grad_pi0, grad_dest);
 }
 
 // the blocking forms: d_exp_gio holds [B][2][T][Z] cotangents, [B][Z] G_next, [B][T][Z] grad_p_drive, [B][Z] grad_pi0 and pi_0 [Z];
@@ -1847,6 +1901,7 @@ int32_t build_dest_tangent(cpm_ctx *c)
         HIP_TRY(hipGetLastError());
     }
     c->tan_valid = true;
+    ++c->tan_gen;
     return CPM_OK;
 }
 
@@ -1870,6 +1925,158 @@ int32_t trip_tangent_enqueue(cpm_ctx *c, double *d_dw)
     HIP_TRY(hipGetLastError());
     cpm::launch(cpm::k_exp_trip_tan_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream,
                 static_cast<const double *>(c->d_exp_wpart.get()), nseg, static_cast<const double *>(c->d_last), Z, T, d_dw);
+    HIP_TRY(hipGetLastError());
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ value and gradient of the objectives (include/cpm_expected_fit.h)
+constexpr int kFitMaxT = 2048;  // (the hours' sums of a workgroup live in LDS; an argmin and an argmax share a word)
+
+// what every entry checks before anything is enqueued, behind exp_enter; B and the parameter arrays included
+int32_t fit_check(cpm_ctx *c, const char *what, int32_t B, const double *p_min, const double *p_max, const double *e_drive, uint32_t flags, const double *weights,
+                  const void *record)
+{
+    if (B < 1 || B > CPM_MAX_BATCH) return fail(CPM_ERR_ARG, "%s: B = %d outside 1..%d", what, B, CPM_MAX_BATCH);
+    if (!p_min || !p_max || !e_drive) return fail(CPM_ERR_ARG, "%s: null parameter array", what);
+    if (!weights) return fail(CPM_ERR_ARG, "%s: null weights", what);
+    if (!record) return fail(CPM_ERR_ARG, "%s: null record", what);
+    if (flags & ~(CPM_EXPECT_IVP | CPM_FIT_DEST)) return fail(CPM_ERR_ARG, "%s: unknown flag bits 0x%x", what, flags);
+    for (int i = 0; i < 3 * B; ++i)
+        if (!std::isfinite(weights[i])) return fail(CPM_ERR_ARG, "%s: weight %d of fleet %d is not finite", what, i % 3 + 1, i / 3 + 1);
+    CTX_TRY(c);
+    if (c->T > kFitMaxT) return fail(CPM_ERR_ARG, "%s: T = %lld above %d", what, (long long)c->T, kFitMaxT);
+    if (!c->have_dmat) return fail(CPM_ERR_STATE, "%s: datamatrix not set (cpm_set_datamatrix, cpm_createdatamatrix_* or cpm_synth_datamatrix)", what);
+    if (!c->have_dist) return fail(CPM_ERR_STATE, "%s: distance matrix not set (cpm_set_distance* or the dist of cpm_set_datamatrix)", what);
+    int32_t rc = exp_tables_ready(c, what);
+    if (rc != CPM_OK) return rc;
+    if ((flags & CPM_FIT_DEST) && (rc = tangent_ready(c, what)) != CPM_OK) return rc;
+    for (int b = 0; b < B; ++b) {
+        if (weights[3 * b] != 0.0 && !c->have_act_meas)
+            return fail(CPM_ERR_STATE, "%s: fleet %d weighs activity_error, but no measured activity is installed (cpm_set_measured_activity)", what, b + 1);
+        if (weights[3 * b + 1] != 0.0 && !c->have_measured)
+            return fail(CPM_ERR_STATE, "%s: fleet %d weighs parking_error, but no measured parking densities are installed (cpm_set_measured)", what, b + 1);
+    }
+    return CPM_OK;
+}
+
+// where the call's arrays lie in d_fit_ws
+struct FitLayout {
+    size_t expected, cot, grad_pd, grad_dest, params, totals, ga, nval, hpart, epart, zone, range, cpart, words;
+    int nbz, nchunk;
+};
+FitLayout fit_layout(const cpm_ctx *c, int B)
+{
+    const size_t nb = static_cast<size_t>(B), Z = static_cast<size_t>(c->Z), T = static_cast<size_t>(c->T), zt = Z * T;
+    FitLayout l;
+    l.nbz = static_cast<int>(nblk(c->Z, cpm::kExpBlock));
+    l.nchunk = static_cast<int>(nblk(static_cast<int64_t>(zt), cpm::kTravelChunk));
+    size_t at = 0;
+    auto take = [&at](size_t n) { const size_t here = at; at += (n + 1) & ~static_cast<size_t>(1); return here; };
+    l.expected = take(nb * 2 * zt);
+    l.cot = take(nb * 2 * zt);
+    l.grad_pd = take(nb * zt);
+    l.grad_dest = take(nb * zt);
+    l.zone = take(5 * nb * Z);
+    l.range = take(2 * Z);
+    l.hpart = take(nb * T * l.nbz);
+    l.epart = take(nb * l.nbz);
+    l.cpart = take(nb * l.nchunk * cpm::kFitChainTerms);
+    l.ga = take(nb * T);
+    l.params = take(6 * nb);
+    l.totals = take(2 * nb);
+    l.nval = take(nb);
+    l.words = at;
+    return l;
+}
+
+// The whole call, enqueued on the context's stream; fit_check has passed.  Outputs that are nullptr stay in the workspace.
+int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const double *p_max, const double *e_drive, const double *d_pi0, uint32_t flags,
+                             const double *weights, double *d_record, double *d_expected, double *d_cot, double *d_grad_pd, double *d_grad_dest)
+{
+    const bool dest = (flags & CPM_FIT_DEST) != 0;
+    const uint32_t eflags = flags & CPM_EXPECT_IVP;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t zt = static_cast<size_t>(Z) * T;
+    GradBatchPlan pl;
+    int32_t rc = grad_batch_plan(c, B, dest, pl);
+    if (rc != CPM_OK) return rc;
+    if ((rc = ensure_exp_trip(c)) != CPM_OK) return rc;
+    bool direct = false;
+    for (int b = 0; b < B; ++b) direct = direct || (dest && weights[3 * b + 2] != 0.0);
+    if (direct && (c->fit_dw_gen != c->tan_gen || c->fit_dw_builds != c->exp_trip_builds)) {
+        c->fit_dw_gen = -1;
+        HIP_TRY(c->d_fit_dw.reserve(2 * zt));
+        if ((rc = trip_tangent_enqueue(c, c->d_fit_dw)) != CPM_OK) return rc;
+        c->fit_dw_gen = c->tan_gen;
+        c->fit_dw_builds = c->exp_trip_builds;
+    }
+    if ((rc = ensure_batch_tables(c, B)) != CPM_OK) return rc;
+    if ((rc = ensure_pdrive_mean(c)) != CPM_OK) return rc;
+    const FitLayout l = fit_layout(c, B);
+    HIP_TRY(c->d_fit_ws.reserve(l.words));  // (a grow frees first: hipFree waits for what still reads the old workspace)
+    HIP_TRY(c->d_fit_int.reserve(static_cast<size_t>(B) * (Z + l.nbz)));
+    double *ws = c->d_fit_ws;
+    double *expected = d_expected ? d_expected : ws + l.expected, *cot = d_cot ? d_cot : ws + l.cot;
+    double *grad_pd = d_grad_pd ? d_grad_pd : ws + l.grad_pd;
+    double *grad_dest = !dest ? nullptr : d_grad_dest ? d_grad_dest : ws + l.grad_dest;
+    double *w_dev = ws + l.params, *par_dev = w_dev + 3 * B;
+    int *arg = c->d_fit_int, *npart = arg + static_cast<size_t>(B) * Z;
+    const size_t rec_stride = static_cast<size_t>(cpm::kFitWords + T);
+
+    // (a) the B tables, as cpm_build_p_drive_batch installs them
+    for (int b = 0; b < B; ++b)
+        hipLaunchKernelGGL(cpm::k_pdrive_final, dim3(nblk(c->Z, 64), static_cast<unsigned>(c->T)), dim3(64), 0, c->stream, c->d_pdrive_mean,
+                           c->d_pdrive_b + b * zt, c->d_thr_b + b * zt, Z, T, p_min[b], p_max[b], e_drive[b]);
+    HIP_TRY(hipGetLastError());
+    c->batch_B = B;
+    cpm::FitParams fp;
+    for (int b = 0; b < B; ++b) {
+        fp.w[3 * b] = weights[3 * b], fp.w[3 * b + 1] = weights[3 * b + 1], fp.w[3 * b + 2] = weights[3 * b + 2];
+        fp.w[3 * (B + b)] = p_min[b], fp.w[3 * (B + b) + 1] = p_max[b], fp.w[3 * (B + b) + 2] = e_drive[b];
+    }
+    hipLaunchKernelGGL(cpm::k_fit_params, dim3(1), dim3(64), 0, c->stream, fp, 6 * B, w_dev);
+    HIP_TRY(hipGetLastError());
+
+    // (b) forward, pi_s kept; the densities of the day from them
+    const double *pd = c->d_pdrive_b;
+    if ((rc = grad_batch_forward(c, pl, d_pi0, eflags, B, pd, zt)) != CPM_OK) return rc;
+    const int pre = (eflags & CPM_EXPECT_IVP) ? T - 1 : 0;
+    const unsigned nbz = static_cast<unsigned>(l.nbz);
+    hipLaunchKernelGGL(cpm::k_fit_dens, dim3(nbz, static_cast<unsigned>(T), static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream,
+                       static_cast<const double *>(pl.ws_pi + static_cast<size_t>(pre) * pl.nb * pl.Zs), pd, zt, Z, pl.Zs, T, B, expected);
+    HIP_TRY(hipGetLastError());
+
+    // (c) objectives and cotangents
+    if ((rc = expected_travel_enqueue(c, expected, B, nullptr, ws + l.totals)) != CPM_OK) return rc;
+    const double *meas = c->have_measured ? c->d_measured.get() : nullptr;
+    const int *flag = c->have_measured ? c->d_meas_flag.get() : nullptr;
+    hipLaunchKernelGGL(cpm::k_fit_zones, dim3(nbz, static_cast<unsigned>(B)), dim3(cpm::kExpBlock), sizeof(double) * cpm::kExpWaves * T, c->stream,
+                       static_cast<const double *>(expected), meas, flag, Z, T, B, ws + l.hpart, ws + l.zone, arg, ws + l.epart, npart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cpm::k_fit_final, dim3(static_cast<unsigned>(B)), dim3(64), sizeof(double) * T, c->stream, static_cast<const double *>(ws + l.hpart),
+                       static_cast<const double *>(ws + l.epart), static_cast<const int *>(npart), l.nbz, T, static_cast<const double *>(ws + l.totals),
+                       c->have_act_meas ? static_cast<const double *>(c->d_act_meas.get()) : nullptr, static_cast<const double *>(w_dev), d_record, rec_stride,
+                       ws + l.ga, ws + l.nval);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cpm::k_fit_cot, dim3(nbz, static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(expected), meas,
+                       static_cast<const double *>(ws + l.zone), static_cast<const int *>(arg), static_cast<const double *>(ws + l.ga),
+                       static_cast<const double *>(ws + l.nval), static_cast<const double *>(c->d_exp_w.get()), static_cast<const double *>(w_dev), Z, T, B, cot);
+    HIP_TRY(hipGetLastError());
+
+    // (d) backward on that cotangent: G_next zero, grad_pi0 not wanted
+    if ((rc = grad_batch_backward(c, pl, eflags, B, pd, zt, cot, nullptr, grad_pd, nullptr, grad_dest)) != CPM_OK) return rc;
+
+    // (e) the chain rule
+    hipLaunchKernelGGL(cpm::k_fit_mean_range, dim3(nbz), dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(c->d_pdrive_mean.get()), Z, T,
+                       ws + l.range);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cpm::k_fit_chain, dim3(static_cast<unsigned>(l.nchunk), static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream,
+                       static_cast<const double *>(grad_pd), static_cast<const double *>(grad_dest), static_cast<const double *>(expected),
+                       direct ? static_cast<const double *>(c->d_fit_dw.get()) : nullptr, static_cast<const double *>(c->d_pdrive_mean.get()),
+                       static_cast<const double *>(ws + l.range), static_cast<const double *>(par_dev), static_cast<const double *>(w_dev), Z, zt, ws + l.cpart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cpm::k_fit_chain_total, dim3(static_cast<unsigned>(B)), dim3(64), 0, c->stream, static_cast<const double *>(ws + l.cpart), l.nchunk,
+                       static_cast<const double *>(w_dev), dest ? 1 : 0, T, d_record, rec_stride);
     HIP_TRY(hipGetLastError());
     return CPM_OK;
 }
@@ -3339,6 +3546,7 @@ int32_t cpm_set_p_dest_tangent(cpm_ctx *c, const double *dp)
     HIP_TRY(hipMemcpyAsync(c->d_tan, dp, sizeof(double) * cells, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->tan_valid = true;
+    ++c->tan_gen;
     return CPM_OK;
 }
 
@@ -3472,6 +3680,64 @@ int32_t cpm_expected_trip_tangent(cpm_ctx *c, double *dw_sec, double *dw_km)
     if ((rc = trip_tangent_enqueue(c, c->d_tan_w)) != CPM_OK) return rc;
     HIP_TRY(hipMemcpyAsync(dw_sec, c->d_tan_w, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(dw_km, c->d_tan_w + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ value and gradient of the objectives (include/cpm_expected_fit.h)
+
+int32_t cpm_set_measured_activity(cpm_ctx *c, const double *activity)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (!activity) {  // (host state only: what is in flight on the stream was enqueued with the data it had)
+        c->have_act_meas = false;
+        return CPM_OK;
+    }
+    for (int64_t t = 0; t < c->T; ++t)
+        if (!std::isfinite(activity[t])) return fail(CPM_ERR_ARG, "set_measured_activity: hour %lld is not finite", (long long)t + 1);
+    HIP_TRY(c->d_act_meas.reserve(static_cast<size_t>(c->T)));
+    HIP_TRY(hipMemcpyAsync(c->d_act_meas, activity, sizeof(double) * c->T, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->have_act_meas = true;
+    return CPM_OK;
+}
+
+int32_t cpm_expected_fit_dev(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive, const void *d_pi0, uint32_t flags,
+                             const double *weights, void *d_record, void *d_expected, void *d_cotangent, void *d_grad_p_drive, void *d_grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = fit_check(c, "expected_fit_dev", B, p_min, p_max, e_drive, flags, weights, d_record)) != CPM_OK) return rc;
+    if (d_grad_dest && !(flags & CPM_FIT_DEST)) return fail(CPM_ERR_ARG, "expected_fit_dev: d_grad_dest without CPM_FIT_DEST");
+    return expected_fit_enqueue(c, B, p_min, p_max, e_drive, static_cast<const double *>(d_pi0), flags, weights, static_cast<double *>(d_record),
+                                static_cast<double *>(d_expected), static_cast<double *>(d_cotangent), static_cast<double *>(d_grad_p_drive),
+                                static_cast<double *>(d_grad_dest));
+}
+
+int32_t cpm_expected_fit(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive, const double *pi0, uint32_t flags,
+                         const double *weights, double *record, double *expected, double *cotangent, double *grad_p_drive, double *grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = fit_check(c, "expected_fit", B, p_min, p_max, e_drive, flags, weights, record)) != CPM_OK) return rc;
+    if (grad_dest && !(flags & CPM_FIT_DEST)) return fail(CPM_ERR_ARG, "expected_fit: grad_dest without CPM_FIT_DEST");
+    if ((rc = check_pi0(c, pi0)) != CPM_OK) return rc;
+    const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nb = static_cast<size_t>(B);
+    const size_t rec_words = nb * static_cast<size_t>(cpm::kFitWords + c->T);
+    HIP_TRY(c->d_fit_rec.reserve(rec_words + Z));
+    double *d_pi0 = c->d_fit_rec + (c->d_fit_rec.cap - Z);  // (pi_0 ends the allocation)
+    if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    rc = expected_fit_enqueue(c, B, p_min, p_max, e_drive, pi0 ? d_pi0 : nullptr, flags, weights, c->d_fit_rec, nullptr, nullptr, nullptr, nullptr);
+    if (rc != CPM_OK) return rc;
+    const FitLayout l = fit_layout(c, B);
+    const double *ws = c->d_fit_ws;
+    HIP_TRY(hipMemcpyAsync(record, c->d_fit_rec, sizeof(double) * rec_words, hipMemcpyDeviceToHost, c->stream));
+    if (expected) HIP_TRY(hipMemcpyAsync(expected, ws + l.expected, sizeof(double) * nb * 2 * zt, hipMemcpyDeviceToHost, c->stream));
+    if (cotangent) HIP_TRY(hipMemcpyAsync(cotangent, ws + l.cot, sizeof(double) * nb * 2 * zt, hipMemcpyDeviceToHost, c->stream));
+    if (grad_p_drive) HIP_TRY(hipMemcpyAsync(grad_p_drive, ws + l.grad_pd, sizeof(double) * nb * zt, hipMemcpyDeviceToHost, c->stream));
+    if (grad_dest && (flags & CPM_FIT_DEST)) HIP_TRY(hipMemcpyAsync(grad_dest, ws + l.grad_dest, sizeof(double) * nb * zt, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
 }

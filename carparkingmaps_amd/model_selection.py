@@ -228,6 +228,7 @@ class Evaluator:
     _pipe: object = field(default=None, repr=False)
     _s_table: object = field(default=None, repr=False)   # build_p_drive(0, 1, 1): the datamatrix's own table, for expected_gradient
     _tangent: object = field(default=None, repr=False)   # the e_dest key whose d p_destin / d e_dest is installed (expected_gradient, dest=True)
+    _fit_measured: object = field(default=None, repr=False)   # expected_fit has installed the measured arrays in the context
 
     def __post_init__(self):
         if self.measured_parking is not None:   # Julia order, like the count tensors: the error is evaluated hour-major on contiguous rows
@@ -401,6 +402,45 @@ class Evaluator:
             outs.append(out)
         return outs
 
+    def expected_fit(self, pts, weights=None, ivp=True, dest=False):
+        """Value and gradient of F = sum of weight * objective at points that share e_dest, in ONE device call with one forward
+        propagation (Sampler.expected_fit_dev, include/cpm_expected_fit.h): the host reads B * (16 + T) words and reduces nothing.
+        weights: a dict over "activity_error", "parking_error", "A_drive" (missing keys: 0), or a list of such dicts, one per point;
+        None: 1 for activity_error alone.  A weighed objective needs its measured data.  Returns per point a dict with the scalar
+        keys of expected_gradient() -- objective (the one weighed objective's name, else "F"), value (= F), d_p_min, d_p_max, d_e_drive,
+    and d_e_dest when dest -- plus F, activity_error,
+        parking_error, A_drive, n_valid, total_seconds, total_km and traffic_activity (T,).  The batch tables hold the points'
+        p_drive when this returns."""
+        pts, w = _fit_inputs("expected_fit", self, pts, weights)
+        import torch
+        s = self.sampler
+        self._install_dest(pts[0].e_dest)
+        if dest:
+            self._install_dest_tangent()
+        if self._fit_measured is None:   # once: resident in the context
+            s.set_measured_activity(self.measured_activity)
+            s.set_measured(self.measured_parking)
+            self._fit_measured = True
+        B, words = len(pts), s.fit_words()
+        rec = torch.empty(B * words, dtype=torch.float64, device=f"cuda:{s.device}")
+        torch.cuda.synchronize(s.device)
+        s.expected_fit_dev([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts], w, rec.data_ptr(), 0, ivp, dest)
+        s.sync()
+        r = s.fit_record(rec.cpu().numpy(), s.T)
+        outs = []
+        for b, pt in enumerate(pts):
+            weighed = [k for k, v in zip(FIT_WEIGHT_KEYS, w[b]) if v != 0]
+            out = {"e_drive": pt.e_drive, "p_min": pt.p_min, "p_max": pt.p_max, "e_dest": float(pt.e_dest),
+                   "objective": weighed[0] if len(weighed) == 1 else "F", "value": float(r["F"][b])}
+            for k in ("F", "activity_error", "parking_error", "A_drive", "d_p_min", "d_p_max", "d_e_drive", "total_seconds", "total_km"):
+                out[k] = float(r[k][b])
+            out["n_valid"] = int(r["n_valid"][b])
+            if dest:
+                out["d_e_dest"] = float(r["d_e_dest"][b])
+            out["traffic_activity"] = r["traffic_activity"][b]
+            outs.append(out)
+        return outs
+
     # -- device objectives: the record of include/cpm_objectives.h in the place of the count tensor --
     def _from_record(self, pt, rec):
         return objectives_from_record(rec, pt, self.C, self.sampler.T, self.measured_activity, self.measured_parking is not None)
@@ -561,6 +601,113 @@ class Evaluator:
                 out = self._objectives(pt, parking, driving, int(flat[b, 2 * zt]))
             outs.append(out)
         return outs
+
+
+FIT_WEIGHT_KEYS = ("activity_error", "parking_error", "A_drive")
+
+
+def _fit_inputs(what, evaluator, pts, weights):
+    """(points, (B, 3) weights) of Evaluator.expected_fit / refine_expected, checked before the sampler is touched: the points share
+    e_dest, every weight key is known and finite, and a weighed objective has its measured data."""
+    pts = list(pts)
+    if not pts:
+        raise ValueError(f"{what}: no points")
+    if len({e_dest_key(pt.e_dest) for pt in pts}) != 1:
+        raise ValueError(f"{what}: the points of a batch share e_dest")
+    if weights is None:
+        weights = {"activity_error": 1.0}
+    per_point = [weights] * len(pts) if isinstance(weights, dict) else list(weights)
+    if len(per_point) != len(pts):
+        raise ValueError(f"{what}: {len(per_point)} weight dicts for {len(pts)} points")
+    w = np.zeros((len(pts), 3))
+    for b, d in enumerate(per_point):
+        unknown = set(d) - set(FIT_WEIGHT_KEYS)
+        if unknown:
+            raise ValueError(f"{what}: unknown weight keys {sorted(unknown)}")
+        for k, key in enumerate(FIT_WEIGHT_KEYS):
+            w[b, k] = float(d.get(key, 0.0))
+    if not np.isfinite(w).all():
+        raise ValueError(f"{what}: a weight is not finite")
+    if (w[:, 0] != 0).any() and evaluator.measured_activity is None:
+        raise ValueError(f"{what}: a weight on activity_error needs measured_activity")
+    if (w[:, 1] != 0).any() and evaluator.measured_parking is None:
+        raise ValueError(f"{what}: a weight on parking_error needs measured_parking")
+    return pts, w
+
+
+DEFAULT_FIT_BOUNDS = {"e_drive": (1e-3, 16.0), "p_min": (0.0, 1.0), "p_max": (0.0, 1.0)}
+
+
+def _project(x, lo, hi, gap):
+    """(e_drive, p_min, p_max) onto the box, then onto p_min + gap <= p_max (the nearest point of that half-plane, kept in the box)."""
+    x = np.minimum(np.maximum(x, lo), hi)
+    if x[1] + gap > x[2]:
+        mid = 0.5 * (x[1] + x[2])
+        x[1], x[2] = mid - 0.5 * gap, mid + 0.5 * gap
+        if x[1] < lo[1]:
+            x[1], x[2] = lo[1], max(x[2], lo[1] + gap)
+        if x[2] > hi[2]:
+            x[1], x[2] = min(x[1], hi[2] - gap), hi[2]
+    return x
+
+
+def refine_expected(evaluator, pts, weights=None, steps=10, bounds=None, ivp=True, step0=1.0, shrink=0.5, armijo=1e-4, max_backtracks=12,
+                    min_gap=1e-3):
+    """Projected gradient descent with Armijo backtracking on (e_drive, p_min, p_max) for the noise-free F of Evaluator.expected_fit:
+    B starting points that share e_dest, ALL advanced by one expected_fit call per trial step (a point whose trial is refused halves
+    its own step and waits for the next call; an accepted point doubles it).  bounds: dict over "e_drive", "p_min", "p_max" of
+    (low, high); default e_drive in [1e-3, 16], 0 <= p_min < p_max <= 1 (min_gap apart).  A trial x+ = P(x - a * g) is accepted when
+    F(x+) <= F(x) - armijo * <g, x - x+>.  Returns per point dict(path: [(Point, F), ...] of the accepted points, the start first;
+    gradient: (d_e_drive, d_p_min, d_p_max) at the last one; result: expected_fit's dict there; calls: expected_fit calls made).
+    Plain host Python over the device call: nothing here is a kernel."""
+    b = dict(DEFAULT_FIT_BOUNDS)
+    for k, v in (bounds or {}).items():
+        if k not in b:
+            raise ValueError(f"refine_expected: unknown bound {k!r}")
+        b[k] = (float(v[0]), float(v[1]))
+    lo = np.array([b["e_drive"][0], b["p_min"][0], b["p_max"][0]])
+    hi = np.array([b["e_drive"][1], b["p_min"][1], b["p_max"][1]])
+    if not (lo <= hi).all():
+        raise ValueError("refine_expected: bounds that cross")
+    if not lo[0] > 0:
+        raise ValueError("refine_expected: e_drive must stay above 0")
+    if lo[1] + min_gap > hi[2]:
+        raise ValueError("refine_expected: bounds that cross: no room for p_min < p_max")
+    pts, _ = _fit_inputs("refine_expected", evaluator, pts, weights)
+    e_dest = pts[0].e_dest
+    B = len(pts)
+    vec = lambda r: np.array([r["d_e_drive"], r["d_p_min"], r["d_p_max"]])
+    point = lambda x: Point(e_drive=float(x[0]), p_min=float(x[1]), p_max=float(x[2]), e_dest=e_dest)
+    x = [_project(np.array([pt.e_drive, pt.p_min, pt.p_max], dtype=np.float64), lo, hi, min_gap) for pt in pts]
+    cur = evaluator.expected_fit([point(v) for v in x], weights, ivp=ivp)
+    calls = 1
+    paths = [[(point(x[k]), cur[k]["F"])] for k in range(B)]
+    alpha = [float(step0)] * B
+    accepted, refused = [0] * B, [0] * B
+    for _ in range(int(steps) * (int(max_backtracks) + 1)):
+        live = [k for k in range(B) if accepted[k] < steps and alpha[k] > 0 and np.isfinite(cur[k]["F"])]
+        if not live:
+            break
+        trial = list(x)
+        for k in live:
+            trial[k] = _project(x[k] - alpha[k] * vec(cur[k]), lo, hi, min_gap)
+        new = evaluator.expected_fit([point(v) for v in trial], weights, ivp=ivp)
+        calls += 1
+        for k in live:
+            moved = x[k] - trial[k]
+            if not moved.any():                      # the projection holds the point where it is: nothing left to gain
+                alpha[k] = 0.0
+                continue
+            if np.isfinite(new[k]["F"]) and new[k]["F"] <= cur[k]["F"] - armijo * float(vec(cur[k]) @ moved):
+                x[k], cur[k] = trial[k], new[k]
+                paths[k].append((point(x[k]), cur[k]["F"]))
+                accepted[k] += 1
+                refused[k] = 0
+                alpha[k] *= 2.0
+            else:
+                refused[k] += 1
+                alpha[k] = alpha[k] * shrink if refused[k] <= max_backtracks else 0.0
+    return [dict(path=paths[k], gradient=tuple(vec(cur[k])), result=cur[k], calls=calls) for k in range(B)]
 
 
 def e_dest_key(e_dest):

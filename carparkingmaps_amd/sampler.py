@@ -753,6 +753,79 @@ class Sampler:
         """Enqueue on the context's stream: d_dw_ptr = device address of float64[2][T][Z], dw_sec then dw_km."""
         _lib.check(self._L.cpm_expected_trip_tangent_dev(self._h, C.c_void_p(int(d_dw_ptr)) if d_dw_ptr else None))
 
+    # -- value and four-parameter gradient of the noise-free objectives (include/cpm_expected_fit.h): one call, one forward pass --
+    def set_measured_activity(self, activity):
+        """The measured traffic activity, (T,), resident until replaced; None: forget it.  NaN or infinite entries raise."""
+        if activity is None:
+            _lib.check(self._L.cpm_set_measured_activity(self._h, None))
+            return
+        a = np.ascontiguousarray(_f64(activity, (self.T,)))
+        _lib.check(self._L.cpm_set_measured_activity(self._h, _vp(a)))
+
+    def fit_words(self):
+        """float64 words of one fleet's expected_fit record: CPM_FIT_WORDS + T."""
+        return _lib.CPM_FIT_WORDS + self.T
+
+    def _fit_args(self, p_min, p_max, e_drive, weights):
+        lo = np.ascontiguousarray(np.atleast_1d(np.asarray(p_min, dtype=np.float64)))
+        B = lo.shape[0]
+        hi = np.ascontiguousarray(_f64(np.atleast_1d(p_max), (B,)))
+        ex = np.ascontiguousarray(_f64(np.atleast_1d(e_drive), (B,)))
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim == 1:
+            w = np.broadcast_to(w, (B, 3))
+        w = np.ascontiguousarray(_f64(w, (B, 3)))
+        return B, lo, hi, ex, w
+
+    def expected_fit_dev(self, p_min, p_max, e_drive, weights, d_record_ptr, d_pi0_ptr=0, ivp=False, dest=False, d_expected_ptr=0,
+                         d_cotangent_ptr=0, d_grad_p_drive_ptr=0, d_grad_dest_ptr=0):
+        """Enqueue on the context's stream: the B points (p_min, p_max, e_drive: (B,)) with weights (B, 3) or (3,) = (w_act, w_park,
+        w_adrive) into d_record_ptr = device address of float64[B][fit_words()].  The batch tables hold these points afterwards.
+        d_expected_ptr / d_cotangent_ptr = device address of float64[B][2][T][Z] or 0; d_grad_p_drive_ptr / d_grad_dest_ptr = device
+        address of float64[B][T][Z] or 0 (kept in the library's workspace).  dest: also dF/de_dest, along the installed tangent."""
+        B, lo, hi, ex, w = self._fit_args(p_min, p_max, e_drive, weights)
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        flags = (_lib.CPM_EXPECT_IVP if ivp else 0) | (_lib.CPM_FIT_DEST if dest else 0)
+        _lib.check(self._L.cpm_expected_fit_dev(self._h, B, _vp(lo), _vp(hi), _vp(ex), p(d_pi0_ptr), flags, _vp(w), p(d_record_ptr),
+                                                p(d_expected_ptr), p(d_cotangent_ptr), p(d_grad_p_drive_ptr), p(d_grad_dest_ptr)))
+
+    @staticmethod
+    def fit_record(rec, T):
+        """An expected_fit record array (B, CPM_FIT_WORDS + T) as a dict of arrays over the fleets."""
+        rec = np.asarray(rec, dtype=np.float64).reshape(-1, _lib.CPM_FIT_WORDS + T)
+        names = ("F", "activity_error", "parking_error", "A_drive", "n_valid", "d_p_min", "d_p_max", "d_e_drive", "d_e_dest", "total_seconds",
+                 "total_km")
+        out = {k: rec[:, i].copy() for i, k in enumerate(names)}
+        out["n_valid"] = out["n_valid"].astype(np.int64)
+        out["traffic_activity"] = rec[:, _lib.CPM_FIT_WORDS:].copy()
+        out["record"] = rec
+        return out
+
+    def expected_fit(self, p_min, p_max, e_drive, weights, pi0=None, ivp=False, dest=False, want=()):
+        """Value and gradient of F = w_act * activity_error + w_park * parking_error + w_adrive * A_drive at B points, blocking: a dict
+        of (B,) arrays F, activity_error, parking_error, A_drive, n_valid, d_p_min, d_p_max, d_e_drive, d_e_dest (NaN without dest),
+        total_seconds, total_km, traffic_activity (B, T) and record (B, fit_words()).  want: names among "expected", "cotangent" (each
+        (B, 2, T, Z): parking then driving, hour-major), "grad_p_drive", "grad_dest" ((Z, T, B) F-order) to return as well."""
+        unknown = set(want) - {"expected", "cotangent", "grad_p_drive", "grad_dest"}
+        if unknown:
+            raise ValueError(f"expected_fit: unknown outputs {sorted(unknown)}")
+        if "grad_dest" in want and not dest:
+            raise ValueError("expected_fit: grad_dest needs dest=True")
+        B, lo, hi, ex, w = self._fit_args(p_min, p_max, e_drive, weights)
+        a = self._pi0(pi0)
+        rec = np.zeros((B, self.fit_words()), dtype=np.float64)
+        arrs = {}
+        for k in ("expected", "cotangent"):
+            arrs[k] = np.zeros((B, 2, self.T, self.Z), dtype=np.float64) if k in want else None
+        for k in ("grad_p_drive", "grad_dest"):
+            arrs[k] = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F") if k in want else None
+        flags = (_lib.CPM_EXPECT_IVP if ivp else 0) | (_lib.CPM_FIT_DEST if dest else 0)
+        _lib.check(self._L.cpm_expected_fit(self._h, B, _vp(lo), _vp(hi), _vp(ex), _vp(a), flags, _vp(w), _vp(rec), _vp(arrs["expected"]),
+                                            _vp(arrs["cotangent"]), _vp(arrs["grad_p_drive"]), _vp(arrs["grad_dest"])))
+        out = self.fit_record(rec, self.T)
+        out.update({k: v for k, v in arrs.items() if v is not None})
+        return out
+
     def last_kernel_ms(self):
         buf = (C.c_float * 8192)()
         n = C.c_int32(0)
