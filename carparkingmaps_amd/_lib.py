@@ -76,6 +76,10 @@ EXPECTED_GRAD_BATCH_SYMBOLS = ["cpm_expected_grad_batch_dev", "cpm_expected_grad
 # every symbol include/cpm_expected_fit.h declares (checked by tests/test_expected_fit.py); a header and a list of its own, likewise
 EXPECTED_FIT_SYMBOLS = ["cpm_set_measured_activity", "cpm_expected_fit_dev", "cpm_expected_fit"]
 
+# every symbol include/cpm_expected_tangent.h declares (checked by tests/test_expected_tangent.py); a header and a list of its own, likewise
+EXPECTED_TANGENT_SYMBOLS = ["cpm_expected_tangent_dev", "cpm_expected_tangent", "cpm_build_p_drive_tangent_dev", "cpm_build_p_drive_tangent"]
+CPM_TANGENT_MAX_DIRECTIONS = 16  # K of one expected_tangent call
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -129,6 +133,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad_dest.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad_batch.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_fit.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_tangent.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -242,9 +247,13 @@ def load():
     L.cpm_set_measured_activity.argtypes = [vp, vp]
     L.cpm_expected_fit_dev.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     L.cpm_expected_fit.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.cpm_expected_tangent_dev.argtypes = [vp, i32, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.cpm_expected_tangent.argtypes = [vp, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.cpm_build_p_drive_tangent_dev.argtypes = [vp, dbl, dbl, dbl, vp]
+    L.cpm_build_p_drive_tangent.argtypes = [vp, dbl, dbl, dbl, vp]
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
                  + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS + EXPECTED_GRAD_BATCH_SYMBOLS
-                 + EXPECTED_FIT_SYMBOLS):
+                 + EXPECTED_FIT_SYMBOLS + EXPECTED_TANGENT_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

@@ -26,6 +26,7 @@
 #include "../../include/cpm_expected_grad_dest.h"
 #include "../../include/cpm_expected_grad_batch.h"
 #include "../../include/cpm_expected_fit.h"
+#include "../../include/cpm_expected_tangent.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -47,6 +48,7 @@
 #include "cpm_expected_grad_dest.h"
 #include "cpm_expected_grad_batch.h"
 #include "cpm_expected_fit.h"
+#include "cpm_expected_tangent.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -289,6 +291,9 @@ struct cpm_ctx {
     DevBuf<double> d_fit_dw;            // [2][T][Z] the trip weights' tangent, kept while the tangent table and the trip weights stay
     int64_t fit_dw_gen = -1, fit_dw_builds = -1;
     DevBuf<double> d_fit_rec;           // [B][CPM_FIT_WORDS + T] the blocking call's records
+    // forward tangent of the expected densities (include/cpm_expected_tangent.h, cpm_expected_tangent.h)
+    DevBuf<double> d_tanf_ws;           // [2][passes][2][8][Zs] pi | x of the passes' vectors, ping and pong; [2][Zs] xm; [Zs] u (expected_tangent_enqueue)
+    DevBuf<double> d_tanf_io;           // the blocking calls' pi_0, directions and outputs (expected_tangent_blocking), or the builder's [3][T][Z]
     // options
     int kernel = CPM_KERNEL_AUTO;
     bool profile = false;
@@ -2081,6 +2086,145 @@ int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const doubl
     return CPM_OK;
 }
 
+// ------------------------------------------------------------------ forward tangent of the expected densities (include/cpm_expected_tangent.h)
+// what every entry checks behind exp_enter, before anything is read, copied or enqueued
+int32_t tangent_check(cpm_ctx *c, const char *what, int32_t K, uint32_t flags, const double *c_dest, const void *out)
+{
+    if (K < 1 || K > CPM_TANGENT_MAX_DIRECTIONS) return fail(CPM_ERR_ARG, "%s: K = %d outside 1 .. %d", what, K, CPM_TANGENT_MAX_DIRECTIONS);
+    if (!out) return fail(CPM_ERR_ARG, "%s: null tangent output", what);
+    int32_t rc = exp_flags_check(flags);
+    if (rc != CPM_OK) return rc;
+    bool any = false;
+    if (c_dest)
+        for (int k = 0; k < K; ++k) {
+            if (!std::isfinite(c_dest[k])) return fail(CPM_ERR_ARG, "%s: c_dest of direction %d is not finite", what, k + 1);
+            any = any || c_dest[k] != 0.0;
+        }
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "%s: p_drive not set", what);
+    if ((rc = exp_tables_ready(c, what)) != CPM_OK) return rc;
+    if (any && (rc = tangent_ready(c, what)) != CPM_OK) return rc;
+    return CPM_OK;
+}
+
+template <int NB>
+void launch_tan_hour(cpm_ctx *c, const cpm::TanHour &a)
+{
+    cpm::launch(cpm::k_tan_hour<NB>, dim3(nblk(a.Z, cpm::kExpRows)), dim3(cpm::kExpBlock), 0, c->stream, a);
+}
+
+// The recurrence of expected_enqueue (B = 1, the installed p_drive) for the primal and K directions: operator-major, per operator one
+// launch per pass of at most kTanDirs directions.  dpi0: [K][Z], dpd: [K][T][Z], c_dest: host [K] (each or nullptr: zero).
+// out: [K][2][T][Z]; dpi_next: [K][Z] or nullptr; expected: [2][T][Z] or nullptr.
+int32_t expected_tangent_enqueue(cpm_ctx *c, int K, const double *d_pi0, uint32_t flags, const double *dpi0, const double *dpd, const double *c_dest,
+                                 double *out, double *dpi_next, double *expected)
+{
+    int32_t rc = ensure_exp_aux(c);
+    if (rc != CPM_OK) return rc;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
+    const size_t zt = static_cast<size_t>(Z) * T;
+    bool with_u = false;
+    if (c_dest)
+        for (int k = 0; k < K; ++k) with_u = with_u || c_dest[k] != 0.0;
+    const int npass = (K + cpm::kTanDirs - 1) / cpm::kTanDirs;
+    const size_t side = static_cast<size_t>(npass) * 2 * cpm::kExpMaxNB * Zs;   // [passes][pi | x][8][Zs]
+    HIP_TRY(c->d_tanf_ws.reserve(2 * side + 3 * static_cast<size_t>(Zs)));  // (a grow frees first: hipFree waits for what still reads the old workspace)
+    double *ws[2] = {c->d_tanf_ws, c->d_tanf_ws + side};
+    double *ws_xm[2] = {c->d_tanf_ws + 2 * side, c->d_tanf_ws + 2 * side + Zs};
+    double *ws_u = c->d_tanf_ws + 2 * side + 2 * static_cast<size_t>(Zs);
+    const size_t vec = static_cast<size_t>(cpm::kExpMaxNB) * Zs;
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0;  // operators in front of the day
+    const double *pd = c->d_pdrive;
+    for (int ps = 0; ps < npass; ++ps) {
+        const int k0 = ps * cpm::kTanDirs, nv = std::min(K - k0, cpm::kTanDirs) + 1;
+        double *pi = ws[0] + static_cast<size_t>(ps) * 2 * vec;
+        double *dpark = pre == 0 ? out + static_cast<size_t>(k0) * 2 * zt : nullptr;
+        cpm::launch(cpm::k_tan_init, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(nv)), dim3(cpm::kExpBlock), 0, c->stream, d_pi0,
+                    dpi0 ? dpi0 + static_cast<size_t>(k0) * Z : nullptr, pd, dpd ? dpd + static_cast<size_t>(k0) * zt : nullptr, zt,
+                    static_cast<const double *>(c->d_last), Z, Zs, pi, pi + vec, (ps == 0 && with_u) ? ws_xm[0] : nullptr,
+                    (ps == 0 && pre == 0) ? expected : nullptr, (ps == 0 && pre == 0 && expected) ? expected + zt : nullptr, dpark,
+                    dpark ? dpark + zt : nullptr, 2 * zt);
+    }
+    HIP_TRY(hipGetLastError());
+    const int steps = pre + T;
+    for (int s = 0; s < steps; ++s) {
+        const int t = s < pre ? s : s - pre;
+        const int day_next = s + 1 - pre;  // the hour of the day whose state this step produces (< 0: still in front of it)
+        const bool more = s + 1 < steps;
+        const int t_next = s + 1 < pre ? s + 1 : s + 1 - pre;
+        const int in = s & 1, ot = in ^ 1;
+        const size_t row = static_cast<size_t>(t) * Z;
+        for (int ps = 0; ps < npass; ++ps) {
+            const int k0 = ps * cpm::kTanDirs, nv = std::min(K - k0, cpm::kTanDirs) + 1;
+            cpm::TanHour a{};
+            a.p_t = c->d_p + row * Z;
+            a.last_t = c->d_last + row;
+            a.r_t = c->d_exp_r + row;
+            a.start_t = c->d_exp_start + static_cast<size_t>(t) * (Z + 1);
+            a.list_t = c->d_exp_list + row;
+            a.last_next = more ? c->d_last + static_cast<size_t>(t_next) * Z : nullptr;
+            a.dp_t = with_u ? c->d_tan + row * Z : nullptr;
+            a.u = ws_u;
+            a.u_mode = !with_u ? 0 : ps == 0 ? 1 : 2;
+            a.q_cur = pd + row;
+            a.q_next = more ? pd + static_cast<size_t>(t_next) * Z : nullptr;
+            a.dq_cur = dpd ? dpd + static_cast<size_t>(k0) * zt + row : nullptr;
+            a.dq_next = (dpd && more) ? dpd + static_cast<size_t>(k0) * zt + static_cast<size_t>(t_next) * Z : nullptr;
+            a.dq_stride = zt;
+            a.pi_in = ws[in] + static_cast<size_t>(ps) * 2 * vec;
+            a.x_in = a.pi_in + vec;
+            a.xm_in = ws_xm[in];
+            a.pi_out = ws[ot] + static_cast<size_t>(ps) * 2 * vec;
+            a.x_out = a.pi_out + vec;
+            a.xm_out = (ps == 0 && with_u && more) ? ws_xm[ot] : nullptr;
+            if (day_next >= 0 && day_next < T) {
+                a.dpark = out + static_cast<size_t>(k0) * 2 * zt + static_cast<size_t>(day_next) * Z;
+                a.ddrv = a.dpark + zt;
+                a.out_stride = 2 * zt;
+                if (ps == 0 && expected) {
+                    a.park0 = expected + static_cast<size_t>(day_next) * Z;
+                    a.drv0 = a.park0 + zt;
+                }
+            } else if (day_next == T && dpi_next) {
+                a.dpark = dpi_next + static_cast<size_t>(k0) * Z;
+                a.out_stride = static_cast<size_t>(Z);
+            }
+            for (int f = 1; f < nv; ++f) a.c[f] = c_dest ? c_dest[k0 + f - 1] : 0.0;
+            a.Z = Z;
+            a.Zs = Zs;
+            a.nv = nv;
+            // the smallest instantiation that holds the pass (vectors beyond nv repeat the last one and are not stored)
+            if (nv > 5) launch_tan_hour<8>(c, a);
+            else if (nv > 4) launch_tan_hour<5>(c, a);  // (K = 4: the model's four parameters)
+            else if (nv > 2) launch_tan_hour<4>(c, a);
+            else launch_tan_hour<2>(c, a);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return CPM_OK;
+}
+
+int32_t check_finite(const char *what, const char *name, const double *v, size_t n)
+{
+    if (v)
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(v[i])) return fail(CPM_ERR_ARG, "%s: word %zu of %s is not finite", what, i + 1, name);
+    return CPM_OK;
+}
+
+// the builder of the three direction tables (cpm_expected_tangent.h): enqueued
+int32_t pdrive_tangent_enqueue(cpm_ctx *c, double p_min, double p_max, double e_drive, double *d_out)
+{
+    if (!c->have_dm()) return fail(CPM_ERR_STATE, "build_p_drive_tangent: datamatrix and distance matrix first");
+    int32_t rc = ensure_pdrive_mean(c);
+    if (rc != CPM_OK) return rc;
+    cpm::launch(cpm::k_tan_pdrive, dim3(nblk(c->Z, 64), static_cast<unsigned>(c->T)), dim3(64), 0, c->stream,
+                static_cast<const double *>(c->d_pdrive_mean.get()), d_out, static_cast<int>(c->Z), static_cast<int>(c->T), p_min, p_max, e_drive);
+    HIP_TRY(hipGetLastError());
+    return CPM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3738,6 +3882,78 @@ int32_t cpm_expected_fit(cpm_ctx *c, int32_t B, const double *p_min, const doubl
     if (cotangent) HIP_TRY(hipMemcpyAsync(cotangent, ws + l.cot, sizeof(double) * nb * 2 * zt, hipMemcpyDeviceToHost, c->stream));
     if (grad_p_drive) HIP_TRY(hipMemcpyAsync(grad_p_drive, ws + l.grad_pd, sizeof(double) * nb * zt, hipMemcpyDeviceToHost, c->stream));
     if (grad_dest && (flags & CPM_FIT_DEST)) HIP_TRY(hipMemcpyAsync(grad_dest, ws + l.grad_dest, sizeof(double) * nb * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ forward tangent of the expected densities (include/cpm_expected_tangent.h)
+
+int32_t cpm_expected_tangent_dev(cpm_ctx *c, int32_t K, const void *d_pi0, uint32_t flags, const void *d_dpi0, const void *d_dp_drive, const double *c_dest,
+                                 void *d_out, void *d_dpi_next, void *d_expected)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = tangent_check(c, "expected_tangent_dev", K, flags, c_dest, d_out)) != CPM_OK) return rc;
+    return expected_tangent_enqueue(c, K, static_cast<const double *>(d_pi0), flags, static_cast<const double *>(d_dpi0),
+                                    static_cast<const double *>(d_dp_drive), c_dest, static_cast<double *>(d_out), static_cast<double *>(d_dpi_next),
+                                    static_cast<double *>(d_expected));
+}
+
+int32_t cpm_expected_tangent(cpm_ctx *c, int32_t K, const double *pi0, uint32_t flags, const double *dpi0, const double *dp_drive, const double *c_dest,
+                             double *d_parking, double *d_driving, double *dpi_next, double *parking, double *driving)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = tangent_check(c, "expected_tangent", K, flags, c_dest, d_parking)) != CPM_OK) return rc;
+    if (!d_driving) return fail(CPM_ERR_ARG, "expected_tangent: null tangent output");
+    if ((parking == nullptr) != (driving == nullptr)) return fail(CPM_ERR_ARG, "expected_tangent: parking and driving go together");
+    if ((rc = check_pi0(c, pi0)) != CPM_OK) return rc;
+    const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nk = static_cast<size_t>(K);
+    if ((rc = check_finite("expected_tangent", "dpi0", dpi0, nk * Z)) != CPM_OK) return rc;
+    if ((rc = check_finite("expected_tangent", "dp_drive", dp_drive, nk * zt)) != CPM_OK) return rc;
+    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;  // (the row-total check: CPM_ERR_TABLE in front of the first copy)
+    // [K][2][T][Z] out | [2][T][Z] primal | [K][Z] d pi_next | [Z] pi_0 | [K][Z] d pi_0 | [K][T][Z] d p_drive
+    HIP_TRY(c->d_tanf_io.reserve(nk * 2 * zt + 2 * zt + nk * Z + Z + nk * Z + nk * zt));
+    double *d_out = c->d_tanf_io, *d_exp = d_out + nk * 2 * zt, *d_next = d_exp + 2 * zt, *d_pi0 = d_next + nk * Z, *d_dpi0 = d_pi0 + Z,
+           *d_dpd = d_dpi0 + nk * Z;
+    if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    if (dpi0) HIP_TRY(hipMemcpyAsync(d_dpi0, dpi0, sizeof(double) * nk * Z, hipMemcpyHostToDevice, c->stream));
+    if (dp_drive) HIP_TRY(hipMemcpyAsync(d_dpd, dp_drive, sizeof(double) * nk * zt, hipMemcpyHostToDevice, c->stream));
+    rc = expected_tangent_enqueue(c, K, pi0 ? d_pi0 : nullptr, flags, dpi0 ? d_dpi0 : nullptr, dp_drive ? d_dpd : nullptr, c_dest, d_out,
+                                  dpi_next ? d_next : nullptr, parking ? d_exp : nullptr);
+    if (rc != CPM_OK) return rc;
+    for (size_t k = 0; k < nk; ++k) {
+        HIP_TRY(hipMemcpyAsync(d_parking + k * zt, d_out + k * 2 * zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_driving + k * zt, d_out + k * 2 * zt + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (dpi_next) HIP_TRY(hipMemcpyAsync(dpi_next, d_next, sizeof(double) * nk * Z, hipMemcpyDeviceToHost, c->stream));
+    if (parking) {
+        HIP_TRY(hipMemcpyAsync(parking, d_exp, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(driving, d_exp + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+int32_t cpm_build_p_drive_tangent_dev(cpm_ctx *c, double p_min, double p_max, double e_drive, void *d_out)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_out) return fail(CPM_ERR_ARG, "build_p_drive_tangent_dev: null d_out");
+    CTX_TRY(c);
+    return pdrive_tangent_enqueue(c, p_min, p_max, e_drive, static_cast<double *>(d_out));
+}
+
+int32_t cpm_build_p_drive_tangent(cpm_ctx *c, double p_min, double p_max, double e_drive, double *out)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!out) return fail(CPM_ERR_ARG, "build_p_drive_tangent: null out");
+    CTX_TRY(c);
+    const size_t words = 3 * static_cast<size_t>(c->Z) * c->T;
+    HIP_TRY(c->d_tanf_io.reserve(words));
+    if ((rc = pdrive_tangent_enqueue(c, p_min, p_max, e_drive, c->d_tanf_io)) != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->d_tanf_io, sizeof(double) * words, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
 }

@@ -158,6 +158,60 @@ def e_dest_param_grad(grad_dest, driving=None, dw_sec=None):
     return d
 
 
+# ------------------------------------------------------------------ host residuals and their forward derivatives (for Sampler.expected_tangent)
+def _minmax_residual_jvp(v, dv, m, axis):
+    """(r, dr): r = ((v - lo) / (hi - lo) - m) / sqrt(n) along `axis` (n its length), so that sum(r * r) over the axis is the mean
+    squared error of the min-max normalised v, and dr[p] its derivative along dv[p] (dv has one leading axis more than v).  lo / hi are
+    attained at the FIRST minimum / maximum (include/cpm_expected_fit.h) and move with dv there.  A flat slice (hi == lo) has r = NaN,
+    like its error, and dr = 0."""
+    v, m, dv = np.asarray(v, dtype=np.float64), np.asarray(m, dtype=np.float64), np.asarray(dv, dtype=np.float64)
+    n = v.shape[axis]
+    imin, imax = np.expand_dims(v.argmin(axis=axis), axis), np.expand_dims(v.argmax(axis=axis), axis)
+    lo, hi = np.take_along_axis(v, imin, axis), np.take_along_axis(v, imax, axis)
+    rng = hi - lo
+    ok = rng != 0
+    safe = np.where(ok, rng, 1.0)
+    vn = (v - lo) / safe
+    dlo, dhi = np.take_along_axis(dv, imin[None], axis + 1), np.take_along_axis(dv, imax[None], axis + 1)
+    dvn = (dv - dlo) / safe - vn * ((dhi - dlo) / safe)
+    scale = 1.0 / np.sqrt(float(n))
+    return np.where(ok, (vn - m) * scale, np.nan), np.where(ok, dvn * scale, 0.0)
+
+
+def activity_residual_jvp(driving, d_driving, measured):
+    """(r (T,), Jr (P, T)) of the traffic-activity term: sum(r * r) = traffic_activity_error(traffic_activity(driving), measured), and
+    Jr[p] the derivative of r along d_driving[p] -- (Z, T) densities, (P, Z, T) tangents (Evaluator.expected_jacobian) -- carried
+    through the hours' zone sums and the min-max normalisation."""
+    a = np.asarray(driving, dtype=np.float64).sum(axis=0)
+    da = np.asarray(d_driving, dtype=np.float64).sum(axis=1)
+    return _minmax_residual_jvp(a, da, measured, 0)
+
+
+def parking_residual_jvp(parking, d_parking, measured):
+    """(r (Z, T), Jr (P, Z, T)) of the parking term: sum(r * r) = parking_density_error(parking, 1, measured), Jr[p] the derivative of
+    r along d_parking[p].  A zone that is not valid (unmeasured or flat) has r = 0 and Jr = 0; with no valid zone r is NaN."""
+    p = np.asarray(parking, dtype=np.float64)
+    m = np.asarray(measured, dtype=np.float64)
+    valid = (m.sum(axis=1) != 0) & (p.max(axis=1) != p.min(axis=1))
+    if not valid.any():
+        return np.full(p.shape, np.nan), np.zeros(np.shape(d_parking))
+    r, dr = _minmax_residual_jvp(p, d_parking, m, 1)
+    scale = 1.0 / np.sqrt(float(valid.sum()))
+    return np.where(valid[:, None], r * scale, 0.0), np.where(valid[None, :, None], dr * scale, 0.0)
+
+
+def a_drive_jvp(w_sec, d_driving, driving=None, dw_sec=None):
+    """(P,): the derivative of the noise-free A_drive = sum(driving * w_sec) / (T * 3600) along d_driving[p], <a_drive_grad(w_sec),
+    d_driving[p]>.  With driving and Sampler.expected_trip_tangent()'s dw_sec the direct term through the trip weights,
+    sum(driving * dw_sec) / (T * 3600), is added to the LAST parameter: e_dest, in Evaluator.expected_jacobian's order."""
+    w = np.asarray(w_sec, dtype=np.float64)
+    n = w.shape[1] * 3600.0
+    out = (np.asarray(d_driving, dtype=np.float64) * (w / n)[None]).sum(axis=(1, 2))
+    if dw_sec is not None:
+        out[-1] += float((np.asarray(driving, dtype=np.float64) * np.asarray(dw_sec, dtype=np.float64)).sum() / n)
+    return out
+
+
 def parking_density_zone_errors(parking, C, measured):
     """The definition of include/cpm_objectives.h on the host, one IEEE f64 operation per step and in its order: (err (Z,) float64
     with -1.0 for a zone that is not valid, valid (Z,) bool).  A zone is valid when its measured row, added in hour order, is != 0 and
@@ -441,6 +495,34 @@ class Evaluator:
             outs.append(out)
         return outs
 
+    def expected_jacobian(self, pt, ivp=True, dest=False):
+        """The densities of evaluate_expected(pt, ivp) and their derivatives for the model's parameters, in forward mode: pt's tables
+        are installed as expected_gradient() installs them, the direction tables d p_drive / d (p_min, p_max, e_drive) are built on the
+        device (Sampler.build_p_drive_tangent_dev) and ONE tangent call (Sampler.expected_tangent_dev, include/cpm_expected_tangent.h)
+        carries K = 3 directions -- 4 with dest: the last one along d p_destin / d e_dest (pt.e_dest > 0).  Returns dict(parking,
+        driving (Z, T), d_parking, d_driving (P, Z, T)) in the parameter order (e_drive, p_min, p_max[, e_dest])."""
+        import torch
+        s = self.sampler
+        self._install(pt)
+        if dest:
+            self._install_dest_tangent()
+        K, zt = (4 if dest else 3), s.Z * s.T
+        dev = f"cuda:{s.device}"
+        built = torch.empty(3 * zt, dtype=torch.float64, device=dev)      # (p_min, p_max, e_drive), as the builder lays them out
+        dpd = torch.zeros(K * zt, dtype=torch.float64, device=dev)
+        out = torch.empty(K * 2 * zt, dtype=torch.float64, device=dev)
+        primal = torch.empty(2 * zt, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(s.device)
+        s.build_p_drive_tangent_dev(pt.p_min, pt.p_max, pt.e_drive, built.data_ptr())
+        s.sync()
+        dpd[:zt], dpd[zt:2 * zt], dpd[2 * zt:3 * zt] = built[2 * zt:], built[:zt], built[zt:2 * zt]
+        torch.cuda.synchronize(s.device)
+        s.expected_tangent_dev(K, out.data_ptr(), dpd.data_ptr(), c_dest=[0.0, 0.0, 0.0, 1.0][:K], ivp=ivp, d_expected_ptr=primal.data_ptr())
+        s.sync()
+        both = out.cpu().numpy().reshape(K, 2, s.T, s.Z)
+        prim = primal.cpu().numpy().reshape(2, s.T, s.Z)
+        return dict(parking=prim[0].T, driving=prim[1].T, d_parking=both[:, 0].transpose(0, 2, 1), d_driving=both[:, 1].transpose(0, 2, 1))
+
     # -- device objectives: the record of include/cpm_objectives.h in the place of the count tensor --
     def _from_record(self, pt, rec):
         return objectives_from_record(rec, pt, self.C, self.sampler.T, self.measured_activity, self.measured_parking is not None)
@@ -708,6 +790,107 @@ def refine_expected(evaluator, pts, weights=None, steps=10, bounds=None, ivp=Tru
                 refused[k] += 1
                 alpha[k] = alpha[k] * shrink if refused[k] <= max_backtracks else 0.0
     return [dict(path=paths[k], gradient=tuple(vec(cur[k])), result=cur[k], calls=calls) for k in range(B)]
+
+
+def _lm_terms(evaluator, jac, w, w_sec):
+    """(F, result dict, J^T r, J^T J, gradient of F) over (e_drive, p_min, p_max) from one expected_jacobian() dict: the weighed
+    least-squares residuals stacked, A_drive through its gradient only"""
+    rows, jrows, res = [], [], {}
+    F, lin = 0.0, np.zeros(3)
+    if w[0] != 0:
+        r, Jr = activity_residual_jvp(jac["driving"], jac["d_driving"][:3], evaluator.measured_activity)
+        res["activity_error"] = float((r * r).sum())
+        F += w[0] * res["activity_error"]
+        rows.append(np.sqrt(w[0]) * r.ravel())
+        jrows.append(np.sqrt(w[0]) * Jr.reshape(3, -1))
+    if w[1] != 0:
+        r, Jr = parking_residual_jvp(jac["parking"], jac["d_parking"][:3], evaluator.measured_parking)
+        res["parking_error"] = float((r * r).sum())
+        F += w[1] * res["parking_error"]
+        rows.append(np.sqrt(w[1]) * r.ravel())
+        jrows.append(np.sqrt(w[1]) * Jr.reshape(3, -1))
+    if w[2] != 0:
+        res["A_drive"] = float((np.asarray(jac["driving"]) * w_sec).sum() / (w_sec.shape[1] * 3600.0))
+        F += w[2] * res["A_drive"]
+        lin = w[2] * a_drive_jvp(w_sec, jac["d_driving"][:3])
+    r = np.concatenate(rows) if rows else np.zeros(0)
+    J = np.concatenate(jrows, axis=1) if jrows else np.zeros((3, 0))
+    Jtr = J @ r
+    res["F"] = F
+    return F, res, Jtr, J @ J.T, 2.0 * Jtr + lin
+
+
+def refine_expected_lm(evaluator, pts, weights=None, steps=10, bounds=None, ivp=True, lam0=1e-3, min_gap=1e-3, jacobian=None):
+    """Levenberg-Marquardt on (e_drive, p_min, p_max) for the noise-free F of Evaluator.expected_fit, from the densities' Jacobian in
+    forward mode: activity_error and parking_error are sums of squared residuals r (activity_residual_jvp, parking_residual_jvp) with
+    Jacobian J; a weighed A_drive enters through its gradient only.  Per step
+        delta = -(J^T J + lam * diag(J^T J))^-1 (J^T r + w_adrive / 2 * grad A_drive),
+    the trial P(x + delta) (the projection of refine_expected) is accepted when F decreases, and lam is then divided by 3; a refused
+    trial multiplies lam by 4.  steps: trial steps per point, ONE Jacobian call each (refine_expected takes up to 13 expected_fit calls
+    per accepted step).  jacobian: a callable pt -> dict(parking, driving (Z, T), d_parking, d_driving (P >= 3, Z, T)[, w_sec (Z, T)]) in
+    the parameter order (e_drive, p_min, p_max); default evaluator.expected_jacobian(pt, ivp=ivp), with Sampler.expected_trip()'s w_sec
+    where A_drive is weighed -- any evaluator with measured_activity / measured_parking can drive it, a numpy one included.  Weights
+    of the least-squares terms must not be negative.  bounds, min_gap: as in refine_expected.  Returns per point refine_expected's dict
+    -- path: [(Point, F), ...] of the accepted points, the start first; gradient: dF/d(e_drive, p_min, p_max) at the last one; result:
+    dict(F and the weighed terms) there; calls: Jacobian calls made -- plus lam, the damping it ended with."""
+    b = dict(DEFAULT_FIT_BOUNDS)
+    for k, v in (bounds or {}).items():
+        if k not in b:
+            raise ValueError(f"refine_expected_lm: unknown bound {k!r}")
+        b[k] = (float(v[0]), float(v[1]))
+    lo = np.array([b["e_drive"][0], b["p_min"][0], b["p_max"][0]])
+    hi = np.array([b["e_drive"][1], b["p_min"][1], b["p_max"][1]])
+    if not (lo <= hi).all():
+        raise ValueError("refine_expected_lm: bounds that cross")
+    if not lo[0] > 0:
+        raise ValueError("refine_expected_lm: e_drive must stay above 0")
+    if lo[1] + min_gap > hi[2]:
+        raise ValueError("refine_expected_lm: bounds that cross: no room for p_min < p_max")
+    if not (np.isfinite(lam0) and lam0 > 0):
+        raise ValueError("refine_expected_lm: lam0 must be positive")
+    pts, w = _fit_inputs("refine_expected_lm", evaluator, pts, weights)
+    if (w[:, :2] < 0).any():
+        raise ValueError("refine_expected_lm: a negative weight on a least-squares term")
+    e_dest = pts[0].e_dest
+    point = lambda x: Point(e_drive=float(x[0]), p_min=float(x[1]), p_max=float(x[2]), e_dest=e_dest)
+    if jacobian is None:
+        jacobian = lambda pt: evaluator.expected_jacobian(pt, ivp=ivp)
+    outs = []
+    for k, pt in enumerate(pts):
+        calls = 0
+
+        def terms(x):
+            jac = jacobian(point(x))
+            w_sec = None
+            if w[k, 2] != 0:   # (after the call: the weights belong to the tables it installed)
+                w_sec = np.asarray(jac["w_sec"] if "w_sec" in jac else evaluator.sampler.expected_trip()[0], dtype=np.float64)
+            return _lm_terms(evaluator, jac, w[k], w_sec)
+
+        x = _project(np.array([pt.e_drive, pt.p_min, pt.p_max], dtype=np.float64), lo, hi, min_gap)
+        cur = terms(x)
+        calls += 1
+        path, lam = [(point(x), cur[0])], float(lam0)
+        for _ in range(int(steps)):
+            F, _, Jtr, JtJ, grad = cur
+            if not np.isfinite(F):
+                break
+            diag = np.where(np.diag(JtJ) > 0, np.diag(JtJ), 1.0)     # (a parameter no residual moves with: damped on its own scale)
+            try:
+                delta = -np.linalg.solve(JtJ + lam * np.diag(diag), 0.5 * grad)
+            except np.linalg.LinAlgError:
+                break
+            trial = _project(x + delta, lo, hi, min_gap)
+            if not (x - trial).any():                # the projection holds the point where it is: nothing left to gain
+                break
+            new = terms(trial)
+            calls += 1
+            if np.isfinite(new[0]) and new[0] < F:
+                x, cur, lam = trial, new, lam / 3.0
+                path.append((point(x), cur[0]))
+            else:
+                lam *= 4.0
+        outs.append(dict(path=path, gradient=tuple(cur[4]), result=cur[1], calls=calls, lam=lam))
+    return outs
 
 
 def e_dest_key(e_dest):
