@@ -80,6 +80,10 @@ EXPECTED_FIT_SYMBOLS = ["cpm_set_measured_activity", "cpm_expected_fit_dev", "cp
 EXPECTED_TANGENT_SYMBOLS = ["cpm_expected_tangent_dev", "cpm_expected_tangent", "cpm_build_p_drive_tangent_dev", "cpm_build_p_drive_tangent"]
 CPM_TANGENT_MAX_DIRECTIONS = 16  # K of one expected_tangent call
 
+# every symbol include/cpm_expected_sparse.h declares (checked by tests/test_expected_sparse.py); a header and a list of its own, likewise
+EXPECTED_SPARSE_SYMBOLS = ["cpm_expected_sparse_dev", "cpm_expected_sparse_batch_dev", "cpm_expected_sparse", "cpm_expected_sparse_batch",
+                           "cpm_expected_sparse_aux"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -94,6 +98,7 @@ CPM_INFO_KERNEL, CPM_INFO_CAP_MULT, CPM_INFO_PARTS, CPM_INFO_FUSED, CPM_INFO_FUS
 CPM_INFO_LAST_KERNEL, CPM_INFO_LAST_FORM, CPM_INFO_STEPS_REPEATED = 7, 8, 9
 CPM_INFO_LAST_HOUR = 11  # 1: hour T of the most recent step ran the count-only kernel (10 stays unknown: tests/abi_harness.c)
 CPM_INFO_TRAVEL_TABLE = 12  # the travel table of the resident datamatrix: 0 none yet, 1 compact rows (dataset route), 2 sparse rows, 3 dense gather
+CPM_INFO_P_DENSE = 13  # 1: the dense [T][Z][Z] p_destin array is resident and valid for the installed tables (include/cpm.h)
 CPM_KIT_LOG, CPM_KIT_SQRT, CPM_KIT_ERF, CPM_KIT_PPND, CPM_KIT_EXP_NEG = 0, 1, 2, 3, 4  # cpm_debug_f64_kit's functions
 # include/cpm_batch.h: the installed batch tables' fleets, the fleets the batched kernels produced in the most recent batch step, and the
 # CPM_INFO_LAST_FORM of such a step
@@ -134,6 +139,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_grad_batch.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_fit.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_tangent.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_sparse.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -225,6 +231,11 @@ def load():
     L.cpm_expected_batch_dev.argtypes = [vp, vp, u32, vp]
     L.cpm_expected.argtypes = [vp, vp, u32, vp, vp, vp]
     L.cpm_expected_batch.argtypes = [vp, vp, u32, vp, vp]
+    L.cpm_expected_sparse_dev.argtypes = [vp, vp, u32, vp, vp]
+    L.cpm_expected_sparse_batch_dev.argtypes = [vp, vp, u32, vp]
+    L.cpm_expected_sparse.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.cpm_expected_sparse_batch.argtypes = [vp, vp, u32, vp, vp]
+    L.cpm_expected_sparse_aux.argtypes = [vp, i32, vp, vp, vp, vp]
     L.cpm_expected_trip_dev.argtypes = [vp, vp]
     L.cpm_expected_trip.argtypes = [vp, vp, vp]
     L.cpm_expected_travel_dev.argtypes = [vp, vp, i32, vp, vp]
@@ -253,7 +264,7 @@ def load():
     L.cpm_build_p_drive_tangent.argtypes = [vp, dbl, dbl, dbl, vp]
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
                  + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS + EXPECTED_GRAD_BATCH_SYMBOLS
-                 + EXPECTED_FIT_SYMBOLS + EXPECTED_TANGENT_SYMBOLS):
+                 + EXPECTED_FIT_SYMBOLS + EXPECTED_TANGENT_SYMBOLS + EXPECTED_SPARSE_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

@@ -27,6 +27,7 @@
 #include "../../include/cpm_expected_grad_batch.h"
 #include "../../include/cpm_expected_fit.h"
 #include "../../include/cpm_expected_tangent.h"
+#include "../../include/cpm_expected_sparse.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -49,6 +50,7 @@
 #include "cpm_expected_grad_batch.h"
 #include "cpm_expected_fit.h"
 #include "cpm_expected_tangent.h"
+#include "cpm_expected_sparse.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -260,6 +262,20 @@ struct cpm_ctx {
     DevBuf<unsigned long long> d_exp_bad;     // the first row whose total exceeds 1, and its pinned twin
     PinnedBuf<unsigned long long> h_exp_bad;
     bool exp_aux_valid = false;
+    // the same from the compact rows of sparse tables, and their transpose (include/cpm_expected_sparse.h, cpm_expected_sparse.h): arrays of
+    // their own, so that exp_aux_valid keeps meaning "built with the dense array expanded"; stale wherever exp_aux_valid is
+    DevBuf<int> d_exps_ell;             // [T][Z]
+    DevBuf<double> d_exps_r;            // [T][Z]
+    DevBuf<int> d_exps_start;           // [T][Z + 1]
+    DevBuf<int> d_exps_list;            // [T][Z]
+    DevBuf<uint32_t> d_exps_colptr;     // [T][Z + 1] where column (t, d) begins in ...
+    DevBuf<uint32_t> d_exps_o;          // [cells] ... the origins and ...
+    DevBuf<double> d_exps_p;            // [cells] ... the values of the stored cells, each column sorted by cpm::exps_key
+    DevBuf<uint32_t> d_exps_cur;        // [T][Z + 1] the builder's counts, then its tickets
+    DevBuf<unsigned long long> d_exps_stat;   // {first row whose total exceeds 1, cells}, and their pinned twin
+    PinnedBuf<unsigned long long> h_exps_stat;
+    size_t exps_cells = 0;
+    bool exps_valid = false;
     DevBuf<double> d_exp_ws;            // [4][cap / 4] pi and x, ping and pong, of as many fleets ([Zs] each) as it was last grown for
     DevBuf<double> d_exp_out;           // [B][2][T][Z] + [Z] + [Z]: the blocking calls' outputs; pi_next and pi_0 end the allocation (exp_out_tail)
     // expected travel (include/cpm_expected_travel.h, cpm_expected_travel.h): the trip weights, built on first use and stale wherever
@@ -400,6 +416,7 @@ int32_t build_rows(cpm_ctx *c, bool with_cdf)
     const bool cdf = with_cdf || !pack;
     c->have_cdf = false;
     c->exp_aux_valid = false;
+    c->exps_valid = false;
     c->exp_trip_valid = false;
     c->cdf_full = false;
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
@@ -661,6 +678,7 @@ int32_t build_p_dest_sparse(cpm_ctx *c, double e_dest, int32_t e_is_integer, boo
     c->have_cdf = false;
     c->cdf_full = false;
     c->exp_aux_valid = false;
+    c->exps_valid = false;
     c->exp_trip_valid = false;
     hipLaunchKernelGGL(cpm::k_ds_pdest, dim3(cpm::ds_grid(rows)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_ds_cells, c->d_ds_cnt, cpm::kDsCap,
                        rows, static_cast<int>(c->Z), e_dest, e_is_integer, nc, zq_c, g_c, c->d_hi, c->d_last, c->d_sp, c->d_sj, c->d_scnt, c->d_err);
@@ -687,6 +705,7 @@ int32_t pack_uploaded_rows(cpm_ctx *c, int nc)
     const int64_t rows = c->T * c->Z;
     const int zq_c = cpm::pack_zq(nc), g_c = cpm::pack_guide_bits(nc);
     c->exp_aux_valid = false;
+    c->exps_valid = false;
     c->exp_trip_valid = false;
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     int32_t rc = ensure_hi(c, static_cast<size_t>(rows) * cpm::pack_row_words(zq_c, g_c, 1));
@@ -1278,6 +1297,67 @@ int32_t ensure_exp_aux(cpm_ctx *c)
     return CPM_OK;
 }
 
+// The same per-table arrays from the compact rows of sparse tables, and the rows' transpose (cpm_expected_sparse.h): once per table.
+// d_p is neither read nor built, and exp_aux_valid is left alone: launch_exp_hour reads d_p on the strength of ensure_exp_aux.
+// Synchronises once (the row-total check and the number of cells are read back).
+int32_t ensure_exps(cpm_ctx *c)
+{
+    if (!c->sparse_tables)
+        return fail(CPM_ERR_STATE, "expected_sparse: the installed p_destin tables have no compact rows (cpm_build_p_dest on a sparse datamatrix, or "
+                                   "cpm_set_p_dest under CPM_OPT_SPARSE_UPLOAD, produce them)");
+    if (c->exps_valid) return CPM_OK;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    if (Z > cpm::kExpsMaxZ) return fail(CPM_ERR_STATE, "expected_sparse: more than %d zones", cpm::kExpsMaxZ);
+    const int64_t nrows = static_cast<int64_t>(Z) * T;
+    const size_t rows = static_cast<size_t>(nrows), cols = rows + T;
+    HIP_TRY(c->d_exps_ell.reserve(rows));
+    HIP_TRY(c->d_exps_r.reserve(rows));
+    HIP_TRY(c->d_exps_start.reserve(cols));
+    HIP_TRY(c->d_exps_list.reserve(rows));
+    HIP_TRY(c->d_exps_colptr.reserve(cols + 1));
+    HIP_TRY(c->d_exps_stat.reserve(2));
+    HIP_TRY(c->h_exps_stat.reserve(2));
+    HIP_TRY(c->d_exps_cur.reserve(cols));
+    uint32_t *const d_cur = c->d_exps_cur;  // the columns' counts, then the fill's tickets
+    HIP_TRY(hipMemsetAsync(c->d_exps_stat, 0xff, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(d_cur, 0, sizeof(uint32_t) * cols, c->stream));
+    const dim3 rgrid(cpm::ds_grid(nrows)), rblock(cpm::kDsThreads * cpm::kDsRows);
+    cpm::launch(cpm::k_exps_aux, rgrid, rblock, 0, c->stream, c->d_sp.get(), c->d_sj.get(), c->d_scnt.get(), cpm::kDsCap, nrows, Z, c->d_last,
+                c->d_exps_ell.get(), c->d_exps_r.get(), c->d_exps_stat.get(), d_cur);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T));
+    const size_t lds = sizeof(int) * static_cast<size_t>(Z);
+    HIP_TRY(cpm::lds_opt_in<cpm::k_exp_lists>(lds));
+    cpm::launch(cpm::k_exp_lists, grid, dim3(cpm::kExpBlock), lds, c->stream, c->d_exps_ell.get(), Z, c->d_exps_start.get(), c->d_exps_list.get());
+    HIP_TRY(hipGetLastError());
+    cpm::launch(cpm::k_exps_scan, dim3(1), dim3(cpm::kExpBlock), 0, c->stream, d_cur, cols, c->d_exps_colptr.get(), c->d_exps_stat.get() + 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_exps_stat, c->d_exps_stat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const unsigned long long bad = c->h_exps_stat[0];
+    if (bad != ~0ull)
+        return fail(CPM_ERR_TABLE, "expected: the row total of hour %llu, origin %llu exceeds 1: not the sampler's law (include/cpm_expected.h)",
+                    bad / static_cast<unsigned long long>(Z) + 1, bad % static_cast<unsigned long long>(Z) + 1);
+    const size_t cells = static_cast<size_t>(c->h_exps_stat[1]);
+    if (cells > rows * cpm::kDsCap) return fail(CPM_ERR_HIP, "expected_sparse: %zu cells counted in rows that hold %zu", cells, rows * cpm::kDsCap);
+    HIP_TRY(c->d_exps_o.reserve(cells));
+    HIP_TRY(c->d_exps_p.reserve(cells));
+    DevBuf<double> d_tmp;  // the columns' cells in the order the tickets came, values then origins: freed behind the sort (hipFree waits for it)
+    HIP_TRY(d_tmp.reserve(cells + (cells + 1) / 2));
+    double *const d_tmp_p = d_tmp;
+    uint32_t *const d_tmp_o = reinterpret_cast<uint32_t *>(d_tmp_p + cells);
+    HIP_TRY(hipMemsetAsync(d_cur, 0, sizeof(uint32_t) * cols, c->stream));
+    cpm::launch(cpm::k_exps_fill, rgrid, rblock, 0, c->stream, c->d_sp.get(), c->d_sj.get(), c->d_scnt.get(), cpm::kDsCap, nrows, Z, c->d_exps_colptr.get(),
+                d_cur, d_tmp_o, d_tmp_p);
+    HIP_TRY(hipGetLastError());
+    cpm::launch(cpm::k_exps_sort, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream, c->d_exps_colptr.get(),
+                d_tmp_o, d_tmp_p, Z, c->d_exps_o.get(), c->d_exps_p.get());
+    HIP_TRY(hipGetLastError());
+    c->exps_cells = cells;
+    c->exps_valid = true;
+    return CPM_OK;
+}
+
 // the installed p_destin tables are there for the propagation to read (what: the family that asks, as its error text names it)
 int32_t exp_tables_ready(const cpm_ctx *c, const char *what)
 {
@@ -1296,13 +1376,26 @@ void launch_exp_hour(cpm_ctx *c, int t, const double *q_cur, const double *q_nex
                 out_stride, Z, Zs, nf);
 }
 
+// the same hour from the transposed compact rows (k_exps_hour; ensure_exps built them)
+template <int NB>
+void launch_exps_hour(cpm_ctx *c, int t, const double *q_cur, const double *q_next, size_t q_stride, const double *pi_in, const double *x_in,
+                      double *pi_out, double *x_out, double *park, double *drv, size_t out_stride, int Zs, int nf)
+{
+    const int Z = static_cast<int>(c->Z);
+    const size_t row = static_cast<size_t>(t) * Z;
+    cpm::launch(cpm::k_exps_hour<NB>, dim3(nblk(Z, cpm::kExpRows)), dim3(cpm::kExpBlock), 0, c->stream, c->d_exps_colptr + static_cast<size_t>(t) * (Z + 1),
+                c->d_exps_o.get(), c->d_exps_p.get(), t & 1, c->d_last + row, c->d_exps_r + row, c->d_exps_start + static_cast<size_t>(t) * (Z + 1),
+                c->d_exps_list + row, q_cur, q_next, q_stride, pi_in, x_in, pi_out, x_out, park, drv, out_stride, Z, Zs, nf);
+}
+
 // The recurrence for B fleets whose p_drive tables ([T][Z] each) lie q_stride words apart at pd: enqueued on the context's stream.
-// out: [B][2][T][Z].  pi_next: [Z] or nullptr (B = 1).
-int32_t expected_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *out, double *pi_next)
+// out: [B][2][T][Z].  pi_next: [Z] or nullptr (B = 1).  sparse: the hours read the transposed compact rows (k_exps_hour) instead of d_p.
+int32_t expected_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *out, double *pi_next,
+                         bool sparse = false)
 {
     int32_t rc = exp_tables_ready(c, "expected");
     if (rc != CPM_OK) return rc;
-    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
+    if ((rc = sparse ? ensure_exps(c) : ensure_exp_aux(c)) != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;  // (every fleet's vector starts on a 16-byte line)
     HIP_TRY(c->d_exp_ws.reserve(4 * static_cast<size_t>(B) * Zs));  // (a grow frees first: hipFree waits for what still reads the old workspace)
@@ -1337,7 +1430,8 @@ int32_t expected_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B,
             // the smallest instantiation that holds the pass (fleets beyond nf repeat the last one and are not stored)
             using Go = void (*)(cpm_ctx *, int, const double *, const double *, size_t, const double *, const double *, double *, double *, double *, double *,
                                 size_t, int, int);
-            const Go go = nf > 4 ? Go(launch_exp_hour<8>) : nf > 2 ? Go(launch_exp_hour<4>) : nf > 1 ? Go(launch_exp_hour<2>) : Go(launch_exp_hour<1>);
+            const Go go = sparse ? (nf > 4 ? Go(launch_exps_hour<8>) : nf > 2 ? Go(launch_exps_hour<4>) : nf > 1 ? Go(launch_exps_hour<2>) : Go(launch_exps_hour<1>))
+                                 : (nf > 4 ? Go(launch_exp_hour<8>) : nf > 2 ? Go(launch_exp_hour<4>) : nf > 1 ? Go(launch_exp_hour<2>) : Go(launch_exp_hour<1>));
             go(c, t, q_cur, q_next, q_stride, ws_pi[in] + w0, ws_x[in] + w0, ws_pi[ot] + w0, ws_x[ot] + w0, park, drv, out_stride, Zs, nf);
         }
         HIP_TRY(hipGetLastError());
@@ -1399,7 +1493,7 @@ int32_t ensure_exp_out(cpm_ctx *c, int B, double **tail)
 }
 
 int32_t expected_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *parking, double *driving,
-                          double *pi_next)
+                          double *pi_next, bool sparse = false)
 {
     int32_t rc = check_pi0(c, pi0);
     if (rc != CPM_OK) return rc;
@@ -1408,7 +1502,7 @@ int32_t expected_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, 
     const size_t zt = static_cast<size_t>(c->Z) * c->T;
     double *d_pi0 = d_next + c->Z;
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream));
-    rc = expected_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, c->d_exp_out, pi_next ? d_next : nullptr);
+    rc = expected_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, c->d_exp_out, pi_next ? d_next : nullptr, sparse);
     if (rc != CPM_OK) return rc;
     for (int b = 0; b < B; ++b) {
         HIP_TRY(hipMemcpyAsync(parking + b * zt, c->d_exp_out + b * 2 * zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
@@ -2401,6 +2495,9 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
         return CPM_OK;
     case CPM_INFO_FUSED_BAILOUTS:
         *value_out = c->fused_bailouts;
+        return CPM_OK;
+    case CPM_INFO_P_DENSE:
+        *value_out = c->have_cdf && (c->sparse_tables ? c->p_dense_valid : c->d_p.get() != nullptr) ? 1 : 0;
         return CPM_OK;
     case CPM_INFO_LAST_KERNEL:
     case CPM_INFO_LAST_FORM:
@@ -3577,6 +3674,66 @@ int32_t cpm_expected_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double
     ExpTables tb;
     if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
     return expected_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, parking, driving, nullptr);
+}
+
+// ------------------------------------------------------------------ the same from sparse tables (include/cpm_expected_sparse.h)
+
+int32_t cpm_expected_sparse_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, void *d_out, void *d_pi_next)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_out) return fail(CPM_ERR_ARG, "expected_sparse_dev: null d_out");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    return expected_enqueue(c, static_cast<const double *>(d_pi0), flags, tb.B, tb.pd, tb.q_stride, static_cast<double *>(d_out),
+                            static_cast<double *>(d_pi_next), true);
+}
+
+int32_t cpm_expected_sparse_batch_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, void *d_out)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_out) return fail(CPM_ERR_ARG, "expected_sparse_batch_dev: null d_out");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    return expected_enqueue(c, static_cast<const double *>(d_pi0), flags, tb.B, tb.pd, tb.q_stride, static_cast<double *>(d_out), nullptr, true);
+}
+
+int32_t cpm_expected_sparse(cpm_ctx *c, const double *pi0, uint32_t flags, double *parking, double *driving, double *pi_next)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "expected_sparse: null density outputs");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    return expected_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, parking, driving, pi_next, true);
+}
+
+int32_t cpm_expected_sparse_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double *parking, double *driving)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!parking || !driving) return fail(CPM_ERR_ARG, "expected_sparse_batch: null density outputs");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    return expected_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, parking, driving, nullptr, true);
+}
+
+int32_t cpm_expected_sparse_aux(cpm_ctx *c, int32_t sparse, int32_t *ell, double *r, int32_t *start, int32_t *list)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!ell || !r || !start || !list) return fail(CPM_ERR_ARG, "expected_sparse_aux: null outputs");
+    CTX_TRY(c);
+    if ((rc = exp_tables_ready(c, "expected_sparse_aux")) != CPM_OK) return rc;
+    if ((rc = sparse ? ensure_exps(c) : ensure_exp_aux(c)) != CPM_OK) return rc;
+    const size_t rows = static_cast<size_t>(c->Z) * c->T;
+    HIP_TRY(hipMemcpyAsync(ell, sparse ? c->d_exps_ell.get() : c->d_exp_ell.get(), sizeof(int) * rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(r, sparse ? c->d_exps_r.get() : c->d_exp_r.get(), sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(start, sparse ? c->d_exps_start.get() : c->d_exp_start.get(), sizeof(int) * (rows + c->T), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(list, sparse ? c->d_exps_list.get() : c->d_exp_list.get(), sizeof(int) * rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
 }
 
 // ------------------------------------------------------------------ expected travel (include/cpm_expected_travel.h)

@@ -278,6 +278,7 @@ class Evaluator:
     travel: bool = True
     fallbacks: int = 0      # pipelined points whose asynchronous step overflowed a bucket region and were evaluated again, blocking
     device_objectives: bool = False   # reduce the counts on the device (include/cpm_objectives.h): the host reads 4 + 2*T words per point
+    expected_sparse: bool = False     # evaluate_expected[_batch] propagate from the compact rows of sparse tables (include/cpm_expected_sparse.h): same bits
     _e_dest: object = field(default=None, repr=False)
     _pipe: object = field(default=None, repr=False)
     _s_table: object = field(default=None, repr=False)   # build_p_drive(0, 1, 1): the datamatrix's own table, for expected_gradient
@@ -337,9 +338,9 @@ class Evaluator:
         tot = torch.empty(2 * B, dtype=torch.float64, device=dev)
         torch.cuda.synchronize(s.device)
         if batch:
-            s.expected_batch_dev(out.data_ptr(), 0, ivp)
+            s.expected_batch_dev(out.data_ptr(), 0, ivp, sparse=self.expected_sparse)
         else:
-            s.expected_dev(out.data_ptr(), 0, ivp)
+            s.expected_dev(out.data_ptr(), 0, ivp, sparse=self.expected_sparse)
         s.expected_travel_dev(out.data_ptr(), B, 0, tot.data_ptr())
         s.sync()
         both = out.cpu().numpy().reshape(B, 2, s.T, s.Z)

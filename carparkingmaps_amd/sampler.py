@@ -548,44 +548,59 @@ class Sampler:
     def _pi0(self, pi0):
         return None if pi0 is None else np.ascontiguousarray(_f64(pi0, (self.Z,)))
 
-    def expected(self, pi0=None, ivp=False, want_next=False):
+    def expected(self, pi0=None, ivp=False, want_next=False, sparse=False):
         """The mean of the sampler's chain from the installed tables, blocking: (parking_density, driving_density), each (Z, T)
         float64 F-order; parking_density[:, t] = pi_t, driving_density = pi_t * p_drive as the Bernoulli maps it.  C * these are
         the expected counts of resample().  pi0: (Z,) or None (uniform 1/Z); ivp: start the day from pi0 carried through hours
-        0 .. T-2 (the expected solve_ivp).  want_next: also return pi after the day's last operator."""
+        0 .. T-2 (the expected solve_ivp).  want_next: also return pi after the day's last operator.  sparse: straight from the
+        compact rows of sparse tables (include/cpm_expected_sparse.h): the same bits, the dense p_destin array neither read nor built."""
         a = self._pi0(pi0)
         parking = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
         driving = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
         nxt = np.zeros(self.Z, dtype=np.float64) if want_next else None
-        _lib.check(self._L.cpm_expected(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(parking), _vp(driving), _vp(nxt)))
+        call = self._L.cpm_expected_sparse if sparse else self._L.cpm_expected
+        _lib.check(call(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(parking), _vp(driving), _vp(nxt)))
         return (parking, driving, nxt) if want_next else (parking, driving)
 
-    def expected_batch(self, pi0=None, ivp=False):
+    def expected_batch(self, pi0=None, ivp=False, sparse=False):
         """The same for every fleet of the installed batch tables: (parking_density, driving_density), each (Z, T, B); fleet b bit
-        for bit expected() with p_drive[:, :, b] installed."""
+        for bit expected() with p_drive[:, :, b] installed.  sparse: as in expected()."""
         a = self._pi0(pi0)
         B = self.get_info(_lib.CPM_INFO_BATCH)
         parking = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
         driving = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
-        _lib.check(self._L.cpm_expected_batch(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(parking), _vp(driving)))
+        call = self._L.cpm_expected_sparse_batch if sparse else self._L.cpm_expected_batch
+        _lib.check(call(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(parking), _vp(driving)))
         return parking, driving
 
     def expected_words(self):
         """float64 words of one fleet's expected_dev tensor: 2*T*Z (parking[T][Z], then driving[T][Z])."""
         return 2 * self.T * self.Z
 
-    def expected_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False, d_pi_next_ptr=0):
+    def expected_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False, d_pi_next_ptr=0, sparse=False):
         """Enqueue on the context's stream: d_out_ptr = device address of float64[expected_words()]; d_pi0_ptr = device address of
         float64[Z] or 0 (uniform); d_pi_next_ptr = device address of float64[Z] or 0.  (The first call after the p_destin tables
-        changed builds its per-table arrays and synchronises once.)"""
-        _lib.check(self._L.cpm_expected_dev(self._h, C.c_void_p(int(d_pi0_ptr)) if d_pi0_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
-                                            C.c_void_p(int(d_out_ptr)) if d_out_ptr else None,
-                                            C.c_void_p(int(d_pi_next_ptr)) if d_pi_next_ptr else None))
+        changed builds its per-table arrays and synchronises once.)  sparse: cpm_expected_sparse_dev, as in expected()."""
+        call = self._L.cpm_expected_sparse_dev if sparse else self._L.cpm_expected_dev
+        _lib.check(call(self._h, C.c_void_p(int(d_pi0_ptr)) if d_pi0_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
+                        C.c_void_p(int(d_out_ptr)) if d_out_ptr else None, C.c_void_p(int(d_pi_next_ptr)) if d_pi_next_ptr else None))
 
-    def expected_batch_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False):
-        """Enqueue on the context's stream: d_out_ptr = device address of float64[B][expected_words()] for the installed batch tables."""
-        _lib.check(self._L.cpm_expected_batch_dev(self._h, C.c_void_p(int(d_pi0_ptr)) if d_pi0_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
-                                                  C.c_void_p(int(d_out_ptr)) if d_out_ptr else None))
+    def expected_batch_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False, sparse=False):
+        """Enqueue on the context's stream: d_out_ptr = device address of float64[B][expected_words()] for the installed batch tables.
+        sparse: cpm_expected_sparse_batch_dev, as in expected()."""
+        call = self._L.cpm_expected_sparse_batch_dev if sparse else self._L.cpm_expected_batch_dev
+        _lib.check(call(self._h, C.c_void_p(int(d_pi0_ptr)) if d_pi0_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
+                        C.c_void_p(int(d_out_ptr)) if d_out_ptr else None))
+
+    def expected_sparse_aux(self, sparse=True):
+        """Test aid (cpm_expected_sparse_aux): (ell, r, start, list) of the installed tables as the sparse (True) or the dense builder
+        left them: int32 (T, Z), float64 (T, Z), int32 (T, Z + 1), int32 (T, Z)."""
+        ell = np.zeros((self.T, self.Z), dtype=np.int32)
+        r = np.zeros((self.T, self.Z), dtype=np.float64)
+        start = np.zeros((self.T, self.Z + 1), dtype=np.int32)
+        lst = np.zeros((self.T, self.Z), dtype=np.int32)
+        _lib.check(self._L.cpm_expected_sparse_aux(self._h, 1 if sparse else 0, _vp(ell), _vp(r), _vp(start), _vp(lst)))
+        return ell, r, start, lst
 
     # -- expected travel time and distance (include/cpm_expected_travel.h): the trip weights of the tables, times the driving density --
     def expected_trip(self):

@@ -153,6 +153,10 @@ int32_t cpm_set_option(cpm_ctx *ctx, int32_t option, int64_t value);
                                     * came), 1 the travel rows of the dataset route's compact rows (csrc/cpm_dataset.h: fixed stride), 2 sparse
                                     * rows built from the datamatrix itself (a row's cells fit 32 KB of LDS), 3 the dense table the kernel
                                     * gathers from.  The travel times do not depend on it */
+#define CPM_INFO_P_DENSE 13        /* 1 when the dense [T][Z][Z] p_destin array is resident on the device and valid for the installed tables, else 0:
+                                    * always 1 for tables with dense packs and for an uploaded table; for the tables cpm_build_p_dest makes from
+                                    * compact rows, 0 until something expands them (the caller's own out array, cpm_get_cdf_row, the f64-row
+                                    * kernels, the cpm_expected* family).  Read-only; include/cpm_expected_sparse.h never changes it */
 /* Which INSTANTIATION of the grouped path's hourly kernels the most recent step launched, one word per role, written by the innermost
  * launch helper from its own template parameters (host memory only; committed as CPM_INFO_LAST_FORM is: a repeated attempt overwrites
  * it, an asynchronous IVP's is published when the IVP is committed, batch steps write their own).  0: the step had no such launch.
