@@ -84,6 +84,12 @@ CPM_TANGENT_MAX_DIRECTIONS = 16  # K of one expected_tangent call
 EXPECTED_SPARSE_SYMBOLS = ["cpm_expected_sparse_dev", "cpm_expected_sparse_batch_dev", "cpm_expected_sparse", "cpm_expected_sparse_batch",
                            "cpm_expected_sparse_aux"]
 
+# every symbol include/cpm_expected_sparse_grad.h declares (checked by tests/test_expected_sparse_grad.py); a header and a list of its own, likewise
+EXPECTED_SPARSE_GRAD_SYMBOLS = ["cpm_expected_sparse_grad_dev", "cpm_expected_sparse_grad", "cpm_expected_sparse_grad_batch_dev",
+                                "cpm_expected_sparse_grad_batch", "cpm_expected_sparse_trip_dev", "cpm_expected_sparse_trip",
+                                "cpm_expected_sparse_travel_dev", "cpm_expected_sparse_travel", "cpm_expected_sparse_travel_batch",
+                                "cpm_expected_sparse_fit_dev", "cpm_expected_sparse_fit"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -140,6 +146,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_fit.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_tangent.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_sparse.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_sparse_grad.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -236,6 +243,17 @@ def load():
     L.cpm_expected_sparse.argtypes = [vp, vp, u32, vp, vp, vp]
     L.cpm_expected_sparse_batch.argtypes = [vp, vp, u32, vp, vp]
     L.cpm_expected_sparse_aux.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.cpm_expected_sparse_grad_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    L.cpm_expected_sparse_grad.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    L.cpm_expected_sparse_grad_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    L.cpm_expected_sparse_grad_batch.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    L.cpm_expected_sparse_trip_dev.argtypes = [vp, vp]
+    L.cpm_expected_sparse_trip.argtypes = [vp, vp, vp]
+    L.cpm_expected_sparse_travel_dev.argtypes = [vp, vp, i32, vp, vp]
+    L.cpm_expected_sparse_travel.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.cpm_expected_sparse_travel_batch.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.cpm_expected_sparse_fit_dev.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.cpm_expected_sparse_fit.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     L.cpm_expected_trip_dev.argtypes = [vp, vp]
     L.cpm_expected_trip.argtypes = [vp, vp, vp]
     L.cpm_expected_travel_dev.argtypes = [vp, vp, i32, vp, vp]
@@ -264,7 +282,7 @@ def load():
     L.cpm_build_p_drive_tangent.argtypes = [vp, dbl, dbl, dbl, vp]
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
                  + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS + EXPECTED_GRAD_BATCH_SYMBOLS
-                 + EXPECTED_FIT_SYMBOLS + EXPECTED_TANGENT_SYMBOLS + EXPECTED_SPARSE_SYMBOLS):
+                 + EXPECTED_FIT_SYMBOLS + EXPECTED_TANGENT_SYMBOLS + EXPECTED_SPARSE_SYMBOLS + EXPECTED_SPARSE_GRAD_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

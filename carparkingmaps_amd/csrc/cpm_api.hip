@@ -28,6 +28,7 @@
 #include "../../include/cpm_expected_fit.h"
 #include "../../include/cpm_expected_tangent.h"
 #include "../../include/cpm_expected_sparse.h"
+#include "../../include/cpm_expected_sparse_grad.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -51,6 +52,7 @@
 #include "cpm_expected_fit.h"
 #include "cpm_expected_tangent.h"
 #include "cpm_expected_sparse.h"
+#include "cpm_expected_sparse_grad.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -284,6 +286,10 @@ struct cpm_ctx {
     DevBuf<double> d_exp_wpart;         // [segments][2][T][Z] the destination segments' sums
     bool exp_trip_valid = false;
     int64_t exp_trip_builds = 0;
+    // ... and the same weights from the compact rows (include/cpm_expected_sparse_grad.h): a cache of their own, so that a sparse call
+    // never changes what a later dense call returns; stale wherever exp_trip_valid or exps_valid is
+    DevBuf<double> d_exps_w;            // [2][T][Z] w_sec | w_km
+    bool exps_trip_valid = false;
     DevBuf<double> d_exp_trav;          // [B][2][T][Z] + [B][2]: the blocking calls' seconds | km and totals, B = cap / (2 T Z + 2)
     DevBuf<double> d_exp_tpart;         // [B][chunks][2] the chunks' sums of k_exp_travel, added in order by k_exp_travel_total
     // the adjoint of the expected densities (include/cpm_expected_grad.h, cpm_expected_grad.h)
@@ -417,7 +423,7 @@ int32_t build_rows(cpm_ctx *c, bool with_cdf)
     c->have_cdf = false;
     c->exp_aux_valid = false;
     c->exps_valid = false;
-    c->exp_trip_valid = false;
+    c->exp_trip_valid = c->exps_trip_valid = false;
     c->cdf_full = false;
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     if (!c->d_ckpt) HIP_TRY(hipMalloc(&c->d_ckpt, sizeof(double) * static_cast<size_t>(rows) * cpm::ckpt_count(static_cast<int>(c->Z))));
@@ -679,7 +685,7 @@ int32_t build_p_dest_sparse(cpm_ctx *c, double e_dest, int32_t e_is_integer, boo
     c->cdf_full = false;
     c->exp_aux_valid = false;
     c->exps_valid = false;
-    c->exp_trip_valid = false;
+    c->exp_trip_valid = c->exps_trip_valid = false;
     hipLaunchKernelGGL(cpm::k_ds_pdest, dim3(cpm::ds_grid(rows)), dim3(cpm::kDsThreads * cpm::kDsRows), 0, c->stream, c->d_ds_cells, c->d_ds_cnt, cpm::kDsCap,
                        rows, static_cast<int>(c->Z), e_dest, e_is_integer, nc, zq_c, g_c, c->d_hi, c->d_last, c->d_sp, c->d_sj, c->d_scnt, c->d_err);
     HIP_TRY(hipGetLastError());
@@ -706,7 +712,7 @@ int32_t pack_uploaded_rows(cpm_ctx *c, int nc)
     const int zq_c = cpm::pack_zq(nc), g_c = cpm::pack_guide_bits(nc);
     c->exp_aux_valid = false;
     c->exps_valid = false;
-    c->exp_trip_valid = false;
+    c->exp_trip_valid = c->exps_trip_valid = false;
     if (!c->d_last) HIP_TRY(hipMalloc(&c->d_last, sizeof(double) * static_cast<size_t>(rows)));
     int32_t rc = ensure_hi(c, static_cast<size_t>(rows) * cpm::pack_row_words(zq_c, g_c, 1));
     if (rc != CPM_OK) return rc;
@@ -1297,15 +1303,20 @@ int32_t ensure_exp_aux(cpm_ctx *c)
     return CPM_OK;
 }
 
+int32_t exps_no_rows()
+{
+    return fail(CPM_ERR_STATE, "expected_sparse: the installed p_destin tables have no compact rows (cpm_build_p_dest on a sparse datamatrix, or "
+                               "cpm_set_p_dest under CPM_OPT_SPARSE_UPLOAD, produce them)");
+}
+
 // The same per-table arrays from the compact rows of sparse tables, and the rows' transpose (cpm_expected_sparse.h): once per table.
 // d_p is neither read nor built, and exp_aux_valid is left alone: launch_exp_hour reads d_p on the strength of ensure_exp_aux.
 // Synchronises once (the row-total check and the number of cells are read back).
 int32_t ensure_exps(cpm_ctx *c)
 {
-    if (!c->sparse_tables)
-        return fail(CPM_ERR_STATE, "expected_sparse: the installed p_destin tables have no compact rows (cpm_build_p_dest on a sparse datamatrix, or "
-                                   "cpm_set_p_dest under CPM_OPT_SPARSE_UPLOAD, produce them)");
+    if (!c->sparse_tables) return exps_no_rows();
     if (c->exps_valid) return CPM_OK;
+    c->exps_trip_valid = false;  // (the sparse trip weights read l and r: never older than these)
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     if (Z > cpm::kExpsMaxZ) return fail(CPM_ERR_STATE, "expected_sparse: more than %d zones", cpm::kExpsMaxZ);
     const int64_t nrows = static_cast<int64_t>(Z) * T;
@@ -1544,16 +1555,42 @@ int32_t ensure_exp_trip(cpm_ctx *c)
     return CPM_OK;
 }
 
-// seconds | km and the totals of B fleets from their expected tensors (enqueued); either output may be nullptr
-int32_t expected_travel_enqueue(cpm_ctx *c, const double *d_expected, int B, double *d_travel, double *d_totals)
+// The same weights from the compact rows in d_exps_w (cpm_expected_sparse_grad.h): d_p is neither read nor built, and neither
+// d_exp_w nor exp_trip_builds moves.  d_exp_wpart is scratch of either build: nothing reads it afterwards.
+int32_t ensure_exps_trip(cpm_ctx *c)
 {
-    int32_t rc = ensure_exp_trip(c);
+    int32_t rc = exp_tables_ready(c, "expected travel");
+    if (rc != CPM_OK) return rc;
+    if (!c->have_dmat) return fail(CPM_ERR_STATE, "expected travel: datamatrix not set (cpm_set_datamatrix, cpm_createdatamatrix_* or cpm_synth_datamatrix)");
+    if (!c->have_dist) return fail(CPM_ERR_STATE, "expected travel: distance matrix not set (cpm_set_distance* or the dist of cpm_set_datamatrix)");
+    if ((rc = ensure_exps(c)) != CPM_OK) return rc;  // (the row-total check; clears exps_trip_valid when it rebuilds)
+    if (c->exps_trip_valid) return CPM_OK;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t zt = static_cast<size_t>(Z) * T;
+    const int nseg = cpm::trip_segments(Z, T), seg_len = cpm::trip_segment_len(Z, nseg);
+    HIP_TRY(c->d_exps_w.reserve(2 * zt));
+    HIP_TRY(c->d_exp_wpart.reserve(2 * zt * nseg));
+    cpm::launch(cpm::k_exps_trip, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(T)), dim3(cpm::kExpsGradBlock), 0, c->stream, c->d_sp.get(),
+                c->d_sj.get(), c->d_scnt.get(), cpm::kDsCap, c->d_dm.get(), c->d_dist.get(), Z, T, seg_len, nseg, c->d_exp_wpart.get());
+    HIP_TRY(hipGetLastError());
+    cpm::launch(cpm::k_exp_trip_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream, c->d_exp_wpart.get(),
+                nseg, c->d_dm.get(), c->d_dist.get(), c->d_last, c->d_exps_ell.get(), c->d_exps_r.get(), Z, T, c->d_exps_w.get());
+    HIP_TRY(hipGetLastError());
+    c->exps_trip_valid = true;
+    return CPM_OK;
+}
+
+// seconds | km and the totals of B fleets from their expected tensors (enqueued); either output may be nullptr.  sparse: the weights
+// come from the compact rows (ensure_exps_trip).
+int32_t expected_travel_enqueue(cpm_ctx *c, const double *d_expected, int B, double *d_travel, double *d_totals, bool sparse = false)
+{
+    int32_t rc = sparse ? ensure_exps_trip(c) : ensure_exp_trip(c);
     if (rc != CPM_OK) return rc;
     const size_t zt = static_cast<size_t>(c->Z) * c->T;
     const int nchunk = static_cast<int>(nblk(static_cast<int64_t>(zt), cpm::kTravelChunk));
     if (d_totals) HIP_TRY(c->d_exp_tpart.reserve(2 * static_cast<size_t>(B) * nchunk));  // (a grow frees first: hipFree waits for its readers)
     cpm::launch(cpm::k_exp_travel, dim3(static_cast<unsigned>(nchunk), static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream, d_expected,
-                c->d_exp_w.get(), zt, d_travel, d_totals ? c->d_exp_tpart.get() : nullptr);
+                sparse ? c->d_exps_w.get() : c->d_exp_w.get(), zt, d_travel, d_totals ? c->d_exp_tpart.get() : nullptr);
     HIP_TRY(hipGetLastError());
     if (d_totals) {
         cpm::launch(cpm::k_exp_travel_total, dim3(static_cast<unsigned>(B)), dim3(64), 0, c->stream, c->d_exp_tpart.get(), nchunk, d_totals);
@@ -1564,11 +1601,11 @@ int32_t expected_travel_enqueue(cpm_ctx *c, const double *d_expected, int B, dou
 
 // the blocking calls: the propagation into d_exp_out, the product into d_exp_trav, then the copies
 int32_t expected_travel_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, int B, const double *pd, size_t q_stride, double *seconds, double *km,
-                                 double *totals)
+                                 double *totals, bool sparse = false)
 {
     int32_t rc = check_pi0(c, pi0);
     if (rc != CPM_OK) return rc;
-    if ((rc = ensure_exp_trip(c)) != CPM_OK) return rc;  // (first: a missing datamatrix is reported before any work is enqueued)
+    if ((rc = sparse ? ensure_exps_trip(c) : ensure_exp_trip(c)) != CPM_OK) return rc;  // (first: a missing datamatrix is reported before any work is enqueued)
     double *d_next = nullptr;
     if ((rc = ensure_exp_out(c, B, &d_next)) != CPM_OK) return rc;
     const size_t zt = static_cast<size_t>(c->Z) * c->T;
@@ -1576,9 +1613,9 @@ int32_t expected_travel_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, 
     double *d_pi0 = d_next + c->Z;
     double *d_tot = c->d_exp_trav + c->d_exp_trav.cap / (2 * zt + 2) * 2 * zt;  // (behind the tensors of the fleets it was last grown for)
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream));
-    rc = expected_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, c->d_exp_out, nullptr);
+    rc = expected_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, c->d_exp_out, nullptr, sparse);
     if (rc != CPM_OK) return rc;
-    rc = expected_travel_enqueue(c, c->d_exp_out, B, c->d_exp_trav, d_tot);
+    rc = expected_travel_enqueue(c, c->d_exp_out, B, c->d_exp_trav, d_tot, sparse);
     if (rc != CPM_OK) return rc;
     for (int b = 0; b < B; ++b) {
         HIP_TRY(hipMemcpyAsync(seconds + b * zt, c->d_exp_trav + b * 2 * zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
@@ -1590,14 +1627,33 @@ int32_t expected_travel_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, 
 }
 
 // ------------------------------------------------------------------ adjoint of the expected densities (include/cpm_expected_grad.h)
+// one backward product of the hour whose first row is `row`, from the compact rows (k_exps_grad_u; ensure_exps has run)
+void launch_exps_grad_u(cpm_ctx *c, size_t row, const double *mu, int Zs, int nseg, int seg_len, double *part)
+{
+    const int Z = static_cast<int>(c->Z);
+    cpm::launch(cpm::k_exps_grad_u, dim3(static_cast<unsigned>(Z)), dim3(cpm::kExpsGradBlock), 0, c->stream, c->d_sp + row * cpm::kDsCap,
+                c->d_sj + row * cpm::kDsCap, c->d_scnt + row, cpm::kDsCap, mu, Z, Zs, seg_len, nseg, part);
+}
+
+// ... of a pass of nf > 1 fleets (k_exps_grad_u_b<NB>)
+template <int NB>
+void launch_exps_grad_u_b(cpm_ctx *c, size_t row, const double *mu, int Zs, int nseg, int seg_len, int nf, double *part)
+{
+    const int Z = static_cast<int>(c->Z);
+    cpm::launch(cpm::k_exps_grad_u_b<NB>, dim3(static_cast<unsigned>(Z)), dim3(cpm::kExpsGradBlock), 0, c->stream, c->d_sp + row * cpm::kDsCap,
+                c->d_sj + row * cpm::kDsCap, c->d_scnt + row, cpm::kDsCap, mu, Z, Zs, seg_len, nseg, nf, part);
+}
+
 // The forward propagation with the kernels of expected_enqueue (B = 1; pi_s of every operator kept, operator N - 1 not applied: nothing
 // reads pi_N), then the N backward operators: enqueued on the context's stream.  cot: [2][T][Z]; gnext, grad_pi0: [Z] or nullptr;
 // grad_pd: [T][Z].
-int32_t expected_grad_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, const double *cot, const double *gnext, double *grad_pd, double *grad_pi0)
+// sparse: both halves read the compact rows (k_exps_hour, k_exps_grad_u) and the per-table arrays of ensure_exps.
+int32_t expected_grad_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, const double *cot, const double *gnext, double *grad_pd, double *grad_pi0,
+                              bool sparse = false)
 {
     int32_t rc = exp_tables_ready(c, "expected");
     if (rc != CPM_OK) return rc;
-    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
+    if ((rc = sparse ? ensure_exps(c) : ensure_exp_aux(c)) != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
     const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
@@ -1615,20 +1671,26 @@ int32_t expected_grad_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, c
     cpm::launch(cpm::k_exp_init, dim3(nblk(Z, cpm::kExpBlock), 1u), dim3(cpm::kExpBlock), 0, c->stream, d_pi0, pd, static_cast<size_t>(0), Z, Zs, ws_pi,
                 ws_x[0], static_cast<double *>(nullptr), static_cast<double *>(nullptr), static_cast<size_t>(0));
     HIP_TRY(hipGetLastError());
+    using Go = void (*)(cpm_ctx *, int, const double *, const double *, size_t, const double *, const double *, double *, double *, double *, double *, size_t,
+                        int, int);
+    const Go hour = sparse ? Go(launch_exps_hour<1>) : Go(launch_exp_hour<1>);
     for (int s = 0; s + 1 < steps; ++s) {
         const int t = hour_of(s), t_next = hour_of(s + 1);
-        launch_exp_hour<1>(c, t, pd + static_cast<size_t>(t) * Z, pd + static_cast<size_t>(t_next) * Z, 0, ws_pi + static_cast<size_t>(s) * Zs, ws_x[s & 1],
-                           ws_pi + static_cast<size_t>(s + 1) * Zs, ws_x[(s + 1) & 1], nullptr, nullptr, 0, Zs, 1);
+        hour(c, t, pd + static_cast<size_t>(t) * Z, pd + static_cast<size_t>(t_next) * Z, 0, ws_pi + static_cast<size_t>(s) * Zs, ws_x[s & 1],
+             ws_pi + static_cast<size_t>(s + 1) * Zs, ws_x[(s + 1) & 1], nullptr, nullptr, 0, Zs, 1);
         HIP_TRY(hipGetLastError());
     }
 
+    const int *const d_ell = sparse ? c->d_exps_ell.get() : c->d_exp_ell.get();
+    const double *const d_r = sparse ? c->d_exps_r.get() : c->d_exp_r.get();
     const double *mu = gnext;  // (nullptr: zero by construction, the product of the last operator is skipped)
     for (int s = steps - 1; s >= 0; --s) {
         const int t = hour_of(s), j = s - pre;
         const size_t row = static_cast<size_t>(t) * Z;
         if (mu) {
             const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg));
-            if (Z & 1) cpm::launch(cpm::k_exp_grad_u<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, mu, Z, Zs, seg_len, part);
+            if (sparse) launch_exps_grad_u(c, row, mu, Zs, nseg, seg_len, part);
+            else if (Z & 1) cpm::launch(cpm::k_exp_grad_u<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, mu, Z, Zs, seg_len, part);
             else cpm::launch(cpm::k_exp_grad_u<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, mu, Z, Zs, seg_len, part);
             HIP_TRY(hipGetLastError());
         }
@@ -1636,8 +1698,7 @@ int32_t expected_grad_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, c
         const double *gp = j >= 0 ? cot + static_cast<size_t>(j) * Z : nullptr;
         const double *gd = j >= 0 ? cot + zt + static_cast<size_t>(j) * Z : nullptr;
         cpm::launch(cpm::k_exp_grad_finish, dim3(nblk(Z, cpm::kFinishBlock)), dim3(cpm::kFinishBlock), 0, c->stream, part, nseg, Zs, c->d_last + row,
-                    c->d_exp_ell + row, c->d_exp_r + row, pd + row, ws_pi + static_cast<size_t>(s) * Zs, mu, gp, gd, Z, s < pre ? 1 : 0, mu_out,
-                    grad_pd + row);
+                    d_ell + row, d_r + row, pd + row, ws_pi + static_cast<size_t>(s) * Zs, mu, gp, gd, Z, s < pre ? 1 : 0, mu_out, grad_pd + row);
         HIP_TRY(hipGetLastError());
         mu = mu_out;
     }
@@ -1645,7 +1706,7 @@ int32_t expected_grad_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, c
 }
 
 int32_t expected_grad_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
-                               double *grad_pd, double *grad_pi0)
+                               double *grad_pd, double *grad_pi0, bool sparse = false)
 {
     const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T);
     int32_t rc = check_pi0(c, pi0);
@@ -1662,7 +1723,7 @@ int32_t expected_grad_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, co
     HIP_TRY(hipMemcpyAsync(d_cot + zt, g_driving, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
     if (g_next) HIP_TRY(hipMemcpyAsync(d_gnext, g_next, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
-    rc = expected_grad_enqueue(c, pi0 ? d_pi0 : nullptr, flags, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr);
+    rc = expected_grad_enqueue(c, pi0 ? d_pi0 : nullptr, flags, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr, sparse);
     if (rc != CPM_OK) return rc;
     HIP_TRY(hipMemcpyAsync(grad_pd, d_grad, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
     if (grad_pi0) HIP_TRY(hipMemcpyAsync(grad_pi0, d_gpi0, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
@@ -1789,18 +1850,21 @@ void launch_grad_u_b(cpm_ctx *c, const double *p_t, const double *dp_t, const do
 // likewise.
 // where the batched adjoint keeps what its two halves share: the workspace's vectors and the geometry of the segments
 struct GradBatchPlan {
+    bool sparse = false;  // both halves read the compact rows and the per-table arrays of ensure_exps (no tangent there)
     int Zs = 0, nseg = 0, seg_len = 0;
     size_t nb = 0;
     double *ws_pi = nullptr, *ws_x[2] = {nullptr, nullptr}, *ws_mu[2] = {nullptr, nullptr}, *part = nullptr, *part_dp = nullptr;
 };
 
 // the checks that can refuse and the workspace of B fleets (with_dest: the call runs along the tangent)
-int32_t grad_batch_plan(cpm_ctx *c, int B, bool with_dest, GradBatchPlan &pl)
+int32_t grad_batch_plan(cpm_ctx *c, int B, bool with_dest, GradBatchPlan &pl, bool sparse = false)
 {
     int32_t rc = exp_tables_ready(c, "expected");
     if (rc != CPM_OK) return rc;
+    if (sparse && with_dest) return fail(CPM_ERR_ARG, "expected_sparse: the p_destin tangent is a dense array: no sparse form reads it");
     if (with_dest && (rc = tangent_ready(c, "expected_grad_dest_batch")) != CPM_OK) return rc;
-    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
+    if ((rc = sparse ? ensure_exps(c) : ensure_exp_aux(c)) != CPM_OK) return rc;
+    pl.sparse = sparse;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
     const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
@@ -1838,7 +1902,8 @@ int32_t grad_batch_forward(cpm_ctx *c, const GradBatchPlan &pl, const double *d_
             const size_t w0 = static_cast<size_t>(f0) * Zs;
             using Go = void (*)(cpm_ctx *, int, const double *, const double *, size_t, const double *, const double *, double *, double *, double *, double *,
                                 size_t, int, int);
-            const Go go = nf > 4 ? Go(launch_exp_hour<8>) : nf > 2 ? Go(launch_exp_hour<4>) : nf > 1 ? Go(launch_exp_hour<2>) : Go(launch_exp_hour<1>);
+            const Go go = pl.sparse ? (nf > 4 ? Go(launch_exps_hour<8>) : nf > 2 ? Go(launch_exps_hour<4>) : nf > 1 ? Go(launch_exps_hour<2>) : Go(launch_exps_hour<1>))
+                                    : (nf > 4 ? Go(launch_exp_hour<8>) : nf > 2 ? Go(launch_exp_hour<4>) : nf > 1 ? Go(launch_exp_hour<2>) : Go(launch_exp_hour<1>));
             go(c, t, pd + f0 * q_stride + static_cast<size_t>(t) * Z, pd + f0 * q_stride + static_cast<size_t>(t_next) * Z, q_stride,
                ws_pi + static_cast<size_t>(s) * nb * Zs + w0, ws_x[s & 1] + w0, ws_pi + static_cast<size_t>(s + 1) * nb * Zs + w0, ws_x[(s + 1) & 1] + w0, nullptr,
                nullptr, 0, Zs, nf);
@@ -1861,11 +1926,14 @@ int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags,
     const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
     auto hour_of = [pre](int s) { return s < pre ? s : s - pre; };
 
+    const bool sparse = pl.sparse;  // (grad_dest == nullptr then: grad_batch_plan refused the tangent)
+    const int *const d_ell = sparse ? c->d_exps_ell.get() : c->d_exp_ell.get();
+    const double *const d_r = sparse ? c->d_exps_r.get() : c->d_exp_r.get();
     bool have_mu = gnext != nullptr;  // (false: zero by construction, the products of the last operator are skipped for every fleet)
     for (int s = steps - 1; s >= 0; --s) {
         const int t = hour_of(s), j = s - pre;
         const size_t row = static_cast<size_t>(t) * Z;
-        const double *p_t = c->d_p + row * Z, *dp_t = grad_dest ? c->d_tan + row * Z : nullptr;
+        const double *p_t = sparse ? nullptr : c->d_p + row * Z, *dp_t = grad_dest ? c->d_tan + row * Z : nullptr;
         const int acc = s < pre ? 1 : 0;
         for (int f0 = 0; f0 < B; f0 += cpm::kExpMaxNB) {
             const int nf = std::min(B - f0, cpm::kExpMaxNB);
@@ -1883,7 +1951,9 @@ int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags,
             if (nf == 1) {  // the B = 1 kernels: mu is one vector, the segments' sums are [nseg][Zs]
                 if (mu) {
                     const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg)), block(cpm::kExpBlock);
-                    if (dp_t) {
+                    if (sparse) {
+                        launch_exps_grad_u(c, row, mu, Zs, nseg, seg_len, part);
+                    } else if (dp_t) {
                         if (Z & 1) cpm::launch(cpm::k_exp_grad_dest_u<true>, grid, block, 0, c->stream, p_t, dp_t, mu, Z, Zs, seg_len, part, part_dp);
                         else cpm::launch(cpm::k_exp_grad_dest_u<false>, grid, block, 0, c->stream, p_t, dp_t, mu, Z, Zs, seg_len, part, part_dp);
                     } else {
@@ -1892,9 +1962,9 @@ int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags,
                     }
                 }
                 if (dest_t) cpm::launch(cpm::k_exp_grad_dest_finish, dim3(nblk(Z, cpm::kFinishBlock)), dim3(cpm::kFinishBlock), 0, c->stream, part, part_dp, nseg, Zs,
-                                        c->d_last + row, c->d_exp_ell + row, c->d_exp_r + row, q_t, pi_s, mu, gp, gd, Z, acc, mu_out, grad_t, dest_t);
+                                        c->d_last + row, d_ell + row, d_r + row, q_t, pi_s, mu, gp, gd, Z, acc, mu_out, grad_t, dest_t);
                 else cpm::launch(cpm::k_exp_grad_finish, dim3(nblk(Z, cpm::kFinishBlock)), dim3(cpm::kFinishBlock), 0, c->stream, part, nseg, Zs, c->d_last + row,
-                                 c->d_exp_ell + row, c->d_exp_r + row, q_t, pi_s, mu, gp, gd, Z, acc, mu_out, grad_t);
+                                 d_ell + row, d_r + row, q_t, pi_s, mu, gp, gd, Z, acc, mu_out, grad_t);
                 continue;
             }
             if (mu) {
@@ -1903,16 +1973,22 @@ int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags,
                     cpm::launch(cpm::k_exp_grad_pack_b, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(NB)), dim3(cpm::kExpBlock), 0, c->stream,
                                 gnext + static_cast<size_t>(f0) * Z, Z, NB, nf, packed);
                 }
-                using Go = void (*)(cpm_ctx *, const double *, const double *, const double *, int, int, int, int, double *, double *);
-                const Go go = NB == 8 ? Go(launch_grad_u_b<8>) : NB == 4 ? Go(launch_grad_u_b<4>) : Go(launch_grad_u_b<2>);
-                go(c, p_t, dp_t, mu, Zs, nseg, seg_len, nf, part, part_dp);
+                if (sparse) {
+                    using Gs = void (*)(cpm_ctx *, size_t, const double *, int, int, int, int, double *);
+                    const Gs gs = NB == 8 ? Gs(launch_exps_grad_u_b<8>) : NB == 4 ? Gs(launch_exps_grad_u_b<4>) : Gs(launch_exps_grad_u_b<2>);
+                    gs(c, row, mu, Zs, nseg, seg_len, nf, part);
+                } else {
+                    using Go = void (*)(cpm_ctx *, const double *, const double *, const double *, int, int, int, int, double *, double *);
+                    const Go go = NB == 8 ? Go(launch_grad_u_b<8>) : NB == 4 ? Go(launch_grad_u_b<4>) : Go(launch_grad_u_b<2>);
+                    go(c, p_t, dp_t, mu, Zs, nseg, seg_len, nf, part, part_dp);
+                }
             }
             const dim3 grid(nblk(Z, cpm::kFinishBlock), static_cast<unsigned>(NB)), block(cpm::kFinishBlock);
             const size_t mo_o = to_pi0 ? 1 : static_cast<size_t>(NB), mo_f = to_pi0 ? static_cast<size_t>(Z) : 1;
             const int fill = to_pi0 ? 0 : 1;
-            if (dest_t) cpm::launch(cpm::k_exp_grad_dest_finish_b, grid, block, 0, c->stream, part, part_dp, nseg, Zs, c->d_last + row, c->d_exp_ell + row,
-                                    c->d_exp_r + row, q_t, q_stride, pi_s, mu, NB, gp, gd, cot_stride, Z, nf, acc, mu_out, mo_o, mo_f, fill, grad_t, dest_t, zt);
-            else cpm::launch(cpm::k_exp_grad_finish_b, grid, block, 0, c->stream, part, nseg, Zs, c->d_last + row, c->d_exp_ell + row, c->d_exp_r + row, q_t,
+            if (dest_t) cpm::launch(cpm::k_exp_grad_dest_finish_b, grid, block, 0, c->stream, part, part_dp, nseg, Zs, c->d_last + row, d_ell + row,
+                                    d_r + row, q_t, q_stride, pi_s, mu, NB, gp, gd, cot_stride, Z, nf, acc, mu_out, mo_o, mo_f, fill, grad_t, dest_t, zt);
+            else cpm::launch(cpm::k_exp_grad_finish_b, grid, block, 0, c->stream, part, nseg, Zs, c->d_last + row, d_ell + row, d_r + row, q_t,
                              q_stride, pi_s, mu, NB, gp, gd, cot_stride, Z, nf, acc, mu_out, mo_o, mo_f, fill, grad_t, zt);
         }
         HIP_TRY(hipGetLastError());
@@ -1922,10 +1998,10 @@ int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags,
 }
 
 int32_t expected_grad_batch_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, int B, const double *pd, size_t q_stride, const double *cot,
-                                    const double *gnext, double *grad_pd, double *grad_pi0, double *grad_dest)
+                                    const double *gnext, double *grad_pd, double *grad_pi0, double *grad_dest, bool sparse = false)
 {
     GradBatchPlan pl;
-    int32_t rc = grad_batch_plan(c, B, grad_dest != nullptr, pl);
+    int32_t rc = grad_batch_plan(c, B, grad_dest != nullptr, pl, sparse);
     if (rc != CPM_OK) return rc;
     if ((rc = grad_batch_forward(c, pl, d_pi0, flags, B, pd, q_stride)) != CPM_OK) return rc;
     return grad_batch_backward(c, pl, flags, B, pd, q_stride, cot, gnext, grad_pd, grad_pi0, grad_dest);
@@ -1934,7 +2010,8 @@ int32_t expected_grad_batch_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t fl
 // the blocking forms: d_exp_gio holds [B][2][T][Z] cotangents, [B][Z] G_next, [B][T][Z] grad_p_drive, [B][Z] grad_pi0 and pi_0 [Z];
 // d_exp_gdio [B][T][Z] grad_dest.  what: the entry, as its error text names it.
 int32_t expected_grad_batch_blocking(cpm_ctx *c, const char *what, const double *pi0, uint32_t flags, int B, const double *pd, size_t q_stride,
-                                     const double *g_parking, const double *g_driving, const double *g_next, double *grad_pd, double *grad_pi0, double *grad_dest)
+                                     const double *g_parking, const double *g_driving, const double *g_next, double *grad_pd, double *grad_pi0, double *grad_dest,
+                                     bool sparse = false)
 {
     const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nb = static_cast<size_t>(B);
     int32_t rc = check_pi0(c, pi0);
@@ -1957,7 +2034,7 @@ int32_t expected_grad_batch_blocking(cpm_ctx *c, const char *what, const double 
     if (g_next) HIP_TRY(hipMemcpyAsync(d_gnext, g_next, sizeof(double) * nb * Z, hipMemcpyHostToDevice, c->stream));
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
     rc = expected_grad_batch_enqueue(c, pi0 ? d_pi0 : nullptr, flags, B, pd, q_stride, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr,
-                                     grad_dest ? c->d_exp_gdio.get() : nullptr);
+                                     grad_dest ? c->d_exp_gdio.get() : nullptr, sparse);
     if (rc != CPM_OK) return rc;
     HIP_TRY(hipMemcpyAsync(grad_pd, d_grad, sizeof(double) * nb * zt, hipMemcpyDeviceToHost, c->stream));
     if (grad_pi0) HIP_TRY(hipMemcpyAsync(grad_pi0, d_gpi0, sizeof(double) * nb * Z, hipMemcpyDeviceToHost, c->stream));
@@ -2089,17 +2166,19 @@ FitLayout fit_layout(const cpm_ctx *c, int B)
 }
 
 // The whole call, enqueued on the context's stream; fit_check has passed.  Outputs that are nullptr stay in the workspace.
+// sparse: the propagation, the trip weights (d_exps_w) and the adjoint read the compact rows; CPM_FIT_DEST is refused by the entries.
 int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const double *p_max, const double *e_drive, const double *d_pi0, uint32_t flags,
-                             const double *weights, double *d_record, double *d_expected, double *d_cot, double *d_grad_pd, double *d_grad_dest)
+                             const double *weights, double *d_record, double *d_expected, double *d_cot, double *d_grad_pd, double *d_grad_dest,
+                             bool sparse = false)
 {
     const bool dest = (flags & CPM_FIT_DEST) != 0;
     const uint32_t eflags = flags & CPM_EXPECT_IVP;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const size_t zt = static_cast<size_t>(Z) * T;
     GradBatchPlan pl;
-    int32_t rc = grad_batch_plan(c, B, dest, pl);
+    int32_t rc = grad_batch_plan(c, B, dest, pl, sparse);
     if (rc != CPM_OK) return rc;
-    if ((rc = ensure_exp_trip(c)) != CPM_OK) return rc;
+    if ((rc = sparse ? ensure_exps_trip(c) : ensure_exp_trip(c)) != CPM_OK) return rc;
     bool direct = false;
     for (int b = 0; b < B; ++b) direct = direct || (dest && weights[3 * b + 2] != 0.0);
     if (direct && (c->fit_dw_gen != c->tan_gen || c->fit_dw_builds != c->exp_trip_builds)) {
@@ -2146,7 +2225,7 @@ int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const doubl
     HIP_TRY(hipGetLastError());
 
     // (c) objectives and cotangents
-    if ((rc = expected_travel_enqueue(c, expected, B, nullptr, ws + l.totals)) != CPM_OK) return rc;
+    if ((rc = expected_travel_enqueue(c, expected, B, nullptr, ws + l.totals, sparse)) != CPM_OK) return rc;
     const double *meas = c->have_measured ? c->d_measured.get() : nullptr;
     const int *flag = c->have_measured ? c->d_meas_flag.get() : nullptr;
     hipLaunchKernelGGL(cpm::k_fit_zones, dim3(nbz, static_cast<unsigned>(B)), dim3(cpm::kExpBlock), sizeof(double) * cpm::kExpWaves * T, c->stream,
@@ -2159,7 +2238,8 @@ int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const doubl
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cpm::k_fit_cot, dim3(nbz, static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(expected), meas,
                        static_cast<const double *>(ws + l.zone), static_cast<const int *>(arg), static_cast<const double *>(ws + l.ga),
-                       static_cast<const double *>(ws + l.nval), static_cast<const double *>(c->d_exp_w.get()), static_cast<const double *>(w_dev), Z, T, B, cot);
+                       static_cast<const double *>(ws + l.nval), static_cast<const double *>(sparse ? c->d_exps_w.get() : c->d_exp_w.get()),
+                       static_cast<const double *>(w_dev), Z, T, B, cot);
     HIP_TRY(hipGetLastError());
 
     // (d) backward on that cotangent: G_next zero, grad_pi0 not wanted
@@ -2621,7 +2701,7 @@ int32_t cpm_set_datamatrix(cpm_ctx *c, const double *datamatrix, const double *d
     c->ds_valid = false;
     drop_dest_tangent(c);
     c->pdrive_mean_valid = false;
-    c->exp_trip_valid = false;
+    c->exp_trip_valid = c->exps_trip_valid = false;
     HIP_TRY(hipMemcpyAsync(c->d_dm, datamatrix, bytes, hipMemcpyHostToDevice, c->stream));
     if (dist) HIP_TRY(hipMemcpyAsync(c->d_dist, dist, dbytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2655,7 +2735,7 @@ static int32_t datamatrix_from_device_rows(cpm_ctx *c, const double *d_raw, int6
     c->ds_valid = false;
     drop_dest_tangent(c);
     c->pdrive_mean_valid = false;
-    c->exp_trip_valid = false;
+    c->exp_trip_valid = c->exps_trip_valid = false;
     HIP_TRY(hipMemsetAsync(c->d_dm, 0, sizeof(double) * cells * 2, c->stream));  // zeros(number_zones, number_zones, T, 2) (:7)
     if (n == 0) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2767,7 +2847,7 @@ int32_t cpm_set_distance_from_centroids(cpm_ctx *c, const double *centroid_lat, 
     if (!centroid_lat || !centroid_long) return fail(CPM_ERR_ARG, "null centroids");
     const size_t dbytes = sizeof(double) * c->Z * c->Z;
     HIP_TRY(c->d_dist.reserve(dbytes / sizeof(double)));
-    c->exp_trip_valid = false;  // (before the first byte changes: a copy that fails half way leaves no weights behind)
+    c->exp_trip_valid = c->exps_trip_valid = false;  // (before the first byte changes: a copy that fails half way leaves no weights behind)
     double *d_ll = nullptr;
     HIP_TRY(hipMalloc(&d_ll, sizeof(double) * 2 * c->Z));
     hipError_t e = hipMemcpyAsync(d_ll, centroid_lat, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream);
@@ -2783,7 +2863,7 @@ int32_t cpm_set_distance_from_centroids(cpm_ctx *c, const double *centroid_lat, 
     c->have_dist = true;
     c->dist_rows_valid = false;
     c->pdrive_mean_valid = false;
-    c->exp_trip_valid = false;
+    c->exp_trip_valid = c->exps_trip_valid = false;
     return CPM_OK;
 }
 
@@ -2793,13 +2873,13 @@ int32_t cpm_set_distance(cpm_ctx *c, const double *dist)
     if (!dist) return fail(CPM_ERR_ARG, "null dist");
     const size_t dbytes = sizeof(double) * c->Z * c->Z;
     HIP_TRY(c->d_dist.reserve(dbytes / sizeof(double)));
-    c->exp_trip_valid = false;  // (before the first byte changes: a copy that fails half way leaves no weights behind)
+    c->exp_trip_valid = c->exps_trip_valid = false;  // (before the first byte changes: a copy that fails half way leaves no weights behind)
     HIP_TRY(hipMemcpyAsync(c->d_dist, dist, dbytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_dist = true;
     c->dist_rows_valid = false;
     c->pdrive_mean_valid = false;
-    c->exp_trip_valid = false;
+    c->exp_trip_valid = c->exps_trip_valid = false;
     return CPM_OK;
 }
 
@@ -2971,7 +3051,7 @@ int32_t cpm_synth_datamatrix(cpm_ctx *c, uint64_t table_seed, double density)
     c->ds_valid = false;
     drop_dest_tangent(c);
     c->pdrive_mean_valid = false;
-    c->exp_trip_valid = false;
+    c->exp_trip_valid = c->exps_trip_valid = false;
     hipLaunchKernelGGL(cpm::k_synth_datamatrix, dim3(nblk(c->Z, 256), static_cast<unsigned>(c->Z), static_cast<unsigned>(c->T)), dim3(256), 0, c->stream,
                        c->d_dm, static_cast<int>(c->Z), static_cast<int>(c->T), table_seed, density);
     hipLaunchKernelGGL(cpm::k_synth_dist, dim3(nblk(c->Z, 256), static_cast<unsigned>(c->Z)), dim3(256), 0, c->stream, c->d_dist, static_cast<int>(c->Z),
@@ -3736,6 +3816,133 @@ int32_t cpm_expected_sparse_aux(cpm_ctx *c, int32_t sparse, int32_t *ell, double
     return CPM_OK;
 }
 
+// ------------------------------------------------------------------ the adjoint, the trip weights and the fit from the compact rows
+// (include/cpm_expected_sparse_grad.h): the namesakes' entries with sparse = true, and CPM_ERR_STATE without compact rows in front of
+// anything that is read, copied or enqueued
+static int32_t exps_rows_ready(const cpm_ctx *c, const char *what)
+{
+    int32_t rc = exp_tables_ready(c, what);
+    if (rc != CPM_OK) return rc;
+    return c->sparse_tables ? CPM_OK : exps_no_rows();
+}
+
+int32_t cpm_expected_sparse_grad_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext, void *d_grad_p_drive,
+                                     void *d_grad_pi0)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_sparse_grad_dev: null d_cotangent");
+    if (!d_grad_p_drive) return fail(CPM_ERR_ARG, "expected_sparse_grad_dev: null d_grad_p_drive");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected")) != CPM_OK) return rc;
+    return expected_grad_enqueue(c, static_cast<const double *>(d_pi0), flags, static_cast<const double *>(d_cotangent), static_cast<const double *>(d_gnext),
+                                 static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0), true);
+}
+
+int32_t cpm_expected_sparse_grad(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                                 double *grad_p_drive, double *grad_pi0)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_sparse_grad: null cotangents");
+    if (!grad_p_drive) return fail(CPM_ERR_ARG, "expected_sparse_grad: null grad_p_drive");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected")) != CPM_OK) return rc;
+    return expected_grad_blocking(c, pi0, flags, g_parking, g_driving, g_next, grad_p_drive, grad_pi0, true);
+}
+
+int32_t cpm_expected_sparse_grad_batch_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext, void *d_grad_p_drive,
+                                           void *d_grad_pi0)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_sparse_grad_batch_dev: null d_cotangent");
+    if (!d_grad_p_drive) return fail(CPM_ERR_ARG, "expected_sparse_grad_batch_dev: null d_grad_p_drive");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected")) != CPM_OK) return rc;
+    return expected_grad_batch_enqueue(c, static_cast<const double *>(d_pi0), flags, tb.B, tb.pd, tb.q_stride, static_cast<const double *>(d_cotangent),
+                                       static_cast<const double *>(d_gnext), static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0), nullptr,
+                                       true);
+}
+
+int32_t cpm_expected_sparse_grad_batch(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                                       double *grad_p_drive, double *grad_pi0)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_sparse_grad_batch: null cotangents");
+    if (!grad_p_drive) return fail(CPM_ERR_ARG, "expected_sparse_grad_batch: null grad_p_drive");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected")) != CPM_OK) return rc;  // (state is refused before a cotangent is read or copied)
+    return expected_grad_batch_blocking(c, "expected_sparse_grad_batch", pi0, flags, tb.B, tb.pd, tb.q_stride, g_parking, g_driving, g_next, grad_p_drive,
+                                        grad_pi0, nullptr, true);
+}
+
+int32_t cpm_expected_sparse_trip_dev(cpm_ctx *c, void *d_w)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_w) return fail(CPM_ERR_ARG, "expected_sparse_trip_dev: null d_w");
+    CTX_TRY(c);
+    if ((rc = exps_rows_ready(c, "expected travel")) != CPM_OK) return rc;
+    if ((rc = ensure_exps_trip(c)) != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(d_w, c->d_exps_w, sizeof(double) * 2 * c->Z * c->T, hipMemcpyDeviceToDevice, c->stream));
+    return CPM_OK;
+}
+
+int32_t cpm_expected_sparse_trip(cpm_ctx *c, double *w_sec, double *w_km)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!w_sec || !w_km) return fail(CPM_ERR_ARG, "expected_sparse_trip: null outputs");
+    CTX_TRY(c);
+    if ((rc = exps_rows_ready(c, "expected travel")) != CPM_OK) return rc;
+    if ((rc = ensure_exps_trip(c)) != CPM_OK) return rc;
+    const size_t zt = static_cast<size_t>(c->Z) * c->T;
+    HIP_TRY(hipMemcpyAsync(w_sec, c->d_exps_w, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(w_km, c->d_exps_w + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+int32_t cpm_expected_sparse_travel_dev(cpm_ctx *c, const void *d_expected, int32_t B, void *d_travel, void *d_totals)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_expected) return fail(CPM_ERR_ARG, "expected_sparse_travel_dev: null d_expected");
+    if (B < 1) return fail(CPM_ERR_ARG, "expected_sparse_travel_dev: B = %d", B);
+    if (!d_travel && !d_totals) return fail(CPM_ERR_ARG, "expected_sparse_travel_dev: d_travel and d_totals are both null");
+    CTX_TRY(c);
+    if ((rc = exps_rows_ready(c, "expected travel")) != CPM_OK) return rc;
+    return expected_travel_enqueue(c, static_cast<const double *>(d_expected), B, static_cast<double *>(d_travel), static_cast<double *>(d_totals), true);
+}
+
+int32_t cpm_expected_sparse_travel(cpm_ctx *c, const double *pi0, uint32_t flags, double *seconds, double *km, double *totals)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!seconds || !km) return fail(CPM_ERR_ARG, "expected_sparse_travel: null outputs");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected travel")) != CPM_OK) return rc;
+    return expected_travel_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, seconds, km, totals, true);
+}
+
+int32_t cpm_expected_sparse_travel_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double *seconds, double *km, double *totals)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!seconds || !km) return fail(CPM_ERR_ARG, "expected_sparse_travel_batch: null outputs");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected travel")) != CPM_OK) return rc;
+    return expected_travel_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, seconds, km, totals, true);
+}
+
 // ------------------------------------------------------------------ expected travel (include/cpm_expected_travel.h)
 
 int32_t cpm_expected_trip_dev(cpm_ctx *c, void *d_w)
@@ -4017,20 +4224,18 @@ int32_t cpm_expected_fit_dev(cpm_ctx *c, int32_t B, const double *p_min, const d
                                 static_cast<double *>(d_grad_dest));
 }
 
-int32_t cpm_expected_fit(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive, const double *pi0, uint32_t flags,
-                         const double *weights, double *record, double *expected, double *cotangent, double *grad_p_drive, double *grad_dest)
+// the blocking call behind its checks: pi_0 up, the call into the workspace, the outputs the caller wants down
+static int32_t expected_fit_blocking(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive, const double *pi0, uint32_t flags,
+                              const double *weights, double *record, double *expected, double *cotangent, double *grad_p_drive, double *grad_dest, bool sparse)
 {
-    int32_t rc = exp_enter(c);
+    int32_t rc = check_pi0(c, pi0);
     if (rc != CPM_OK) return rc;
-    if ((rc = fit_check(c, "expected_fit", B, p_min, p_max, e_drive, flags, weights, record)) != CPM_OK) return rc;
-    if (grad_dest && !(flags & CPM_FIT_DEST)) return fail(CPM_ERR_ARG, "expected_fit: grad_dest without CPM_FIT_DEST");
-    if ((rc = check_pi0(c, pi0)) != CPM_OK) return rc;
     const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nb = static_cast<size_t>(B);
     const size_t rec_words = nb * static_cast<size_t>(cpm::kFitWords + c->T);
     HIP_TRY(c->d_fit_rec.reserve(rec_words + Z));
     double *d_pi0 = c->d_fit_rec + (c->d_fit_rec.cap - Z);  // (pi_0 ends the allocation)
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
-    rc = expected_fit_enqueue(c, B, p_min, p_max, e_drive, pi0 ? d_pi0 : nullptr, flags, weights, c->d_fit_rec, nullptr, nullptr, nullptr, nullptr);
+    rc = expected_fit_enqueue(c, B, p_min, p_max, e_drive, pi0 ? d_pi0 : nullptr, flags, weights, c->d_fit_rec, nullptr, nullptr, nullptr, nullptr, sparse);
     if (rc != CPM_OK) return rc;
     const FitLayout l = fit_layout(c, B);
     const double *ws = c->d_fit_ws;
@@ -4041,6 +4246,47 @@ int32_t cpm_expected_fit(cpm_ctx *c, int32_t B, const double *p_min, const doubl
     if (grad_dest && (flags & CPM_FIT_DEST)) HIP_TRY(hipMemcpyAsync(grad_dest, ws + l.grad_dest, sizeof(double) * nb * zt, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
+}
+
+int32_t cpm_expected_fit(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive, const double *pi0, uint32_t flags,
+                         const double *weights, double *record, double *expected, double *cotangent, double *grad_p_drive, double *grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = fit_check(c, "expected_fit", B, p_min, p_max, e_drive, flags, weights, record)) != CPM_OK) return rc;
+    if (grad_dest && !(flags & CPM_FIT_DEST)) return fail(CPM_ERR_ARG, "expected_fit: grad_dest without CPM_FIT_DEST");
+    return expected_fit_blocking(c, B, p_min, p_max, e_drive, pi0, flags, weights, record, expected, cotangent, grad_p_drive, grad_dest, false);
+}
+
+// ... from the compact rows (include/cpm_expected_sparse_grad.h): the e_dest direction needs the p_destin tangent, a dense array
+static int32_t fit_sparse_check(cpm_ctx *c, const char *what, int32_t B, const double *p_min, const double *p_max, const double *e_drive, uint32_t flags,
+                         const double *weights, const void *record, const void *grad_dest)
+{
+    if (flags & CPM_FIT_DEST)
+        return fail(CPM_ERR_ARG, "%s: CPM_FIT_DEST: the p_destin tangent is a dense [T][Z][Z] array, which the sparse calls never read (cpm_expected_fit)", what);
+    int32_t rc = fit_check(c, what, B, p_min, p_max, e_drive, flags, weights, record);
+    if (rc != CPM_OK) return rc;
+    if (grad_dest) return fail(CPM_ERR_ARG, "%s: grad_dest without CPM_FIT_DEST", what);
+    return exps_rows_ready(c, what);
+}
+
+int32_t cpm_expected_sparse_fit_dev(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive, const void *d_pi0, uint32_t flags,
+                                    const double *weights, void *d_record, void *d_expected, void *d_cotangent, void *d_grad_p_drive, void *d_grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = fit_sparse_check(c, "expected_sparse_fit_dev", B, p_min, p_max, e_drive, flags, weights, d_record, d_grad_dest)) != CPM_OK) return rc;
+    return expected_fit_enqueue(c, B, p_min, p_max, e_drive, static_cast<const double *>(d_pi0), flags, weights, static_cast<double *>(d_record),
+                                static_cast<double *>(d_expected), static_cast<double *>(d_cotangent), static_cast<double *>(d_grad_p_drive), nullptr, true);
+}
+
+int32_t cpm_expected_sparse_fit(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive, const double *pi0, uint32_t flags,
+                                const double *weights, double *record, double *expected, double *cotangent, double *grad_p_drive, double *grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = fit_sparse_check(c, "expected_sparse_fit", B, p_min, p_max, e_drive, flags, weights, record, grad_dest)) != CPM_OK) return rc;
+    return expected_fit_blocking(c, B, p_min, p_max, e_drive, pi0, flags, weights, record, expected, cotangent, grad_p_drive, nullptr, true);
 }
 
 // ------------------------------------------------------------------ forward tangent of the expected densities (include/cpm_expected_tangent.h)

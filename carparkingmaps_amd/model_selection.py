@@ -269,7 +269,15 @@ class Point:
 
 @dataclass
 class Evaluator:
-    """Holds a Sampler whose datamatrix is uploaded and whose car state is the post-IVP state."""
+    """Holds a Sampler whose datamatrix is uploaded and whose car state is the post-IVP state.
+
+    expected_sparse=True runs the noise-free calls from the compact rows of sparse tables, with the bits of the default Evaluator and
+    without ever building the dense p_destin array: evaluate_expected[_batch] (propagation and travel product), and
+    expected_gradient[_batch], expected_fit and refine_expected with dest=False.  With dest=True, and in expected_jacobian and
+    refine_expected_lm, the adjoint, the trip weights and the fit are the dense calls as before: the tangent of p_destin is a dense
+    array.  The bits are the default Evaluator's on one condition (include/cpm_expected_sparse_grad.h): every mean of the datamatrix
+    and every distance at a cell p_destin does NOT store is finite.  The dense trip weights form 0 * value there, so a NaN mean at
+    a cell of zero count makes the default Evaluator's travel product, A_drive and their gradients NaN where the sparse ones are not."""
     sampler: object
     C: int
     seed: int
@@ -278,7 +286,13 @@ class Evaluator:
     travel: bool = True
     fallbacks: int = 0      # pipelined points whose asynchronous step overflowed a bucket region and were evaluated again, blocking
     device_objectives: bool = False   # reduce the counts on the device (include/cpm_objectives.h): the host reads 4 + 2*T words per point
-    expected_sparse: bool = False     # evaluate_expected[_batch] propagate from the compact rows of sparse tables (include/cpm_expected_sparse.h): same bits
+    # expected_sparse: evaluate_expected[_batch] (propagation and travel product), and expected_gradient[_batch], expected_fit and so
+    # refine_expected with dest=False, run from the compact rows of sparse tables (include/cpm_expected_sparse.h,
+    # include/cpm_expected_sparse_grad.h): same bits where the means and distances at cells that are not stored are finite (the class
+    # docstring), and the dense p_destin array is never built.  With dest=True, and in
+    # expected_jacobian / refine_expected_lm, the adjoint, the trip weights and the fit are the dense calls as before: the tangent of
+    # p_destin is a dense array.
+    expected_sparse: bool = False
     _e_dest: object = field(default=None, repr=False)
     _pipe: object = field(default=None, repr=False)
     _s_table: object = field(default=None, repr=False)   # build_p_drive(0, 1, 1): the datamatrix's own table, for expected_gradient
@@ -341,7 +355,7 @@ class Evaluator:
             s.expected_batch_dev(out.data_ptr(), 0, ivp, sparse=self.expected_sparse)
         else:
             s.expected_dev(out.data_ptr(), 0, ivp, sparse=self.expected_sparse)
-        s.expected_travel_dev(out.data_ptr(), B, 0, tot.data_ptr())
+        s.expected_travel_dev(out.data_ptr(), B, 0, tot.data_ptr(), sparse=self.expected_sparse)
         s.sync()
         both = out.cpu().numpy().reshape(B, 2, s.T, s.Z)
         totals = tot.cpu().numpy().reshape(B, 2)
@@ -396,12 +410,12 @@ class Evaluator:
                 raise ValueError("expected_gradient: parking_error needs measured_parking")
             gp, gd = parking_density_error_grad(r["parking"], self.measured_parking), zero
         else:
-            gp, gd = zero, a_drive_grad(s.expected_trip()[0])
+            gp, gd = zero, a_drive_grad(s.expected_trip(sparse=self.expected_sparse and not dest)[0])
         if dest:
             self._install_dest_tangent()
             g = s.expected_grad_dest(gp, gd, ivp=ivp)
         else:
-            g = s.expected_grad(gp, gd, ivp=ivp)
+            g = s.expected_grad(gp, gd, ivp=ivp, sparse=self.expected_sparse)
         d_min, d_max, d_e = p_drive_param_grads(g["grad_p_drive"], self._s_table, pt.p_min, pt.p_max, pt.e_drive)
         out = dict(objective=objective, value=r[objective], grad_p_drive=g["grad_p_drive"], grad_pi0=g["grad_pi0"],
                    d_p_min=d_min, d_p_max=d_max, d_e_drive=d_e)
@@ -432,7 +446,8 @@ class Evaluator:
         B = len(pts)
         gp = np.zeros((s.Z, s.T, B), order="F")
         gd = np.zeros((s.Z, s.T, B), order="F")
-        w_sec = s.expected_trip()[0] if objective == "A_drive" else None
+        sparse = self.expected_sparse and not dest
+        w_sec = s.expected_trip(sparse=sparse)[0] if objective == "A_drive" else None
         for b, r in enumerate(rs):
             if objective == "activity_error":
                 gd[:, :, b] = traffic_activity_error_grad(r["driving"], self.measured_activity)
@@ -442,7 +457,7 @@ class Evaluator:
                 gd[:, :, b] = a_drive_grad(w_sec)
         if dest:
             self._install_dest_tangent()
-        g = s.expected_grad_batch(gp, gd, ivp=ivp, dest=dest)
+        g = s.expected_grad_batch(gp, gd, ivp=ivp, dest=dest, sparse=sparse)
         direct = dest and objective == "A_drive"
         dw_sec = s.expected_trip_tangent()[0] if direct else None
         outs = []
@@ -479,7 +494,8 @@ class Evaluator:
         B, words = len(pts), s.fit_words()
         rec = torch.empty(B * words, dtype=torch.float64, device=f"cuda:{s.device}")
         torch.cuda.synchronize(s.device)
-        s.expected_fit_dev([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts], w, rec.data_ptr(), 0, ivp, dest)
+        s.expected_fit_dev([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts], w, rec.data_ptr(), 0, ivp, dest,
+                           sparse=self.expected_sparse and not dest)
         s.sync()
         r = s.fit_record(rec.cpu().numpy(), s.T)
         outs = []

@@ -603,12 +603,15 @@ class Sampler:
         return ell, r, start, lst
 
     # -- expected travel time and distance (include/cpm_expected_travel.h): the trip weights of the tables, times the driving density --
-    def expected_trip(self):
+    def expected_trip(self, sparse=False):
         """(w_sec, w_km), each (Z, T) float64 F-order: the expected seconds and kilometres of ONE trip that starts in zone o in hour
-        t, from the installed p_destin tables, datamatrix and distance matrix alone.  Cached in the context until one of them changes."""
+        t, from the installed p_destin tables, datamatrix and distance matrix alone.  Cached in the context until one of them changes.
+        sparse: from the compact rows of sparse tables (include/cpm_expected_sparse_grad.h): the same bits where the means and
+        distances are finite, the dense p_destin array neither read nor built; a cache of its own."""
         w_sec = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
         w_km = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
-        _lib.check(self._L.cpm_expected_trip(self._h, _vp(w_sec), _vp(w_km)))
+        call = self._L.cpm_expected_sparse_trip if sparse else self._L.cpm_expected_trip
+        _lib.check(call(self._h, _vp(w_sec), _vp(w_km)))
         return w_sec, w_km
 
     def expected_trip_builds(self):
@@ -618,64 +621,74 @@ class Sampler:
             _lib.check(n)
         return n
 
-    def expected_travel(self, pi0=None, ivp=False):
+    def expected_travel(self, pi0=None, ivp=False, sparse=False):
         """The expected travel of a fleet, blocking: dict(seconds, km: (Z, T) float64 F-order, the driving density of expected() times
         the trip weights; total_seconds, total_km; A_drive = total_seconds / (T * 3600), the noise-free share of the day a car
-        drives).  C * seconds[z, t] is the expected travel-time sum of the cars that leave z in hour t of resample(travel=True)."""
+        drives).  C * seconds[z, t] is the expected travel-time sum of the cars that leave z in hour t of resample(travel=True).
+        sparse: as in expected_trip(), its condition on the means and distances included; the propagation is expected(sparse=True)'s."""
         a = self._pi0(pi0)
         seconds = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
         km = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
         totals = np.zeros(2, dtype=np.float64)
-        _lib.check(self._L.cpm_expected_travel(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(seconds), _vp(km), _vp(totals)))
+        call = self._L.cpm_expected_sparse_travel if sparse else self._L.cpm_expected_travel
+        _lib.check(call(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(seconds), _vp(km), _vp(totals)))
         return dict(seconds=seconds, km=km, total_seconds=float(totals[0]), total_km=float(totals[1]),
                     A_drive=float(totals[0]) / (self.T * 3600.0))
 
-    def expected_travel_batch(self, pi0=None, ivp=False):
+    def expected_travel_batch(self, pi0=None, ivp=False, sparse=False):
         """The same for every fleet of the installed batch tables: seconds, km (Z, T, B) and total_seconds, total_km, A_drive (B,);
-        fleet b bit for bit expected_travel() with p_drive[:, :, b] installed."""
+        fleet b bit for bit expected_travel() with p_drive[:, :, b] installed.  sparse: as in expected_travel()."""
         a = self._pi0(pi0)
         B = self.get_info(_lib.CPM_INFO_BATCH)
         seconds = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
         km = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
         totals = np.zeros((B, 2), dtype=np.float64)
-        _lib.check(self._L.cpm_expected_travel_batch(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(seconds), _vp(km), _vp(totals)))
+        call = self._L.cpm_expected_sparse_travel_batch if sparse else self._L.cpm_expected_travel_batch
+        _lib.check(call(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(seconds), _vp(km), _vp(totals)))
         return dict(seconds=seconds, km=km, total_seconds=totals[:, 0].copy(), total_km=totals[:, 1].copy(),
                     A_drive=totals[:, 0] / (self.T * 3600.0))
 
-    def expected_trip_dev(self, d_w_ptr):
-        """Enqueue on the context's stream: d_w_ptr = device address of float64[2][T][Z], w_sec then w_km."""
-        _lib.check(self._L.cpm_expected_trip_dev(self._h, C.c_void_p(int(d_w_ptr)) if d_w_ptr else None))
+    def expected_trip_dev(self, d_w_ptr, sparse=False):
+        """Enqueue on the context's stream: d_w_ptr = device address of float64[2][T][Z], w_sec then w_km.  sparse: as in
+        expected_trip()."""
+        call = self._L.cpm_expected_sparse_trip_dev if sparse else self._L.cpm_expected_trip_dev
+        _lib.check(call(self._h, C.c_void_p(int(d_w_ptr)) if d_w_ptr else None))
 
-    def expected_travel_dev(self, d_expected_ptr, B, d_travel_ptr=0, d_totals_ptr=0):
+    def expected_travel_dev(self, d_expected_ptr, B, d_travel_ptr=0, d_totals_ptr=0, sparse=False):
         """Enqueue on the context's stream: d_expected_ptr = device address of float64[B][expected_words()] as expected_dev /
         expected_batch_dev wrote it (only the driving halves are read); d_travel_ptr = device address of float64[B][2][T][Z], seconds
-        then km, or 0; d_totals_ptr = device address of float64[B][2] or 0.  Not both 0."""
-        _lib.check(self._L.cpm_expected_travel_dev(self._h, C.c_void_p(int(d_expected_ptr)) if d_expected_ptr else None, int(B),
-                                                   C.c_void_p(int(d_travel_ptr)) if d_travel_ptr else None,
-                                                   C.c_void_p(int(d_totals_ptr)) if d_totals_ptr else None))
+        then km, or 0; d_totals_ptr = device address of float64[B][2] or 0.  Not both 0.  sparse: the weights of expected_trip(sparse=True)."""
+        call = self._L.cpm_expected_sparse_travel_dev if sparse else self._L.cpm_expected_travel_dev
+        _lib.check(call(self._h, C.c_void_p(int(d_expected_ptr)) if d_expected_ptr else None, int(B),
+                        C.c_void_p(int(d_travel_ptr)) if d_travel_ptr else None, C.c_void_p(int(d_totals_ptr)) if d_totals_ptr else None))
 
     # -- the adjoint of the expected densities (include/cpm_expected_grad.h): gradients for p_drive and pi0 in one backward pass --
-    def expected_grad(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None):
+    def expected_grad(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None, sparse=False):
         """The gradient of L = <g_parking, parking> + <g_driving, driving> + <g_next, pi_next> over expected()'s outputs at the installed
         tables, blocking: dict(grad_p_drive (Z, T) float64 F-order, grad_pi0 (Z,)).  g_parking / g_driving: (Z, T) cotangents, i.e. the
         derivative of an objective with respect to expected()'s densities; g_next: (Z,) or None (zeros).  grad_p_drive is exactly 0
-        wherever the installed p_drive is not strictly inside (0, 1).  pi0, ivp: as for expected()."""
+        wherever the installed p_drive is not strictly inside (0, 1).  pi0, ivp: as for expected().  sparse: from the compact rows of sparse
+        tables (include/cpm_expected_sparse_grad.h): the same bits for finite cotangents (this call checks them), the dense p_destin array
+        neither read nor built."""
         a = self._pi0(pi0)
         gp = np.asfortranarray(_f64(g_parking, (self.Z, self.T)))
         gd = np.asfortranarray(_f64(g_driving, (self.Z, self.T)))
         gn = None if g_next is None else np.ascontiguousarray(_f64(g_next, (self.Z,)))
         grad = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
         grad_pi0 = np.zeros(self.Z, dtype=np.float64)
-        _lib.check(self._L.cpm_expected_grad(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0)))
+        call = self._L.cpm_expected_sparse_grad if sparse else self._L.cpm_expected_grad
+        _lib.check(call(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0)))
         return dict(grad_p_drive=grad, grad_pi0=grad_pi0)
 
-    def expected_grad_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0):
+    def expected_grad_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0, sparse=False):
         """Enqueue on the context's stream: d_cotangent_ptr = device address of float64[2][T][Z] (g_parking, then g_driving, laid out
         like expected_dev's tensor); d_grad_p_drive_ptr = device address of float64[T][Z]; d_pi0_ptr / d_gnext_ptr = device address of
-        float64[Z] or 0 (uniform / zeros); d_grad_pi0_ptr = device address of float64[Z] or 0 (not wanted)."""
+        float64[Z] or 0 (uniform / zeros); d_grad_pi0_ptr = device address of float64[Z] or 0 (not wanted).  sparse: as in
+        expected_grad(); the cotangents must be finite (the call does not check)."""
         p = lambda v: C.c_void_p(int(v)) if v else None
-        _lib.check(self._L.cpm_expected_grad_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr),
-                                                 p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr)))
+        call = self._L.cpm_expected_sparse_grad_dev if sparse else self._L.cpm_expected_grad_dev
+        _lib.check(call(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr), p(d_grad_p_drive_ptr),
+                        p(d_grad_pi0_ptr)))
 
     # -- the adjoint along a tangent of p_destin (include/cpm_expected_grad_dest.h): the derivative for e_dest --
     def set_p_dest_tangent(self, dp):
@@ -718,11 +731,14 @@ class Sampler:
                                                       p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr), p(d_grad_dest_ptr)))
 
     # -- the adjoint for the fleets of a batch (include/cpm_expected_grad_batch.h): B gradients in one pass over p_destin --
-    def expected_grad_batch(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None, dest=False):
+    def expected_grad_batch(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None, dest=False, sparse=False):
         """expected_grad() -- dest: expected_grad_dest() -- for every fleet of the installed batch tables, blocking.  g_parking /
         g_driving: (Z, T, B) cotangents, fleet b's in [:, :, b]; g_next: (Z, B) or None (zeros for all fleets); pi0 is shared.  Returns
         dict(grad_p_drive (Z, T, B) float64 F-order, grad_pi0 (Z, B)[, grad_dest (Z, T, B)]): fleet b's slices bit for bit what the
-        B = 1 call returns with p_drive[:, :, b] installed and fleet b's cotangents."""
+        B = 1 call returns with p_drive[:, :, b] installed and fleet b's cotangents.  sparse: as in expected_grad(); not with dest (the
+        tangent of p_destin is a dense array)."""
+        if sparse and dest:
+            raise ValueError("expected_grad_batch: dest=True has no sparse form: the p_destin tangent is a dense array")
         a = self._pi0(pi0)
         B = self.get_info(_lib.CPM_INFO_BATCH)
         if B < 1:  # (the library names what is missing; it reads no array before it does)
@@ -734,19 +750,21 @@ class Sampler:
         grad_pi0 = np.zeros((self.Z, B), dtype=np.float64, order="F")
         flags = _lib.CPM_EXPECT_IVP if ivp else 0
         if not dest:
-            _lib.check(self._L.cpm_expected_grad_batch(self._h, _vp(a), flags, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0)))
+            call = self._L.cpm_expected_sparse_grad_batch if sparse else self._L.cpm_expected_grad_batch
+            _lib.check(call(self._h, _vp(a), flags, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0)))
             return dict(grad_p_drive=grad, grad_pi0=grad_pi0)
         grad_dest = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
         _lib.check(self._L.cpm_expected_grad_dest_batch(self._h, _vp(a), flags, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0), _vp(grad_dest)))
         return dict(grad_p_drive=grad, grad_pi0=grad_pi0, grad_dest=grad_dest)
 
-    def expected_grad_batch_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0):
+    def expected_grad_batch_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0, sparse=False):
         """Enqueue on the context's stream: d_cotangent_ptr = device address of float64[B][2][T][Z] (laid out like expected_batch_dev's
         tensor); d_grad_p_drive_ptr = device address of float64[B][T][Z]; d_pi0_ptr = device address of float64[Z] or 0 (uniform);
-        d_gnext_ptr / d_grad_pi0_ptr = device address of float64[B][Z] or 0 (zeros / not wanted)."""
+        d_gnext_ptr / d_grad_pi0_ptr = device address of float64[B][Z] or 0 (zeros / not wanted).  sparse: as in expected_grad_dev()."""
         p = lambda v: C.c_void_p(int(v)) if v else None
-        _lib.check(self._L.cpm_expected_grad_batch_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr),
-                                                       p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr)))
+        call = self._L.cpm_expected_sparse_grad_batch_dev if sparse else self._L.cpm_expected_grad_batch_dev
+        _lib.check(call(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr), p(d_grad_p_drive_ptr),
+                        p(d_grad_pi0_ptr)))
 
     def expected_grad_dest_batch_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_grad_dest_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0,
                                      d_grad_pi0_ptr=0):
@@ -793,16 +811,21 @@ class Sampler:
         return B, lo, hi, ex, w
 
     def expected_fit_dev(self, p_min, p_max, e_drive, weights, d_record_ptr, d_pi0_ptr=0, ivp=False, dest=False, d_expected_ptr=0,
-                         d_cotangent_ptr=0, d_grad_p_drive_ptr=0, d_grad_dest_ptr=0):
+                         d_cotangent_ptr=0, d_grad_p_drive_ptr=0, d_grad_dest_ptr=0, sparse=False):
         """Enqueue on the context's stream: the B points (p_min, p_max, e_drive: (B,)) with weights (B, 3) or (3,) = (w_act, w_park,
         w_adrive) into d_record_ptr = device address of float64[B][fit_words()].  The batch tables hold these points afterwards.
         d_expected_ptr / d_cotangent_ptr = device address of float64[B][2][T][Z] or 0; d_grad_p_drive_ptr / d_grad_dest_ptr = device
-        address of float64[B][T][Z] or 0 (kept in the library's workspace).  dest: also dF/de_dest, along the installed tangent."""
+        address of float64[B][T][Z] or 0 (kept in the library's workspace).  dest: also dF/de_dest, along the installed tangent.
+        sparse: from the compact rows of sparse tables (include/cpm_expected_sparse_grad.h): the same bits where every mean and distance
+        at a cell that is not stored is finite (the dense trip weights form 0 * value there); not with dest."""
+        if sparse and dest:
+            raise ValueError("expected_fit_dev: dest=True has no sparse form: the p_destin tangent is a dense array")
         B, lo, hi, ex, w = self._fit_args(p_min, p_max, e_drive, weights)
         p = lambda v: C.c_void_p(int(v)) if v else None
         flags = (_lib.CPM_EXPECT_IVP if ivp else 0) | (_lib.CPM_FIT_DEST if dest else 0)
-        _lib.check(self._L.cpm_expected_fit_dev(self._h, B, _vp(lo), _vp(hi), _vp(ex), p(d_pi0_ptr), flags, _vp(w), p(d_record_ptr),
-                                                p(d_expected_ptr), p(d_cotangent_ptr), p(d_grad_p_drive_ptr), p(d_grad_dest_ptr)))
+        call = self._L.cpm_expected_sparse_fit_dev if sparse else self._L.cpm_expected_fit_dev
+        _lib.check(call(self._h, B, _vp(lo), _vp(hi), _vp(ex), p(d_pi0_ptr), flags, _vp(w), p(d_record_ptr), p(d_expected_ptr), p(d_cotangent_ptr),
+                        p(d_grad_p_drive_ptr), p(d_grad_dest_ptr)))
 
     @staticmethod
     def fit_record(rec, T):
@@ -816,11 +839,14 @@ class Sampler:
         out["record"] = rec
         return out
 
-    def expected_fit(self, p_min, p_max, e_drive, weights, pi0=None, ivp=False, dest=False, want=()):
+    def expected_fit(self, p_min, p_max, e_drive, weights, pi0=None, ivp=False, dest=False, want=(), sparse=False):
         """Value and gradient of F = w_act * activity_error + w_park * parking_error + w_adrive * A_drive at B points, blocking: a dict
         of (B,) arrays F, activity_error, parking_error, A_drive, n_valid, d_p_min, d_p_max, d_e_drive, d_e_dest (NaN without dest),
         total_seconds, total_km, traffic_activity (B, T) and record (B, fit_words()).  want: names among "expected", "cotangent" (each
-        (B, 2, T, Z): parking then driving, hour-major), "grad_p_drive", "grad_dest" ((Z, T, B) F-order) to return as well."""
+        (B, 2, T, Z): parking then driving, hour-major), "grad_p_drive", "grad_dest" ((Z, T, B) F-order) to return as well.  sparse: as in
+        expected_fit_dev()."""
+        if sparse and dest:
+            raise ValueError("expected_fit: dest=True has no sparse form: the p_destin tangent is a dense array")
         unknown = set(want) - {"expected", "cotangent", "grad_p_drive", "grad_dest"}
         if unknown:
             raise ValueError(f"expected_fit: unknown outputs {sorted(unknown)}")
@@ -835,8 +861,9 @@ class Sampler:
         for k in ("grad_p_drive", "grad_dest"):
             arrs[k] = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F") if k in want else None
         flags = (_lib.CPM_EXPECT_IVP if ivp else 0) | (_lib.CPM_FIT_DEST if dest else 0)
-        _lib.check(self._L.cpm_expected_fit(self._h, B, _vp(lo), _vp(hi), _vp(ex), _vp(a), flags, _vp(w), _vp(rec), _vp(arrs["expected"]),
-                                            _vp(arrs["cotangent"]), _vp(arrs["grad_p_drive"]), _vp(arrs["grad_dest"])))
+        call = self._L.cpm_expected_sparse_fit if sparse else self._L.cpm_expected_fit
+        _lib.check(call(self._h, B, _vp(lo), _vp(hi), _vp(ex), _vp(a), flags, _vp(w), _vp(rec), _vp(arrs["expected"]), _vp(arrs["cotangent"]),
+                        _vp(arrs["grad_p_drive"]), _vp(arrs["grad_dest"])))
         out = self.fit_record(rec, self.T)
         out.update({k: v for k, v in arrs.items() if v is not None})
         return out
