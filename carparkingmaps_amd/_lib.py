@@ -96,6 +96,8 @@ CPM_KERNEL_ZONE_GROUPED = 5
 CPM_OPT_KERNEL, CPM_OPT_PROFILE, CPM_OPT_PROFILE_KERNEL, CPM_OPT_FUSED, CPM_OPT_FUSED_LAG, CPM_OPT_ZONE_ORDER = 1, 2, 3, 4, 5, 6
 CPM_OPT_SPARSE_UPLOAD = 7  # set_p_dest: sparse row packs for an uploaded p_destin that qualifies (include/cpm.h)
 CPM_OPT_LAST_HOUR = 8  # hour T of a grouped resample: 1 (default) counts only where only its counts are wanted, 0 the plain sampler (include/cpm.h)
+CPM_OPT_NARROW_PACK = 9  # the one-launch hour on dense packs in zone order: 1 (default) narrow row packs where the rule allows, 0 wide (include/cpm.h)
+CPM_INFO_NARROW_PACK, CPM_INFO_NARROW_TIES = 14, 15  # 1: the last step's applied hours streamed narrow packs; the undecided draws so far (a blocking read)
 CPM_OPT_FLOWS_KEPT = 16  # include/cpm_flows.h: the OD kernel once per resample over the kept runs of all hours (1) or once per hour (0, default)
 CPM_PROFILE_SAMPLER, CPM_PROFILE_PLACE, CPM_PROFILE_TRAVEL, CPM_PROFILE_UPLOAD = 0, 1, 2, 3
 # cpm_get_info keys (include/cpm.h): what the context would run next ...

@@ -137,6 +137,10 @@ struct cpm_ctx {
     DevBuf<double> d_cdf;        // [T][Z][Zp] canonical f64 CDF rows: built on first need (ensure_full_cdf) -- the car and exact-layout
     bool cdf_full = false;       // kernels and cpm_get_cdf_row read them, the grouped path never does
     DevBuf<uint32_t> d_hi;       // [T][Z][RW] row packs: guide + high words of the CDF (cpm_grouped.h)
+    DevBuf<uint32_t> d_hin;      // [T][Z][narrow_row_words] the NARROW packs of dense tables (cpm_narrow.h), built from d_hi where the one-launch
+    bool narrow_valid = false;   // hour will stream them (narrow_wanted); valid: they are d_hi's -- cleared by whatever writes d_hi (ensure_hi)
+    int narrow_opt = 1;          // CPM_OPT_NARROW_PACK
+    DevBuf<uint32_t> d_narrow_ties;  // [1] draws the narrow search resolved on the wide words, cumulative (CPM_INFO_NARROW_TIES)
     double *d_last = nullptr;    // [T][Z] row totals
     double *d_ckpt = nullptr;    // [T][nck][Z] every 32nd value of the running sums (exact fallback of the grouped path)
     long long *d_thr = nullptr;  // [T][Z] Bernoulli thresholds of p_drive (k_build_thr), rebuilt whenever p_drive changes
@@ -394,6 +398,8 @@ int32_t update_thr(cpm_ctx *c)
     return CPM_OK;
 }
 
+int32_t ensure_narrow(cpm_ctx *c);
+
 template <bool CDF, bool PACK>
 hipError_t launch_build_rows(cpm_ctx *c)
 {
@@ -406,8 +412,10 @@ hipError_t launch_build_rows(cpm_ctx *c)
     return hipGetLastError();
 }
 
+// Every writer of the row packs asks for them here: the narrow packs derived from them are stale from this moment on.
 int32_t ensure_hi(cpm_ctx *c, size_t words)
 {
+    c->narrow_valid = false;
     HIP_TRY(c->d_hi.reserve(words));
     return CPM_OK;
 }
@@ -447,7 +455,7 @@ int32_t build_rows(cpm_ctx *c, bool with_cdf)
     if (rc != CPM_OK) return rc;
     c->have_cdf = true;
     c->cdf_full = cdf;
-    return CPM_OK;
+    return ensure_narrow(c);  // (every path that installs dense packs ends here: synth_tables, build_p_dest, set_p_dest, refresh_tables)
 }
 
 // p_destin in the reference's layout when the installed tables came from a compact dataset (cpm_dataset.h): only for what reads it --
@@ -515,10 +523,50 @@ bool grow_grouped(cpm_ctx *c)
     return true;
 }
 
+// CPM_INFO_FUSED: the one-launch form the next grouped step takes (0: two launches per hour)
+int fused_form(const cpm_ctx *c)
+{
+    // (the conditions grouped_run decides on: the day launch needs two applied hours and bucket regions below the counters' XCD
+    //  bits; with one hour a run has no hour to fuse but in the placing-first form)
+    const bool day = c->zg.fused_day && c->T >= 3 && cpm::grouped_cap(c->n, static_cast<int>(c->Z), c->zg.cap_mult) < (1u << cpm::kCntXccShift);
+    return (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && c->zg.fused_ok && c->zg.parts <= 1 &&
+            cpm::fused_shape_ok(static_cast<int>(c->Z), c->Zq, c->pk_G, c->sparse_tables) &&
+            (!c->zg.fused_auto || cpm::fused_pays(static_cast<int>(c->Z), c->Zq, c->pk_G, c->cu_count, c->sparse_tables, (c->n + c->Z - 1) / std::max<int64_t>(c->Z, 1))))
+               ? (day ? 6 : (c->zg.fused_pf ? 3 : (c->T >= 2 ? 1 : 0)))
+               : 0;
+}
+
+// The next grouped step would stream narrow packs (cpm_narrow.h): asked for, dense packs installed, and the rule says they pay.
+bool narrow_wanted(const cpm_ctx *c)
+{
+    return c->narrow_opt != 0 && c->have_cdf && c->d_hi && c->n > 0 &&
+           cpm::narrow_pays(static_cast<int>(c->Z), !c->sparse_tables, fused_form(c) == 1, c->zg.use_perm != 1, c->zg.fused_auto);
+}
+
+// The narrow packs of the installed dense packs, where the context will use them: at the end of every install, and in front of a grouped
+// step (an option, the cars or the form may have changed since).  Where the rule says no, nothing is built.
+int32_t ensure_narrow(cpm_ctx *c)
+{
+    if (c->narrow_valid || !narrow_wanted(c)) return CPM_OK;
+    const int64_t rows = c->T * c->Z;
+    HIP_TRY(c->d_hin.reserve(static_cast<size_t>(rows) * cpm::narrow_row_words(c->Zq, c->pk_G)));
+    if (!c->d_narrow_ties) {
+        HIP_TRY(c->d_narrow_ties.reserve(1));
+        HIP_TRY(hipMemsetAsync(c->d_narrow_ties, 0, sizeof(uint32_t), c->stream));
+    }
+    HIP_TRY(cpm::narrow_build_rows(c->d_hi, c->d_hin, rows, static_cast<int>(c->Z), c->Zq, c->pk_G, c->stream));
+    c->narrow_valid = true;
+    return CPM_OK;
+}
+
 cpm::GroupedTables grouped_tables(const cpm_ctx *c)
 {
     cpm::GroupedTables tb;
     tb.rp = c->d_hi;
+    if (c->narrow_valid && narrow_wanted(c)) {
+        tb.rpn = c->d_hin;
+        tb.narrow_ties = c->d_narrow_ties;
+    }
     tb.last = c->d_last;
     tb.thr = c->d_thr;
     tb.ckpt = c->d_ckpt;
@@ -933,6 +981,10 @@ int32_t resample_enqueue(cpm_ctx *c, uint64_t seed, uint32_t flags, int64_t *d_c
             int32_t rc_tt = ensure_travel_tables(c);
             if (rc_tt != CPM_OK) return rc_tt;
         }
+        {
+            int32_t rc_n = ensure_narrow(c);
+            if (rc_n != CPM_OK) return rc_n;
+        }
         int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, travel, d_counts, c->cu_count,
                                       [&](int what) { prof_begin(c, what); }, [&](int what) { prof_end(c, what); }, g_last_error, false, nullptr, side);
         rc = parked_pass(rc);
@@ -1009,7 +1061,9 @@ int32_t ivp_grouped(cpm_ctx *c, uint64_t seed)
 {
     c->zx.buckets0_valid = false;  // the current state's grouped buckets may be cached (zg); everything else is stale once the IVP is committed
     c->zb.buckets0_valid = false;
-    int32_t rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, false, c->d_counts, c->cu_count,
+    int32_t rc = ensure_narrow(c);
+    if (rc != CPM_OK) return rc;
+    rc = cpm::grouped_run(c->zg, c->stream, grouped_tables(c), c->n, c->cars, c->d_zone0, seed, false, c->d_counts, c->cu_count,
                                   [](int) {}, [](int) {}, g_last_error, true, c->d_ztmp);
     if (rc != CPM_OK) return rc;
     c->ivp_form = c->zg.last_form;
@@ -2531,6 +2585,10 @@ int32_t cpm_set_option(cpm_ctx *c, int32_t option, int64_t value)
         if (value != 0 && value != 1) return fail(CPM_ERR_ARG, "last hour %lld (0 the plain sampler, 1 counts only)", (long long)value);
         c->zg.count_only = c->zb.count_only = value != 0;
         return CPM_OK;
+    case CPM_OPT_NARROW_PACK:
+        if (value != 0 && value != 1) return fail(CPM_ERR_ARG, "narrow pack %lld (0 wide row packs, 1 narrow where the rule allows)", (long long)value);
+        c->narrow_opt = static_cast<int>(value);  // (read in front of every grouped step: the packs are built there when they are missing)
+        return CPM_OK;
     case CPM_OPT_PROFILE_KERNEL:
         if (value < CPM_PROFILE_SAMPLER || value > CPM_PROFILE_UPLOAD) return fail(CPM_ERR_ARG, "profile kernel %lld", (long long)value);
         c->prof_what = static_cast<int>(value);
@@ -2559,15 +2617,21 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
     case CPM_INFO_PARTS:
         *value_out = c->zg.parts;
         return CPM_OK;
-    case CPM_INFO_FUSED: {
-        // (the conditions grouped_run decides on: the day launch needs two applied hours and bucket regions below the counters' XCD
-        //  bits; with one hour a run has no hour to fuse but in the placing-first form)
-        const bool day = c->zg.fused_day && c->T >= 3 && cpm::grouped_cap(c->n, static_cast<int>(c->Z), c->zg.cap_mult) < (1u << cpm::kCntXccShift);
-        *value_out = (pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && c->zg.fused_ok && c->zg.parts <= 1 &&
-                      cpm::fused_shape_ok(static_cast<int>(c->Z), c->Zq, c->pk_G, c->sparse_tables) &&
-                      (!c->zg.fused_auto || cpm::fused_pays(static_cast<int>(c->Z), c->Zq, c->pk_G, c->cu_count, c->sparse_tables, (c->n + c->Z - 1) / std::max<int64_t>(c->Z, 1))))
-                         ? (day ? 6 : (c->zg.fused_pf ? 3 : (c->T >= 2 ? 1 : 0)))
-                         : 0;
+    case CPM_INFO_FUSED:
+        *value_out = fused_form(c);
+        return CPM_OK;
+    case CPM_INFO_NARROW_TIES: {  // (a blocking read: the stream is drained, one word comes back from the device)
+        uint32_t ties = 0;
+        if (c->d_narrow_ties) {
+            HIP_TRY(hipSetDevice(c->device));
+            if (c->ivp_pending) {
+                int32_t rc_ivp = finish_ivp(c);
+                if (rc_ivp != CPM_OK) return rc_ivp;
+            }
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(hipMemcpy(&ties, c->d_narrow_ties, sizeof(ties), hipMemcpyDeviceToHost));
+        }
+        *value_out = ties;
         return CPM_OK;
     }
     case CPM_INFO_SPARSE_TABLES:
@@ -2597,6 +2661,7 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
         *value_out = !c->tt_valid ? 0 : c->tts_valid ? (c->tts_fixed ? 1 : 2) : 3;
         return CPM_OK;
     case CPM_INFO_LAST_BATCH_FLEETS:
+    case CPM_INFO_NARROW_PACK:
     case CPM_INFO_CELL_APPLIED:
     case CPM_INFO_CELL_HEAVY:
     case CPM_INFO_CELL_LAST:
@@ -2608,6 +2673,7 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
             if (rc_ivp != CPM_OK) return rc_ivp;
         }
         *value_out = what == CPM_INFO_LAST_BATCH_FLEETS ? c->last_batch_fleets
+                     : what == CPM_INFO_NARROW_PACK     ? (c->last_cells.narrow ? 1 : 0)
                      : what == CPM_INFO_CELL_APPLIED    ? c->last_cells.applied
                      : what == CPM_INFO_CELL_HEAVY      ? c->last_cells.heavy
                      : what == CPM_INFO_CELL_LAST       ? c->last_cells.last
@@ -3557,7 +3623,9 @@ int32_t cpm_algorithmic_bytes_per_hour(cpm_ctx *c, int64_t *bytes_out)
     // The second-generation grouped path streams the 4-byte high-word rows (Zq per row) instead of the f64 rows:
     // its true element size is substituted, as 8(d) prescribes for a variant with a different element size.
     const bool hi_rows = pick_kernel(c) == CPM_KERNEL_ZONE_GROUPED && grouped_fits(c, c->zg.cap_mult);
-    const int64_t rows = hi_rows ? c->Z * static_cast<int64_t>(cpm::pack_row_words(c->Zq, c->pk_G, c->sparse_tables)) * 4 + c->Z * 8
+    // ... and where the one-launch hour streams NARROW packs (cpm_narrow.h), theirs.
+    const int64_t pack_words = hi_rows && narrow_wanted(c) ? cpm::narrow_row_words(c->Zq, c->pk_G) : cpm::pack_row_words(c->Zq, c->pk_G, c->sparse_tables);
+    const int64_t rows = hi_rows ? c->Z * pack_words * 4 + c->Z * 8
                                  : c->Z * c->Z * 8;
     *bytes_out = rows + c->Z * 8 + c->n * 8 + 2 * c->Z * 8;
     return CPM_OK;

@@ -45,7 +45,7 @@ inline uint32_t grouped_idbits(int Z, bool general = false)
 }
 
 // ------------------------------------------------------------------------------------------------ row packs
-CPM_HD inline int pack_guide_bits(int Z)
+CPM_HD constexpr int pack_guide_bits(int Z)
 {
     int g = 3;  // >= 8 entries: the guide is a whole number of 16-B pieces
     while ((1 << g) < Z) ++g;
@@ -56,10 +56,10 @@ CPM_HD inline int pack_guide_bits(int Z)
 }
 // high words per row: Z, then at least 31 entries of 0xFFFFFFFF (the unclamped stride walk of pack_search reads up to 30 past
 // its bracket), a whole number of 128-B lines
-CPM_HD inline int pack_zq(int Z) { return (Z + 31 + 31) / 32 * 32; }
-CPM_HD inline int pack_guide_words(int G) { return (1 << G) / 2 + 4; }  // 2^G + 1 entries used (+7 pad: whole 16-B pieces)
+CPM_HD constexpr int pack_zq(int Z) { return (Z + 31 + 31) / 32 * 32; }
+CPM_HD constexpr int pack_guide_words(int G) { return (1 << G) / 2 + 4; }  // 2^G + 1 entries used (+7 pad: whole 16-B pieces)
 // smap (sparse pack, cpm_dataset.h): Zq and G of the compact row, and a u16 destination per entry behind the high words
-CPM_HD inline int pack_row_words(int Zq, int G, int smap = 0)  // at least 1 KiB: one whole LDS-DMA wave-instruction
+CPM_HD constexpr int pack_row_words(int Zq, int G, int smap = 0)  // at least 1 KiB: one whole LDS-DMA wave-instruction
 {
     const int w = pack_guide_words(G) + Zq + (smap ? Zq / 2 : 0);  // (Zq is a multiple of 32, the guide of 4: whole 16-byte pieces)
     return w < 256 ? 256 : w;  // (rows rounded up to whole 128-byte lines: -0.3 % at S4k, within noise -- profiles/round4_notes.md)
@@ -71,7 +71,7 @@ inline bool pack_row_fits(int Z)
     return sizeof(uint32_t) * static_cast<size_t>(pack_row_words(pack_zq(Z), pack_guide_bits(Z))) <= kPackLds;
 }
 // 16-byte pieces of a row pack over the lanes of a sampler workgroup: the LDS-DMA instructions per wave its staging NEEDS
-inline int pack_need(int Zq, int G, int smap = 0) { return (pack_row_words(Zq, G, smap) / 4 + kSampleBlock - 1) / kSampleBlock; }
+constexpr int pack_need(int Zq, int G, int smap = 0) { return (pack_row_words(Zq, G, smap) / 4 + kSampleBlock - 1) / kSampleBlock; }
 
 // ------------------------------------------------------------------------------------------------ cars per thread
 // Cars per thread by the mean bucket size (cars of this GPU / zones): 256 x 4 slots for ~1000 cars per zone, 256 x 2 and 256 x 1

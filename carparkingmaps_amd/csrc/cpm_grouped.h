@@ -37,6 +37,7 @@
 #include "../../include/cpm.h"
 #include "cpm_kernels.h"
 #include "cpm_dispatch.h"
+#include "cpm_narrow.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
 #include "cpm_stays.h"
@@ -743,6 +744,64 @@ __device__ __forceinline__ void pack_search(const uint16_t *guide_g, const uint3
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the narrow pack (cpm_narrow.h)
+// What the narrow twin of the hour needs beyond the rare block, BEHIND it in the same allocation (GroupedWork::rare + 1): the hot kernel
+// takes no pointer and no flag more than the wide one (it lives at its SGPR ceiling), and GroupedRare, which k_grouped_zero copies
+// per run, stays as it is.  Written by grouped_run when the tables or the allocation change.
+struct NarrowRare {
+    const uint32_t *rp_wide;  // [T][Z][rw_wide] the WIDE row packs of the installed tables: what an undecided draw reads
+    uint32_t *ties;           // the context's count of draws resolved on the wide words (CPM_INFO_NARROW_TIES), cumulative
+    uint32_t rw_wide, gw;     // words of a wide pack, of its guide
+    int Zq, pad_;
+};
+
+// the staged narrow pack as narrow_search's accessor: cursors are LDS byte addresses of the u16 entries
+struct NarrowLdsPack {
+    static constexpr uint32_t kStep = 2;
+    uint32_t guide_a, e_a;  // LDS addresses of the guide and of entry 0
+    __device__ __forceinline__ uint32_t guide(uint32_t m) const { return *(lds_cu16 *)static_cast<uintptr_t>(guide_a + 2u * m); }
+    __device__ __forceinline__ uint32_t cur(uint32_t j) const { return e_a + 2u * j; }
+    __device__ __forceinline__ uint32_t at(uint32_t c) const { return *(lds_cu16 *)static_cast<uintptr_t>(c); }
+    __device__ __forceinline__ uint32_t idx(uint32_t c) const { return (c - e_a) >> 1; }
+    __device__ __forceinline__ bool any(bool p) const { return any64(p); }
+};
+
+// One draw the 16 bits could not decide (rare, out of line like search_exact_ckpt: a 2^-14 event per driver): the row's wide words
+// from HBM through the block behind the rare block, and the context's counter -- inside the slow path only, never in the hot one
+// (profiles/round4_notes.md, "the statistics word": what one hot address costs).
+__device__ __noinline__ uint32_t narrow_tie_rare(const GroupedRare *__restrict__ rare, int hour, int o, uint32_t dest, uint32_t khi)
+{
+    const NarrowRare *nr = reinterpret_cast<const NarrowRare *>(rare + 1);
+    const int Z = rare->Z;
+    const uint32_t *hi = nr->rp_wide + (static_cast<size_t>(hour) * Z + o) * nr->rw_wide + nr->gw;
+    atomicAdd(nr->ties, 1u);
+    return narrow_tie_walk([hi](uint32_t j) { return hi[j]; }, dest, khi, Z, nr->Zq);
+}
+
+// pack_search on a staged NARROW pack: (dest, ok) as the wide search gives them
+template <int CPT>
+__device__ __forceinline__ void narrow_pack_search(const uint32_t *pack, int gw, const uint32_t (&khi)[CPT], const bool (&want)[CPT], int sh, uint32_t hi_last,
+                                                   int Z, int Zq, const GroupedRare *rare, int hour, int z, uint32_t (&dest)[CPT], bool (&ok)[CPT])
+{
+    NarrowLdsPack np;
+    np.guide_a = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_cu32 *)pack));
+    np.e_a = np.guide_a + 4u * static_cast<uint32_t>(gw + kNarrowHeadWords);
+    bool tie[CPT], in[CPT], anytie = false;
+    narrow_search<CPT>(np, khi, want, sh, hi_last, Z, Zq, dest, ok, tie, in);
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) anytie |= tie[c];
+    if (__builtin_expect(any64(anytie), 0)) {  // wave-uniform, rare
+#pragma unroll
+        for (int c = 0; c < CPT; ++c) {
+            if (tie[c]) {
+                const uint32_t r = narrow_tie_rare(rare, hour, z, dest[c], khi[c]);
+                dest[c] = r & ~kNarrowTieOk;
+                ok[c] = (r & kNarrowTieOk) != 0u;
+            }
+        }
+    }
+}
+
 // Philox words of (car, step, stream 0): Bernoulli integer kb (53 bits of words 0,1) and the categorical words (2,3)
 __device__ __forceinline__ void car_draw_words(uint64_t seed, uint64_t car, uint32_t step, long long &kb, uint32_t &clo, uint32_t &chi)
 {
@@ -954,18 +1013,22 @@ __device__ __forceinline__ void hand_off_done(uint32_t *done_chunk, int tid)
 // are waited for with vmcnt(0) (nothing of this body is in flight behind them).  The pack is read behind the barrier of the first
 // pass, which follows that wait in every wave.
 // POLICY (store_policy): how the stayers' ids are stored and the pack is streamed; 0 = plain stores, default loads.
-template <int BLOCK, int CPT, int NQ, bool GROUPED, bool FUSED, bool WAIT = false, bool SPARSE = false, bool STAGED = false, int POLICY = 0>
+// NARROW (the narrow twin of the one-launch hour, cpm_narrow.h): a.rp_t holds NARROW packs, NQ is the number of LDS-DMA instructions
+// they take (narrow_nq of the wide rung), and the search runs on 16-bit entries; the wide words behind an undecided draw are reached
+// through a.rare.  Everything else is the wide body's.
+template <int BLOCK, int CPT, int NQ, bool GROUPED, bool FUSED, bool WAIT = false, bool SPARSE = false, bool STAGED = false, int POLICY = 0, bool NARROW = false>
 __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const int z, uint32_t *pack, SampleLds &sl, uint32_t *done_chunk,
                                                     const uint32_t *wait_on = nullptr, uint32_t wait_need = 0)
 {
     static_assert(!(STAGED && (WAIT || FUSED)), "a staged pack is the batched sampler's: two launches per hour");
+    static_assert(!NARROW || (FUSED && GROUPED && !WAIT && !SPARSE && !STAGED), "narrow packs: the one-launch hour on dense tables");
     uint32_t &s_ndrive = sl.ndrive, &s_nstay = sl.nstay, &s_split = sl.split;
     uint32_t(&gb)[kGroups] = sl.gb;
     uint32_t(&stage)[kGroups * kStage] = sl.stage;
     const int tid = threadIdx.x, lane = tid & 63;
     const uint32_t cap = a.cap;
     const uint32_t b = static_cast<uint32_t>(z) * cap;
-    const int gw = pack_guide_words(a.G), rw = pack_row_words(a.Zq, a.G, SPARSE ? 1 : 0), pieces = rw / 4, sh = 32 - a.G;
+    const int gw = pack_guide_words(a.G), rw = NARROW ? narrow_row_words(a.Zq, a.G) : pack_row_words(a.Zq, a.G, SPARSE ? 1 : 0), pieces = rw / 4, sh = 32 - a.G;
     // Scalar loads first, then the id loads -- written in assembly and waited for by hand: with LDS-DMA in flight hipcc
     // (ROCm 7.2) drains vmcnt to 0 at the first use of any ordinary vector load result, which would put Philox behind the whole
     // pack.  The wave issues CPT + 1 id loads, then exactly NQ LDS-DMA instructions; vmcnt retires in order, so vmcnt <= NQ
@@ -1124,9 +1187,11 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
         __syncthreads();
         CPM_SSTAMP(3);
         n = s_split ? static_cast<uint32_t>(CPT * BLOCK) : n_all;  // the cars this workgroup samples
-        hi_last = hi[(SPARSE ? a.Zc : a.Z) - 1];
+        if constexpr (NARROW) hi_last = hi[0];  // (the header piece behind the guide)
+        else hi_last = hi[(SPARSE ? a.Zc : a.Z) - 1];
         if constexpr (K > 0) {
-            pack_search<K>(guide, hi, khi, want, sh, hi_last, a.Zq, dest, ok, smap);
+            if constexpr (NARROW) narrow_pack_search<K>(pack, gw, khi, want, sh, hi_last, a.Z, a.Zq, a.rare, a.hour, z, dest, ok);
+            else pack_search<K>(guide, hi, khi, want, sh, hi_last, a.Zq, dest, ok, smap);
             {
                 bool anyx = false;
 #pragma unroll
@@ -1136,8 +1201,15 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
                 }
                 if (__builtin_expect(any64(anyx), 0)) {  // ties and draws above the row total: the f64 row in HBM (wave-uniform, rare)
 #pragma unroll
-                    for (int c = 0; c < K; ++c)
-                        if (want[c] & !ok[c]) dest[c] = search_exact_any<SPARSE>(a.rare, a.hour, z, u53(clo[c], khi[c]), last, khi[c] <= hi_last ? static_cast<int>(dest[c]) : -1);
+                    for (int c = 0; c < K; ++c) {
+                        if (want[c] & !ok[c]) {
+                            if constexpr (NARROW) {  // (the low word drawn again here, where it is rare: six registers the twin's search needs for its bounds)
+                                long long kb;
+                                car_draw_words(a.seed, a.cars.global(id[c]), a.step, kb, clo[c], khi[c]);
+                            }
+                            dest[c] = search_exact_any<SPARSE>(a.rare, a.hour, z, u53(clo[c], khi[c]), last, khi[c] <= hi_last ? static_cast<int>(dest[c]) : -1);
+                        }
+                    }
                 }
             }
             CPM_SSTAMP(4);
@@ -1258,7 +1330,8 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
         car_draw_words(a.seed, car, a.step, kb, clo1[0], khi1[0]);
         const bool drive1 = valid1 & (kb <= thr);
         want1[0] = drive1 & (last != 0.0);
-        pack_search<1>(guide, hi, khi1, want1, sh, hi_last, a.Zq, dest1, ok1, smap);
+        if constexpr (NARROW) narrow_pack_search<1>(pack, gw, khi1, want1, sh, hi_last, a.Z, a.Zq, a.rare, a.hour, z, dest1, ok1);
+        else pack_search<1>(guide, hi, khi1, want1, sh, hi_last, a.Zq, dest1, ok1, smap);
         if (!want1[0]) dest1[0] = z;
         else if (!ok1[0]) dest1[0] = search_exact_any<SPARSE>(a.rare, a.hour, z, u53(clo1[0], khi1[0]), last, khi1[0] <= hi_last ? static_cast<int>(dest1[0]) : -1);
         if (GROUPED) {
@@ -1942,8 +2015,9 @@ constexpr int kDoneStride = 32;  // words between the hand-off counters of conse
 // hour of the initial-value problem, the same tables a day earlier) -- so that the workgroups that enter last are the short ones: buckets
 // spread from half to 2.5 x the mean, and in zone order the sampler phase ended on whatever came last.  Chunks are chunks of POSITIONS:
 // they still complete in launch order, and a placing block finds its chunk's zones through the same list.
-template <int CPT, int NQ, bool SPARSE = false, bool PERM = false>
-__global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_grouped_hour(GroupedArgs a)
+// NARROW (k_grouped_hour_narrow, below): the sampler workgroups stream narrow packs (cpm_narrow.h); the placing blocks are the same.
+template <int CPT, int NQ, bool SPARSE, bool PERM, bool NARROW>
+__device__ __forceinline__ void grouped_hour_block(const GroupedArgs &a)
 {
     extern __shared__ uint32_t dyn[];  // sampler: the zone's row pack; placing block: its sorted list
     __shared__ union {
@@ -1977,7 +2051,7 @@ __global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_groupe
         }
     }
     if (z >= 0) {
-        grouped_sample_body<kFusedThreads, CPT, NQ, true, true, false, SPARSE, false, policy_dense_pack_only(kPolicyHour, SPARSE)>(
+        grouped_sample_body<kFusedThreads, CPT, NARROW ? narrow_nq(NQ) : NQ, true, true, false, SPARSE, false, policy_dense_pack_only(kPolicyHour, SPARSE), NARROW>(
             a, z, dyn, u.s, a.done_t + static_cast<size_t>((PERM ? static_cast<int>(blockIdx.x) : z) / kFusedChunk) * kDoneStride);
     } else {
         const uint32_t need = static_cast<uint32_t>(min(kFusedChunk, a.Z - j * kFusedChunk));
@@ -1988,6 +2062,19 @@ __global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_groupe
             g, j, u.p, dyn, a.D, a.cntg, static_cast<int>(gdiv_zpg(a.gdiv)), kFusedChunk, a.Z, a.cap, a.scap, a.idbits, a.cnt_next + a.Z, a.ids_next, a.rare->status,
             a.done_t + static_cast<size_t>(j) * kDoneStride, need, a.spin_limit, nullptr, PERM ? a.perm_t : nullptr, SPARSE);
     }
+}
+template <int CPT, int NQ, bool SPARSE = false, bool PERM = false>
+__global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_grouped_hour(GroupedArgs a)
+{
+    grouped_hour_block<CPT, NQ, SPARSE, PERM, false>(a);
+}
+// The narrow twin of k_grouped_hour<CPT, NQ, false, false> (dense packs, zone order): the same CPT and the same NQ RUNG as the wide rule
+// gives -- the launch record is the wide kernel's -- while its waves issue narrow_nq(NQ) LDS-DMA instructions and wait for their ids
+// with vmcnt(narrow_nq(NQ)).
+template <int CPT, int NQ>
+__global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_grouped_hour_narrow(GroupedArgs a)
+{
+    grouped_hour_block<CPT, NQ, false, false, true>(a);
 }
 
 // ------------------------------------------------------------------------------------------------ the hour, placing first
@@ -2031,6 +2118,7 @@ __global__ __launch_bounds__(kFusedThreads, CPM_WPS) CPM_SGPR_ATTR void k_groupe
 struct LaunchCells {
     uint32_t applied = 0, heavy = 0, last = 0, place = 0, batch = 0;
     bool hour_T = false;
+    bool narrow = false;  // CPM_INFO_NARROW_PACK: an applied hour streamed narrow packs (k_grouped_hour_narrow; its record word is the wide kernel's)
     void sampler(uint32_t word) { (hour_T ? last : applied) = word; }
 };
 inline LaunchCells &launch_cells()
@@ -2426,6 +2514,10 @@ inline size_t fused_lds_bytes(int Zq, int G, int smap = 0)
 {
     return std::max(sizeof(uint32_t) * static_cast<size_t>(pack_row_words(Zq, G, smap)), static_cast<size_t>(4 + sizeof(PlaceLds<kFusedThreads, kFusedKruns, kFusedZpg>::zone_t)) * kFusedKruns * kFusedKdeep * kFusedThreads);
 }
+inline size_t fused_lds_bytes_narrow(int Zq, int G)  // (the narrow twin: max(narrow pack, placing list))
+{
+    return std::max(sizeof(uint32_t) * static_cast<size_t>(narrow_row_words(Zq, G)), fused_lds_bytes(0, 3));
+}
 template <int CPT, int NQ, bool SPARSE, bool PERM = false>
 inline hipError_t grouped_launch_hour_t(const GroupedArgs &a, hipStream_t stream)
 {
@@ -2460,11 +2552,62 @@ inline bool fused_pays(int Z, int Zq, int G, int cu_count, int smap = 0, int64_t
     const size_t lds = fused_lds_bytes(Zq, G, smap) + 4608;  // (+ the static part: SampleLds / PlaceLds)
     return Z >= 12 * std::max(cu_count, 1) && 5 * lds <= 160 * 1024;
 }
-inline hipError_t grouped_launch_hour(const GroupedArgs &a, int64_t mean, hipStream_t stream)
+// ... its narrow twin (a.rp_t: narrow packs): the record word is the wide kernel's, `narrow` says what was streamed
+template <int CPT, int NQ>
+inline hipError_t grouped_launch_hour_narrow_t(const GroupedArgs &a, hipStream_t stream)
+{
+    static_assert(sizeof(uint32_t) * 1024 * narrow_nq(NQ) <= kPackLds, "the narrow pack of every Z of the rung fits");
+    const int nchunk = (a.Z + kFusedChunk - 1) / kFusedChunk;
+    constexpr auto kernel = k_grouped_hour_narrow<CPT, NQ>;
+    const size_t lds = fused_lds_bytes_narrow(a.Zq, a.G);
+    if (narrow_need(a.Zq, a.G) > narrow_nq(NQ)) return hipErrorInvalidValue;  // (cannot happen: narrow_nq covers the rung's band)
+    const hipError_t e = lds_opt_in<kernel>(lds, kPackLds);
+    if (e != hipSuccess) return e;
+    const unsigned blocks = a.lag >= nchunk ? static_cast<unsigned>(((a.Z + 7) & ~7) + nchunk * kGroups)
+                                            : static_cast<unsigned>((nchunk + a.lag) * (kFusedChunk + kGroups));
+    launch_cells().sampler(cell_word(kCellHour, CPT, NQ, true, false, false));
+    launch_cells().narrow = true;
+    launch(kernel, dim3(blocks), dim3(kFusedThreads), lds, stream, a);
+    return hipSuccess;
+}
+// narrow: a.rp_t holds the hour's NARROW packs (grouped_run decides: narrow_pays, no list of zones largest-first)
+inline hipError_t grouped_launch_hour(const GroupedArgs &a, int64_t mean, hipStream_t stream, bool narrow = false)
 {
     // (one launch per hour only while no heavy bucket has been seen: the wide rule)
-    return cell_walk<HourCells>(grouped_cpt_wide(mean), pack_need(a.Zq, a.G, a.smap), a.smap != 0,
-                                [&](auto CPT, auto NQ, auto SPARSE) { return grouped_launch_hour_t<CPT, NQ, SPARSE>(a, stream); });
+    return cell_walk<HourCells>(grouped_cpt_wide(mean), pack_need(a.Zq, a.G, a.smap), a.smap != 0, [&](auto CPT, auto NQ, auto SPARSE) {
+        if constexpr (!SPARSE) {
+            if (narrow) return grouped_launch_hour_narrow_t<CPT, NQ>(a, stream);
+        }
+        return grouped_launch_hour_t<CPT, NQ, SPARSE>(a, stream);
+    });
+}
+
+// The narrow packs FROM the wide ones (cpm_narrow.h: guide verbatim, header piece, 16 bits per entry), 16 bytes per load and store:
+// one block per row, a thread per 16-byte piece of the narrow row.  Run behind whatever installs dense packs, when the context will
+// stream them (narrow_pays).
+__global__ __launch_bounds__(256) void k_narrow_rows(const uint32_t *__restrict__ wide, uint32_t *__restrict__ narrow, int Z, int Zq, int G)
+{
+    struct WideRow {
+        const uint32_t *w;
+        __device__ NarrowPiece piece(int i) const
+        {
+            const uint4 v = reinterpret_cast<const uint4 *>(w)[i];
+            return NarrowPiece{{v.x, v.y, v.z, v.w}};
+        }
+        __device__ uint32_t word(int i) const { return w[i]; }
+    };
+    const int rw = pack_row_words(Zq, G), rn = narrow_row_words(Zq, G);
+    const WideRow row{wide + static_cast<size_t>(blockIdx.x) * rw};
+    uint4 *o = reinterpret_cast<uint4 *>(narrow + static_cast<size_t>(blockIdx.x) * rn);
+    for (int q = threadIdx.x; q < rn / 4; q += 256) {
+        const NarrowPiece p = narrow_piece(row, q, Z, Zq, G);
+        o[q] = make_uint4(p.v[0], p.v[1], p.v[2], p.v[3]);
+    }
+}
+inline hipError_t narrow_build_rows(const uint32_t *wide, uint32_t *narrow, int64_t rows, int Z, int Zq, int G, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_narrow_rows, dim3(static_cast<unsigned>(rows)), dim3(256), 0, stream, wide, narrow, Z, Zq, G);
+    return hipGetLastError();
 }
 
 template <int CPT, int NQ, bool GROUPED, bool SPARSE>
@@ -2644,6 +2787,7 @@ struct GroupedWork {
     uint32_t *cntg = nullptr;                                    // [Z][kGroups] run lengths
     unsigned long long *tt_part = nullptr;                       // [kTravelParts] partial travel-time sums, kept zero between resamples
     GroupedRare *rare = nullptr;                                 // what the rare branches of the hourly kernels read (written by k_grouped_zero per run)
+    NarrowRare narrow_rare{};                                    // what stands behind it for the narrow twin of the hour, as last written (all 0: not yet)
     uint32_t *maxn = nullptr;                                    // [2] of the current run: largest heavy bucket (> kHeavy x the sampler workgroup's slots), most heavy buckets in one hour
     uint32_t *heavy_list = nullptr, *nheavy = nullptr;           // [kHeavyCap] zones handed to the heavy kernel this hour; [T+1] how many, per hour
     int run_hours = kDayRunCopies;                               // copies of Dq / cntg: 3 (rotating), or T when the runs of every hour of a resample are kept (ensure_history)
@@ -2709,6 +2853,7 @@ struct GroupedWork {
         maxn = nullptr;
         if (rare) (void)hipFree(rare);
         rare = nullptr;
+        narrow_rare = NarrowRare{};
         if (day_hours) (void)hipFree(day_hours);
         day_hours = nullptr;
         if (perm) (void)hipFree(perm);
@@ -2751,7 +2896,7 @@ struct GroupedWork {
         if (e == hipSuccess) e = hipMalloc(&tt_part, sizeof(unsigned long long) * kTravelParts);
         if (e == hipSuccess) e = hipMemset(tt_part, 0, sizeof(unsigned long long) * kTravelParts);
         if (e == hipSuccess) e = hipMalloc(&maxn, 2 * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&rare, sizeof(GroupedRare));
+        if (e == hipSuccess) e = hipMalloc(&rare, sizeof(GroupedRare) + sizeof(NarrowRare));  // (NarrowRare: behind the rare block)
         if (e == hipSuccess) e = hipMalloc(&day_hours, sizeof(GroupedArgs) * static_cast<size_t>(std::max(T, 1)));
         if (e == hipSuccess) e = hipMalloc(&perm, sizeof(uint32_t) * static_cast<size_t>(std::max(T, 1)) * Z);
         if (e != hipSuccess) release();
@@ -2761,6 +2906,8 @@ struct GroupedWork {
 
 struct GroupedTables {
     const uint32_t *rp;      // [T][Z][RW]
+    const uint32_t *rpn = nullptr;      // [T][Z][narrow_row_words] the NARROW packs of the same tables (cpm_narrow.h), or null: none valid / not wanted
+    uint32_t *narrow_ties = nullptr;    // ... the context's count of their undecided draws
     const double *last;      // [T][Z]
     const long long *thr;    // [T][Z]
     const double *ckpt;      // [T][nck][Z] checkpoints of the running sums
@@ -2868,6 +3015,9 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
     const bool shape = w.fused_ok && w.parts <= 1 && fused_shape_ok(Z, tb.Zq, G, tb.smap) && (!w.fused_auto || fused_pays(Z, tb.Zq, G, cu_count, tb.smap, mean));
     // ... and one launch for ALL hours that are applied (k_grouped_day): the IVP's T - 1, a resample's first T - 1 (hour T is sampled,
     // never applied: the plain form behind the placing of hour T - 1, k_grouped_hour_pf); hourly travel launches need hourly boundaries
+    // ... streaming NARROW packs where they are installed and the rule allows (cpm_narrow.h): the plain one-launch hour in zone order
+    const bool narrow = tb.rpn != nullptr && narrow_pays(Z, tb.smap == 0, shape && !w.fused_pf && !w.fused_day, w.use_perm != 1, w.fused_auto);
+    const size_t rwn = static_cast<size_t>(narrow_row_words(tb.Zq, G));
     const int day_n = (shape && w.fused_day && w.cap < (1u << kCntXccShift) && (!(travel || flows || stays || paths || charge) || history)) ? (ivp ? hours : hours - 1) : 0;
     const int nchunk = (Z + kFusedChunk - 1) / kFusedChunk;
     GroupedDay day{};
@@ -2940,6 +3090,18 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         rn.Z = Z;
         hipLaunchKernelGGL(k_grouped_zero, dim3(zgrid), dim3(256), 0, stream, parking, nwords, w.maxn, w.nheavy, T + 1, w.cnt, w.cnt_words(), w.rare, rn, w.day_hours, day);
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "zeroing the counters");
+    }
+    if (narrow) {  // the block behind the rare block: rewritten only when the tables, or the allocation, have changed
+        NarrowRare nr{};
+        nr.rp_wide = tb.rp;
+        nr.ties = tb.narrow_ties;
+        nr.rw_wide = static_cast<uint32_t>(rw);
+        nr.gw = static_cast<uint32_t>(pack_guide_words(G));
+        nr.Zq = tb.Zq;
+        if (std::memcmp(&nr, &w.narrow_rare, sizeof(nr)) != 0) {
+            w.narrow_rare = nr;  // (the copy's source outlives the call)
+            if ((e = hipMemcpyAsync(w.rare + 1, &w.narrow_rare, sizeof(NarrowRare), hipMemcpyHostToDevice, stream)) != hipSuccess) return hip_fail(e, "narrow rare block");
+        }
     }
     if (!w.buckets0_valid) {  // bucket the car-indexed state once; reused until the state changes
         const int64_t chunk = (n + w.nb0 - 1) / w.nb0;
@@ -3020,7 +3182,10 @@ int32_t grouped_run(GroupedWork &w, hipStream_t stream, const GroupedTables &tb,
         prof_begin(CPM_PROFILE_SAMPLER);
         if (pf && grouped) e = grouped_launch_hour_pf<true>(a, mean, stream);
         else if (pf) e = grouped_launch_hour_pf<false>(a, mean, stream);
-        else if (fuse) e = grouped_launch_hour(a, mean, stream);
+        else if (fuse && narrow && !a.perm_t) {
+            a.rp_t = tb.rpn + static_cast<size_t>(t) * Z * rwn;
+            e = grouped_launch_hour(a, mean, stream, true);
+        } else if (fuse) e = grouped_launch_hour(a, mean, stream);
         else if (grouped) e = grouped_launch_sample<true>(a, mean, w.parts > 1, stream);
         else if (w.count_only) {  // hour T, counts only: nobody reads the destinations the plain form draws (cpm_count.h)
             e = grouped_launch_count(a, mean, w.parts > 1, stream);

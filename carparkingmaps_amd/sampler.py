@@ -104,6 +104,21 @@ class Sampler:
         tells what the most recent step ran."""
         _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_LAST_HOUR, 1 if count_only else 0))
 
+    def set_narrow_pack(self, on=True):
+        """The one-launch hour on dense row packs in zone order streams narrow packs (16 bracket-relative bits per destination instead
+        of a 32-bit high word: include/cpm.h, CPM_OPT_NARROW_PACK) where the library's rule allows: True (the library's default), or
+        False: wide packs everywhere.  The counts do not depend on it; narrow_pack() tells what the most recent step streamed."""
+        _lib.check(self._L.cpm_set_option(self._h, _lib.CPM_OPT_NARROW_PACK, 1 if on else 0))
+
+    def narrow_pack(self):
+        """1 when the applied hours of the most recent step streamed narrow row packs, from what was launched (CPM_INFO_NARROW_PACK)."""
+        return self.get_info(_lib.CPM_INFO_NARROW_PACK)
+
+    def narrow_ties(self):
+        """Draws so far that a narrow pack's 16 bits could not decide and that read the wide words instead (CPM_INFO_NARROW_TIES).  A
+        device word: the call BLOCKS until the context's stream has drained, so it must not be made while the stream is captured."""
+        return self.get_info(_lib.CPM_INFO_NARROW_TIES)
+
     def get_info(self, what):
         """cpm_get_info (keys: _lib.CPM_INFO_*).  What the context would run next: 1 = kernel family AUTO resolves to now, 2 =
         bucket-region size in multiples of the mean bucket, 3 = workgroups per heavy zone, 4 = form of the hour (0 two launches, 1 one,

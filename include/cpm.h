@@ -99,6 +99,11 @@ extern "C" {
                                    forms -- a count-only kernel (csrc/cpm_count.h: ids, one Philox call per car, a compare; no row pack, no
                                    destination draw), in cpm_resample* and cpm_resample_batch* alike; 0: the plain form of the full sampler,
                                    which also draws the destinations nobody reads.  The counts do not depend on it; what ran is CPM_INFO_LAST_HOUR */
+#define CPM_OPT_NARROW_PACK 9   /* the one-launch hour on DENSE row packs in zone order: 1 (default) its sampler workgroups stream NARROW packs
+                                   (csrc/cpm_narrow.h: 16 bracket-relative bits per destination instead of a 32-bit high word, built once per
+                                   table from the wide packs, which stay) where the rule narrow_pays allows; 0 the wide packs everywhere.  Every
+                                   other form of the hour streams wide packs either way.  The counts do not depend on it; what ran is
+                                   CPM_INFO_NARROW_PACK */
 #define CPM_OPT_PROFILE_KERNEL 3 /* which hourly launch CPM_OPT_PROFILE brackets: */
 #define CPM_PROFILE_SAMPLER 0   /*   the sampler (default; every kernel family has one) */
 #define CPM_PROFILE_PLACE 1     /*   the grouped path's placing kernel */
@@ -157,6 +162,11 @@ int32_t cpm_set_option(cpm_ctx *ctx, int32_t option, int64_t value);
                                     * always 1 for tables with dense packs and for an uploaded table; for the tables cpm_build_p_dest makes from
                                     * compact rows, 0 until something expands them (the caller's own out array, cpm_get_cdf_row, the f64-row
                                     * kernels, the cpm_expected* family).  Read-only; include/cpm_expected_sparse.h never changes it */
+#define CPM_INFO_NARROW_PACK 14    /* 1 when the applied hours of the most recent step streamed narrow row packs (CPM_OPT_NARROW_PACK), from what
+                                    * was launched; 0 otherwise.  The launch record (CPM_INFO_CELL_APPLIED) is the wide kernel's either way */
+#define CPM_INFO_NARROW_TIES 15    /* draws so far, in this context, that the 16 bits of a narrow pack could not decide and that read the wide
+                                    * words instead (about 2^-14 of the drivers).  A device word: reading it BLOCKS until the context's
+                                    * stream has drained (and commits an IVP left in flight) */
 /* Which INSTANTIATION of the grouped path's hourly kernels the most recent step launched, one word per role, written by the innermost
  * launch helper from its own template parameters (host memory only; committed as CPM_INFO_LAST_FORM is: a repeated attempt overwrites
  * it, an asynchronous IVP's is published when the IVP is committed, batch steps write their own).  0: the step had no such launch.
