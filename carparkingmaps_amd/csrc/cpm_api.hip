@@ -29,6 +29,7 @@
 #include "../../include/cpm_expected_tangent.h"
 #include "../../include/cpm_expected_sparse.h"
 #include "../../include/cpm_expected_sparse_grad.h"
+#include "../../include/cpm_expected_sparse_dest.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -53,6 +54,7 @@
 #include "cpm_expected_tangent.h"
 #include "cpm_expected_sparse.h"
 #include "cpm_expected_sparse_grad.h"
+#include "cpm_expected_sparse_dest.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -309,6 +311,17 @@ struct cpm_ctx {
     DevBuf<double> d_tan_w;             // [2][T][Z] the blocking trip-tangent call's dw_sec | dw_km
     DevBuf<double> d_exp_gdio;          // [T][Z] the blocking call's grad_dest
     int64_t tan_gen = 0;                // tangent tables installed so far: what a cached trip-weight tangent is checked against
+    // ... and the same tangent on the stored cells of sparse tables (include/cpm_expected_sparse_dest.h, cpm_expected_sparse_dest.h):
+    // independent of d_tan, dropped wherever tan_valid is
+    DevBuf<double> d_sdp;               // [T * Z][kDsCap] entry for entry with d_sp, allocated by the first call that installs one
+    bool sdp_valid = false;
+    int64_t sdp_gen = 0;                // compact tangents installed so far
+    DevBuf<double> d_sdp_stage;         // [Z dest][Z origin] one hour of a host tangent on its way to or from the cells; released after the call
+    DevBuf<unsigned long long> d_sdp_bad;   // the first non-zero entry of a host tangent off the stored cells, and its pinned twin
+    PinnedBuf<unsigned long long> h_sdp_bad;
+    DevBuf<double> d_fits_dw;           // [2][T][Z] the trip weights' tangent of the sparse fit, kept while sdp and the sparse trip weights stay
+    int64_t fits_dw_gen = -1, fits_dw_builds = -1;
+    int64_t exps_trip_builds = 0;       // builds of d_exps_w so far
     // value and gradient of the noise-free objectives (include/cpm_expected_fit.h, cpm_expected_fit.h)
     DevBuf<double> d_act_meas;          // [T] measured traffic activity
     bool have_act_meas = false;
@@ -352,6 +365,7 @@ namespace {
 void drop_dest_tangent(cpm_ctx *c)
 {
     c->tan_valid = false;
+    c->sdp_valid = false;
     c->dest_built = false;
 }
 
@@ -1631,6 +1645,7 @@ int32_t ensure_exps_trip(cpm_ctx *c)
                 nseg, c->d_dm.get(), c->d_dist.get(), c->d_last, c->d_exps_ell.get(), c->d_exps_r.get(), Z, T, c->d_exps_w.get());
     HIP_TRY(hipGetLastError());
     c->exps_trip_valid = true;
+    ++c->exps_trip_builds;
     return CPM_OK;
 }
 
@@ -1793,15 +1808,42 @@ int32_t tangent_ready(const cpm_ctx *c, const char *what)
     return CPM_OK;
 }
 
+// ... on the stored cells (include/cpm_expected_sparse_dest.h)
+int32_t sdp_ready(const cpm_ctx *c, const char *what)
+{
+    if (!c->sdp_valid || !c->d_sdp)
+        return fail(CPM_ERR_STATE, "%s: no compact tangent of the installed p_destin tables (cpm_set_p_dest_tangent_sparse or cpm_build_p_dest_tangent_sparse)", what);
+    return CPM_OK;
+}
+
+// one fused backward product of the hour whose first row is `row`, from the compact rows and the compact tangent (k_exps_grad_dest_u)
+void launch_exps_grad_dest_u(cpm_ctx *c, size_t row, const double *mu, int Zs, int nseg, int seg_len, double *part, double *part_dp)
+{
+    const int Z = static_cast<int>(c->Z);
+    cpm::launch(cpm::k_exps_grad_dest_u, dim3(static_cast<unsigned>(Z)), dim3(cpm::kExpsGradBlock), 0, c->stream, c->d_sp + row * cpm::kDsCap,
+                c->d_sdp + row * cpm::kDsCap, c->d_sj + row * cpm::kDsCap, c->d_scnt + row, cpm::kDsCap, mu, Z, Zs, seg_len, nseg, part, part_dp);
+}
+
+// ... of a pass of nf > 1 fleets (k_exps_grad_dest_u_b<NB>)
+template <int NB>
+void launch_exps_grad_dest_u_b(cpm_ctx *c, size_t row, const double *mu, int Zs, int nseg, int seg_len, int nf, double *part, double *part_dp)
+{
+    const int Z = static_cast<int>(c->Z);
+    const unsigned groups = static_cast<unsigned>((nf + cpm::kExpsDestFleets - 1) / cpm::kExpsDestFleets);  // (nf <= NB: every group lies inside mu's NB columns)
+    cpm::launch(cpm::k_exps_grad_dest_u_b<NB>, dim3(static_cast<unsigned>(Z), groups), dim3(cpm::kExpsGradBlock), 0, c->stream, c->d_sp + row * cpm::kDsCap,
+                c->d_sdp + row * cpm::kDsCap, c->d_sj + row * cpm::kDsCap, c->d_scnt + row, cpm::kDsCap, mu, Z, Zs, seg_len, nseg, nf, part, part_dp);
+}
+
 // expected_grad_enqueue with the fused product and the finishing kernel of cpm_expected_grad_dest.h: the same forward propagation, the
 // same workspace with the segments' sums of w behind those of a.  grad_dest: [T][Z].
+// sparse: both halves read the compact rows, the product the compact tangent beside them (k_exps_hour, k_exps_grad_dest_u).
 int32_t expected_grad_dest_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t flags, const double *cot, const double *gnext, double *grad_pd, double *grad_pi0,
-                                   double *grad_dest)
+                                   double *grad_dest, bool sparse = false)
 {
     int32_t rc = exp_tables_ready(c, "expected");
     if (rc != CPM_OK) return rc;
-    if ((rc = tangent_ready(c, "expected_grad_dest")) != CPM_OK) return rc;
-    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;
+    if ((rc = sparse ? sdp_ready(c, "expected_sparse_grad_dest") : tangent_ready(c, "expected_grad_dest")) != CPM_OK) return rc;
+    if ((rc = sparse ? ensure_exps(c) : ensure_exp_aux(c)) != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
     const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
@@ -1822,18 +1864,22 @@ int32_t expected_grad_dest_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t fla
     HIP_TRY(hipGetLastError());
     for (int s = 0; s + 1 < steps; ++s) {
         const int t = hour_of(s), t_next = hour_of(s + 1);
-        launch_exp_hour<1>(c, t, pd + static_cast<size_t>(t) * Z, pd + static_cast<size_t>(t_next) * Z, 0, ws_pi + static_cast<size_t>(s) * Zs, ws_x[s & 1],
-                           ws_pi + static_cast<size_t>(s + 1) * Zs, ws_x[(s + 1) & 1], nullptr, nullptr, 0, Zs, 1);
+        (sparse ? launch_exps_hour<1> : launch_exp_hour<1>)(c, t, pd + static_cast<size_t>(t) * Z, pd + static_cast<size_t>(t_next) * Z, 0,
+                                                            ws_pi + static_cast<size_t>(s) * Zs, ws_x[s & 1], ws_pi + static_cast<size_t>(s + 1) * Zs,
+                                                            ws_x[(s + 1) & 1], nullptr, nullptr, 0, Zs, 1);
         HIP_TRY(hipGetLastError());
     }
 
+    const int *const d_ell = sparse ? c->d_exps_ell.get() : c->d_exp_ell.get();
+    const double *const d_r = sparse ? c->d_exps_r.get() : c->d_exp_r.get();
     const double *mu = gnext;  // (nullptr: zero by construction, the products of the last operator are skipped)
     for (int s = steps - 1; s >= 0; --s) {
         const int t = hour_of(s), j = s - pre;
         const size_t row = static_cast<size_t>(t) * Z;
         if (mu) {
             const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg));
-            if (Z & 1) cpm::launch(cpm::k_exp_grad_dest_u<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, c->d_tan + row * Z, mu, Z, Zs, seg_len,
+            if (sparse) launch_exps_grad_dest_u(c, row, mu, Zs, nseg, seg_len, part, part_dp);
+            else if (Z & 1) cpm::launch(cpm::k_exp_grad_dest_u<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, c->d_tan + row * Z, mu, Z, Zs, seg_len,
                                    part, part_dp);
             else cpm::launch(cpm::k_exp_grad_dest_u<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, c->d_p + row * Z, c->d_tan + row * Z, mu, Z, Zs, seg_len,
                              part, part_dp);
@@ -1843,7 +1889,7 @@ int32_t expected_grad_dest_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t fla
         const double *gp = j >= 0 ? cot + static_cast<size_t>(j) * Z : nullptr;
         const double *gd = j >= 0 ? cot + zt + static_cast<size_t>(j) * Z : nullptr;
         cpm::launch(cpm::k_exp_grad_dest_finish, dim3(nblk(Z, cpm::kFinishBlock)), dim3(cpm::kFinishBlock), 0, c->stream, part, part_dp, nseg, Zs,
-                    c->d_last + row, c->d_exp_ell + row, c->d_exp_r + row, pd + row, ws_pi + static_cast<size_t>(s) * Zs, mu, gp, gd, Z, s < pre ? 1 : 0, mu_out,
+                    c->d_last + row, d_ell + row, d_r + row, pd + row, ws_pi + static_cast<size_t>(s) * Zs, mu, gp, gd, Z, s < pre ? 1 : 0, mu_out,
                     grad_pd + row, grad_dest + row);
         HIP_TRY(hipGetLastError());
         mu = mu_out;
@@ -1852,7 +1898,7 @@ int32_t expected_grad_dest_enqueue(cpm_ctx *c, const double *d_pi0, uint32_t fla
 }
 
 int32_t expected_grad_dest_blocking(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
-                                    double *grad_pd, double *grad_pi0, double *grad_dest)
+                                    double *grad_pd, double *grad_pi0, double *grad_dest, bool sparse = false)
 {
     const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T);
     int32_t rc = check_pi0(c, pi0);
@@ -1870,7 +1916,7 @@ int32_t expected_grad_dest_blocking(cpm_ctx *c, const double *pi0, uint32_t flag
     HIP_TRY(hipMemcpyAsync(d_cot + zt, g_driving, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
     if (g_next) HIP_TRY(hipMemcpyAsync(d_gnext, g_next, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
     if (pi0) HIP_TRY(hipMemcpyAsync(d_pi0, pi0, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
-    rc = expected_grad_dest_enqueue(c, pi0 ? d_pi0 : nullptr, flags, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr, c->d_exp_gdio);
+    rc = expected_grad_dest_enqueue(c, pi0 ? d_pi0 : nullptr, flags, d_cot, g_next ? d_gnext : nullptr, d_grad, grad_pi0 ? d_gpi0 : nullptr, c->d_exp_gdio, sparse);
     if (rc != CPM_OK) return rc;
     HIP_TRY(hipMemcpyAsync(grad_pd, d_grad, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
     if (grad_pi0) HIP_TRY(hipMemcpyAsync(grad_pi0, d_gpi0, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
@@ -1904,7 +1950,7 @@ void launch_grad_u_b(cpm_ctx *c, const double *p_t, const double *dp_t, const do
 // likewise.
 // where the batched adjoint keeps what its two halves share: the workspace's vectors and the geometry of the segments
 struct GradBatchPlan {
-    bool sparse = false;  // both halves read the compact rows and the per-table arrays of ensure_exps (no tangent there)
+    bool sparse = false;  // both halves read the compact rows and the per-table arrays of ensure_exps (the tangent, if any, is the compact one)
     int Zs = 0, nseg = 0, seg_len = 0;
     size_t nb = 0;
     double *ws_pi = nullptr, *ws_x[2] = {nullptr, nullptr}, *ws_mu[2] = {nullptr, nullptr}, *part = nullptr, *part_dp = nullptr;
@@ -1915,8 +1961,7 @@ int32_t grad_batch_plan(cpm_ctx *c, int B, bool with_dest, GradBatchPlan &pl, bo
 {
     int32_t rc = exp_tables_ready(c, "expected");
     if (rc != CPM_OK) return rc;
-    if (sparse && with_dest) return fail(CPM_ERR_ARG, "expected_sparse: the p_destin tangent is a dense array: no sparse form reads it");
-    if (with_dest && (rc = tangent_ready(c, "expected_grad_dest_batch")) != CPM_OK) return rc;
+    if (with_dest && (rc = sparse ? sdp_ready(c, "expected_sparse_grad_dest_batch") : tangent_ready(c, "expected_grad_dest_batch")) != CPM_OK) return rc;
     if ((rc = sparse ? ensure_exps(c) : ensure_exp_aux(c)) != CPM_OK) return rc;
     pl.sparse = sparse;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
@@ -1980,14 +2025,14 @@ int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags,
     const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
     auto hour_of = [pre](int s) { return s < pre ? s : s - pre; };
 
-    const bool sparse = pl.sparse;  // (grad_dest == nullptr then: grad_batch_plan refused the tangent)
+    const bool sparse = pl.sparse;  // (with grad_dest: the tangent is the compact one, grad_batch_plan has checked it)
     const int *const d_ell = sparse ? c->d_exps_ell.get() : c->d_exp_ell.get();
     const double *const d_r = sparse ? c->d_exps_r.get() : c->d_exp_r.get();
     bool have_mu = gnext != nullptr;  // (false: zero by construction, the products of the last operator are skipped for every fleet)
     for (int s = steps - 1; s >= 0; --s) {
         const int t = hour_of(s), j = s - pre;
         const size_t row = static_cast<size_t>(t) * Z;
-        const double *p_t = sparse ? nullptr : c->d_p + row * Z, *dp_t = grad_dest ? c->d_tan + row * Z : nullptr;
+        const double *p_t = sparse ? nullptr : c->d_p + row * Z, *dp_t = grad_dest && !sparse ? c->d_tan + row * Z : nullptr;
         const int acc = s < pre ? 1 : 0;
         for (int f0 = 0; f0 < B; f0 += cpm::kExpMaxNB) {
             const int nf = std::min(B - f0, cpm::kExpMaxNB);
@@ -2006,7 +2051,8 @@ int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags,
                 if (mu) {
                     const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg)), block(cpm::kExpBlock);
                     if (sparse) {
-                        launch_exps_grad_u(c, row, mu, Zs, nseg, seg_len, part);
+                        if (dest_t) launch_exps_grad_dest_u(c, row, mu, Zs, nseg, seg_len, part, part_dp);
+                        else launch_exps_grad_u(c, row, mu, Zs, nseg, seg_len, part);
                     } else if (dp_t) {
                         if (Z & 1) cpm::launch(cpm::k_exp_grad_dest_u<true>, grid, block, 0, c->stream, p_t, dp_t, mu, Z, Zs, seg_len, part, part_dp);
                         else cpm::launch(cpm::k_exp_grad_dest_u<false>, grid, block, 0, c->stream, p_t, dp_t, mu, Z, Zs, seg_len, part, part_dp);
@@ -2027,7 +2073,11 @@ int32_t grad_batch_backward(cpm_ctx *c, const GradBatchPlan &pl, uint32_t flags,
                     cpm::launch(cpm::k_exp_grad_pack_b, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(NB)), dim3(cpm::kExpBlock), 0, c->stream,
                                 gnext + static_cast<size_t>(f0) * Z, Z, NB, nf, packed);
                 }
-                if (sparse) {
+                if (sparse && dest_t) {
+                    using Gd = void (*)(cpm_ctx *, size_t, const double *, int, int, int, int, double *, double *);
+                    const Gd gd_b = NB == 8 ? Gd(launch_exps_grad_dest_u_b<8>) : NB == 4 ? Gd(launch_exps_grad_dest_u_b<4>) : Gd(launch_exps_grad_dest_u_b<2>);
+                    gd_b(c, row, mu, Zs, nseg, seg_len, nf, part, part_dp);
+                } else if (sparse) {
                     using Gs = void (*)(cpm_ctx *, size_t, const double *, int, int, int, int, double *);
                     const Gs gs = NB == 8 ? Gs(launch_exps_grad_u_b<8>) : NB == 4 ? Gs(launch_exps_grad_u_b<4>) : Gs(launch_exps_grad_u_b<2>);
                     gs(c, row, mu, Zs, nseg, seg_len, nf, part);
@@ -2159,12 +2209,38 @@ int32_t trip_tangent_enqueue(cpm_ctx *c, double *d_dw)
     return CPM_OK;
 }
 
+// ... from the compact tangent (include/cpm_expected_sparse_dest.h): k_exps_trip on the rows of d_sdp in place of those of d_sp, then
+// the same finishing kernel.  Neither d_p nor d_tan is read.
+int32_t trip_tangent_sparse_enqueue(cpm_ctx *c, double *d_dw)
+{
+    int32_t rc = exp_tables_ready(c, "expected_sparse_trip_tangent");
+    if (rc != CPM_OK) return rc;
+    if (!c->sparse_tables) return exps_no_rows();
+    if ((rc = sdp_ready(c, "expected_sparse_trip_tangent")) != CPM_OK) return rc;
+    if (!c->have_dmat)
+        return fail(CPM_ERR_STATE, "expected_sparse_trip_tangent: datamatrix not set (cpm_set_datamatrix, cpm_createdatamatrix_* or cpm_synth_datamatrix)");
+    if (!c->have_dist) return fail(CPM_ERR_STATE, "expected_sparse_trip_tangent: distance matrix not set (cpm_set_distance* or the dist of cpm_set_datamatrix)");
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t zt = static_cast<size_t>(Z) * T;
+    const int nseg = cpm::trip_segments(Z, T), seg_len = cpm::trip_segment_len(Z, nseg);
+    HIP_TRY(c->d_exp_wpart.reserve(2 * zt * nseg));  // (scratch of the trip weights' own build: nothing reads it afterwards)
+    cpm::launch(cpm::k_exps_trip, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(T)), dim3(cpm::kExpsGradBlock), 0, c->stream,
+                static_cast<const double *>(c->d_sdp.get()), static_cast<const uint32_t *>(c->d_sj.get()), static_cast<const uint32_t *>(c->d_scnt.get()),
+                cpm::kDsCap, static_cast<const double *>(c->d_dm.get()), static_cast<const double *>(c->d_dist.get()), Z, T, seg_len, nseg,
+                c->d_exp_wpart.get());
+    HIP_TRY(hipGetLastError());
+    cpm::launch(cpm::k_exp_trip_tan_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream,
+                static_cast<const double *>(c->d_exp_wpart.get()), nseg, static_cast<const double *>(c->d_last), Z, T, d_dw);
+    HIP_TRY(hipGetLastError());
+    return CPM_OK;
+}
+
 // ------------------------------------------------------------------ value and gradient of the objectives (include/cpm_expected_fit.h)
 constexpr int kFitMaxT = 2048;  // (the hours' sums of a workgroup live in LDS; an argmin and an argmax share a word)
 
 // what every entry checks before anything is enqueued, behind exp_enter; B and the parameter arrays included
 int32_t fit_check(cpm_ctx *c, const char *what, int32_t B, const double *p_min, const double *p_max, const double *e_drive, uint32_t flags, const double *weights,
-                  const void *record)
+                  const void *record, bool sparse = false)
 {
     if (B < 1 || B > CPM_MAX_BATCH) return fail(CPM_ERR_ARG, "%s: B = %d outside 1..%d", what, B, CPM_MAX_BATCH);
     if (!p_min || !p_max || !e_drive) return fail(CPM_ERR_ARG, "%s: null parameter array", what);
@@ -2179,7 +2255,7 @@ int32_t fit_check(cpm_ctx *c, const char *what, int32_t B, const double *p_min, 
     if (!c->have_dist) return fail(CPM_ERR_STATE, "%s: distance matrix not set (cpm_set_distance* or the dist of cpm_set_datamatrix)", what);
     int32_t rc = exp_tables_ready(c, what);
     if (rc != CPM_OK) return rc;
-    if ((flags & CPM_FIT_DEST) && (rc = tangent_ready(c, what)) != CPM_OK) return rc;
+    if ((flags & CPM_FIT_DEST) && (rc = sparse ? sdp_ready(c, what) : tangent_ready(c, what)) != CPM_OK) return rc;
     for (int b = 0; b < B; ++b) {
         if (weights[3 * b] != 0.0 && !c->have_act_meas)
             return fail(CPM_ERR_STATE, "%s: fleet %d weighs activity_error, but no measured activity is installed (cpm_set_measured_activity)", what, b + 1);
@@ -2220,7 +2296,8 @@ FitLayout fit_layout(const cpm_ctx *c, int B)
 }
 
 // The whole call, enqueued on the context's stream; fit_check has passed.  Outputs that are nullptr stay in the workspace.
-// sparse: the propagation, the trip weights (d_exps_w) and the adjoint read the compact rows; CPM_FIT_DEST is refused by the entries.
+// sparse: the propagation, the trip weights (d_exps_w) and the adjoint read the compact rows, CPM_FIT_DEST the compact tangent (the
+// entries refuse it where none is installed).
 int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const double *p_max, const double *e_drive, const double *d_pi0, uint32_t flags,
                              const double *weights, double *d_record, double *d_expected, double *d_cot, double *d_grad_pd, double *d_grad_dest,
                              bool sparse = false)
@@ -2235,12 +2312,19 @@ int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const doubl
     if ((rc = sparse ? ensure_exps_trip(c) : ensure_exp_trip(c)) != CPM_OK) return rc;
     bool direct = false;
     for (int b = 0; b < B; ++b) direct = direct || (dest && weights[3 * b + 2] != 0.0);
-    if (direct && (c->fit_dw_gen != c->tan_gen || c->fit_dw_builds != c->exp_trip_builds)) {
+    if (direct && !sparse && (c->fit_dw_gen != c->tan_gen || c->fit_dw_builds != c->exp_trip_builds)) {
         c->fit_dw_gen = -1;
         HIP_TRY(c->d_fit_dw.reserve(2 * zt));
         if ((rc = trip_tangent_enqueue(c, c->d_fit_dw)) != CPM_OK) return rc;
         c->fit_dw_gen = c->tan_gen;
         c->fit_dw_builds = c->exp_trip_builds;
+    }
+    if (direct && sparse && (c->fits_dw_gen != c->sdp_gen || c->fits_dw_builds != c->exps_trip_builds)) {  // (a cache of its own, as d_exps_w is)
+        c->fits_dw_gen = -1;
+        HIP_TRY(c->d_fits_dw.reserve(2 * zt));
+        if ((rc = trip_tangent_sparse_enqueue(c, c->d_fits_dw)) != CPM_OK) return rc;
+        c->fits_dw_gen = c->sdp_gen;
+        c->fits_dw_builds = c->exps_trip_builds;
     }
     if ((rc = ensure_batch_tables(c, B)) != CPM_OK) return rc;
     if ((rc = ensure_pdrive_mean(c)) != CPM_OK) return rc;
@@ -2305,7 +2389,8 @@ int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const doubl
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cpm::k_fit_chain, dim3(static_cast<unsigned>(l.nchunk), static_cast<unsigned>(B)), dim3(cpm::kExpBlock), 0, c->stream,
                        static_cast<const double *>(grad_pd), static_cast<const double *>(grad_dest), static_cast<const double *>(expected),
-                       direct ? static_cast<const double *>(c->d_fit_dw.get()) : nullptr, static_cast<const double *>(c->d_pdrive_mean.get()),
+                       direct ? static_cast<const double *>(sparse ? c->d_fits_dw.get() : c->d_fit_dw.get()) : nullptr,
+                       static_cast<const double *>(c->d_pdrive_mean.get()),
                        static_cast<const double *>(ws + l.range), static_cast<const double *>(par_dev), static_cast<const double *>(w_dev), Z, zt, ws + l.cpart);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cpm::k_fit_chain_total, dim3(static_cast<unsigned>(B)), dim3(64), 0, c->stream, static_cast<const double *>(ws + l.cpart), l.nchunk,
@@ -2642,6 +2727,12 @@ int32_t cpm_get_info(cpm_ctx *c, int32_t what, int64_t *value_out)
         return CPM_OK;
     case CPM_INFO_P_DENSE:
         *value_out = c->have_cdf && (c->sparse_tables ? c->p_dense_valid : c->d_p.get() != nullptr) ? 1 : 0;
+        return CPM_OK;
+    case CPM_INFO_DEST_TANGENT_DENSE:
+        *value_out = c->tan_valid && c->d_tan ? 1 : 0;
+        return CPM_OK;
+    case CPM_INFO_DEST_TANGENT_COMPACT:
+        *value_out = c->sdp_valid && c->d_sdp ? 1 : 0;
         return CPM_OK;
     case CPM_INFO_LAST_KERNEL:
     case CPM_INFO_LAST_FORM:
@@ -4326,15 +4417,18 @@ int32_t cpm_expected_fit(cpm_ctx *c, int32_t B, const double *p_min, const doubl
     return expected_fit_blocking(c, B, p_min, p_max, e_drive, pi0, flags, weights, record, expected, cotangent, grad_p_drive, grad_dest, false);
 }
 
-// ... from the compact rows (include/cpm_expected_sparse_grad.h): the e_dest direction needs the p_destin tangent, a dense array
+// ... from the compact rows (include/cpm_expected_sparse_grad.h): the e_dest direction needs the compact tangent of
+// include/cpm_expected_sparse_dest.h; the dense one is never read
 static int32_t fit_sparse_check(cpm_ctx *c, const char *what, int32_t B, const double *p_min, const double *p_max, const double *e_drive, uint32_t flags,
                          const double *weights, const void *record, const void *grad_dest)
 {
-    if (flags & CPM_FIT_DEST)
-        return fail(CPM_ERR_ARG, "%s: CPM_FIT_DEST: the p_destin tangent is a dense [T][Z][Z] array, which the sparse calls never read (cpm_expected_fit)", what);
-    int32_t rc = fit_check(c, what, B, p_min, p_max, e_drive, flags, weights, record);
+    if ((flags & CPM_FIT_DEST) && !(c->sdp_valid && c->d_sdp))
+        return fail(CPM_ERR_ARG, "%s: CPM_FIT_DEST: the p_destin tangent is a dense [T][Z][Z] array, which the sparse calls never read (cpm_expected_fit); "
+                                 "install a compact one with cpm_build_p_dest_tangent_sparse or cpm_set_p_dest_tangent_sparse",
+                    what);
+    int32_t rc = fit_check(c, what, B, p_min, p_max, e_drive, flags, weights, record, true);
     if (rc != CPM_OK) return rc;
-    if (grad_dest) return fail(CPM_ERR_ARG, "%s: grad_dest without CPM_FIT_DEST", what);
+    if (grad_dest && !(flags & CPM_FIT_DEST)) return fail(CPM_ERR_ARG, "%s: grad_dest without CPM_FIT_DEST", what);
     return exps_rows_ready(c, what);
 }
 
@@ -4345,7 +4439,8 @@ int32_t cpm_expected_sparse_fit_dev(cpm_ctx *c, int32_t B, const double *p_min, 
     if (rc != CPM_OK) return rc;
     if ((rc = fit_sparse_check(c, "expected_sparse_fit_dev", B, p_min, p_max, e_drive, flags, weights, d_record, d_grad_dest)) != CPM_OK) return rc;
     return expected_fit_enqueue(c, B, p_min, p_max, e_drive, static_cast<const double *>(d_pi0), flags, weights, static_cast<double *>(d_record),
-                                static_cast<double *>(d_expected), static_cast<double *>(d_cotangent), static_cast<double *>(d_grad_p_drive), nullptr, true);
+                                static_cast<double *>(d_expected), static_cast<double *>(d_cotangent), static_cast<double *>(d_grad_p_drive),
+                                static_cast<double *>(d_grad_dest), true);
 }
 
 int32_t cpm_expected_sparse_fit(cpm_ctx *c, int32_t B, const double *p_min, const double *p_max, const double *e_drive, const double *pi0, uint32_t flags,
@@ -4354,7 +4449,197 @@ int32_t cpm_expected_sparse_fit(cpm_ctx *c, int32_t B, const double *p_min, cons
     int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
     if ((rc = fit_sparse_check(c, "expected_sparse_fit", B, p_min, p_max, e_drive, flags, weights, record, grad_dest)) != CPM_OK) return rc;
-    return expected_fit_blocking(c, B, p_min, p_max, e_drive, pi0, flags, weights, record, expected, cotangent, grad_p_drive, nullptr, true);
+    return expected_fit_blocking(c, B, p_min, p_max, e_drive, pi0, flags, weights, record, expected, cotangent, grad_p_drive, grad_dest, true);
+}
+
+// ------------------------------------------------------------------ the e_dest direction from a compact tangent (include/cpm_expected_sparse_dest.h)
+// what the three calls that install or read the compact tangent need: tables with compact rows, and the table itself
+static int32_t sdp_reserve(cpm_ctx *c, const char *what)
+{
+    int32_t rc = exps_rows_ready(c, what);
+    if (rc != CPM_OK) return rc;
+    HIP_TRY(c->d_sdp.reserve(static_cast<size_t>(c->T) * c->Z * cpm::kDsCap));
+    return CPM_OK;
+}
+
+int32_t cpm_build_p_dest_tangent_sparse(cpm_ctx *c)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (!c->have_cdf || !c->dest_built)
+        return fail(CPM_ERR_STATE, "build_p_dest_tangent_sparse: the installed p_destin tables do not come from cpm_build_p_dest on the resident datamatrix");
+    if (!c->have_dmat) return fail(CPM_ERR_STATE, "build_p_dest_tangent_sparse: no datamatrix is resident");
+    if (!(c->dest_built_e > 0.0))
+        return fail(CPM_ERR_STATE, "build_p_dest_tangent_sparse: the tables were built with e_dest = %g; the tangent needs e_dest > 0", c->dest_built_e);
+    if (!c->sparse_tables) return exps_no_rows();
+    if (c->tables_uploaded || !c->ds_valid || !c->ds_ok)
+        return fail(CPM_ERR_STATE, "build_p_dest_tangent_sparse: the compact rows these tables were built from are gone");
+    c->sdp_valid = false;
+    if ((rc = sdp_reserve(c, "build_p_dest_tangent_sparse")) != CPM_OK) return rc;
+    const int64_t rows = c->T * c->Z;
+    cpm::launch(cpm::k_exps_tan_cells, dim3(nblk(rows, 64)), dim3(64), 0, c->stream, c->d_ds_cells.get(), c->d_sp.get(), c->d_sj.get(), c->d_scnt.get(),
+                cpm::kDsCap, rows, static_cast<int>(c->Z), c->d_sdp.get());
+    HIP_TRY(hipGetLastError());
+    c->sdp_valid = true;
+    ++c->sdp_gen;
+    return CPM_OK;
+}
+
+int32_t cpm_set_p_dest_tangent_sparse(cpm_ctx *c, const double *dp)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!dp) return fail(CPM_ERR_ARG, "set_p_dest_tangent_sparse: null dp");
+    CTX_TRY(c);
+    if ((rc = exps_rows_ready(c, "set_p_dest_tangent_sparse")) != CPM_OK) return rc;
+    const size_t Z = static_cast<size_t>(c->Z), T = static_cast<size_t>(c->T), block = Z * Z;
+    for (size_t i = 0; i < block * T; ++i)
+        if (!std::isfinite(dp[i]))
+            return fail(CPM_ERR_ARG, "set_p_dest_tangent_sparse: the entry of origin %lld, destination %lld, hour %lld is not finite", (long long)(i % Z) + 1,
+                        (long long)(i / Z % Z) + 1, (long long)(i / block) + 1);
+    // first every hour is checked against the stored cells, then every hour is moved: a refused array leaves the installed tangent alone
+    HIP_TRY(c->d_sdp_stage.reserve(block));
+    HIP_TRY(c->d_sdp_bad.reserve(1));
+    HIP_TRY(c->h_sdp_bad.reserve(1));
+    HIP_TRY(hipMemsetAsync(c->d_sdp_bad, 0xff, sizeof(unsigned long long), c->stream));
+    const int Zi = static_cast<int>(Z);
+    for (size_t t = 0; t < T; ++t) {
+        HIP_TRY(hipMemcpyAsync(c->d_sdp_stage, dp + t * block, sizeof(double) * block, hipMemcpyHostToDevice, c->stream));
+        cpm::launch(cpm::k_exps_tan_check, dim3(nblk(c->Z, 256), static_cast<unsigned>(Z)), dim3(256), 0, c->stream,
+                    static_cast<const double *>(c->d_sdp_stage.get()), static_cast<const uint32_t *>(c->d_sj + t * Z * cpm::kDsCap),
+                    static_cast<const uint32_t *>(c->d_scnt + t * Z), cpm::kDsCap, Zi, static_cast<unsigned long long>(t * block), c->d_sdp_bad.get());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_sdp_bad, c->d_sdp_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const unsigned long long bad = *c->h_sdp_bad;
+    if (bad != ~0ull) {
+        c->d_sdp_stage.release();
+        return fail(CPM_ERR_TABLE, "set_p_dest_tangent_sparse: the entry of hour %llu, origin %llu, destination %llu is not zero, but the compact rows do not "
+                                   "store that cell",
+                    bad / block + 1, bad % Z + 1, bad / Z % Z + 1);
+    }
+    c->sdp_valid = false;
+    if ((rc = sdp_reserve(c, "set_p_dest_tangent_sparse")) != CPM_OK) return rc;
+    for (size_t t = 0; t < T; ++t) {
+        HIP_TRY(hipMemcpyAsync(c->d_sdp_stage, dp + t * block, sizeof(double) * block, hipMemcpyHostToDevice, c->stream));
+        cpm::launch(cpm::k_exps_tan_gather, dim3(nblk(cpm::kDsCap, 64), static_cast<unsigned>(Z)), dim3(64), 0, c->stream,
+                    static_cast<const double *>(c->d_sdp_stage.get()), static_cast<const uint32_t *>(c->d_sj + t * Z * cpm::kDsCap),
+                    static_cast<const uint32_t *>(c->d_scnt + t * Z), cpm::kDsCap, Zi, c->d_sdp + t * Z * cpm::kDsCap);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->d_sdp_stage.release();
+    c->sdp_valid = true;
+    ++c->sdp_gen;
+    return CPM_OK;
+}
+
+int32_t cpm_get_p_dest_tangent_sparse(cpm_ctx *c, double *out)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!out) return fail(CPM_ERR_ARG, "get_p_dest_tangent_sparse: null out");
+    CTX_TRY(c);
+    if ((rc = exps_rows_ready(c, "get_p_dest_tangent_sparse")) != CPM_OK) return rc;
+    if ((rc = sdp_ready(c, "get_p_dest_tangent_sparse")) != CPM_OK) return rc;
+    const size_t Z = static_cast<size_t>(c->Z), T = static_cast<size_t>(c->T), block = Z * Z;
+    HIP_TRY(c->d_sdp_stage.reserve(block));
+    for (size_t t = 0; t < T; ++t) {
+        HIP_TRY(hipMemsetAsync(c->d_sdp_stage, 0, sizeof(double) * block, c->stream));
+        cpm::launch(cpm::k_exps_tan_scatter, dim3(nblk(cpm::kDsCap, 64), static_cast<unsigned>(Z)), dim3(64), 0, c->stream,
+                    static_cast<const double *>(c->d_sdp + t * Z * cpm::kDsCap), static_cast<const uint32_t *>(c->d_sj + t * Z * cpm::kDsCap),
+                    static_cast<const uint32_t *>(c->d_scnt + t * Z), cpm::kDsCap, static_cast<int>(Z), c->d_sdp_stage.get());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out + t * block, c->d_sdp_stage, sizeof(double) * block, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->d_sdp_stage.release();
+    return CPM_OK;
+}
+
+int32_t cpm_expected_sparse_grad_dest_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext, void *d_grad_p_drive,
+                                          void *d_grad_pi0, void *d_grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_sparse_grad_dest_dev: null d_cotangent");
+    if (!d_grad_p_drive || !d_grad_dest) return fail(CPM_ERR_ARG, "expected_sparse_grad_dest_dev: null d_grad_p_drive or d_grad_dest");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected")) != CPM_OK) return rc;
+    return expected_grad_dest_enqueue(c, static_cast<const double *>(d_pi0), flags, static_cast<const double *>(d_cotangent),
+                                      static_cast<const double *>(d_gnext), static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0),
+                                      static_cast<double *>(d_grad_dest), true);
+}
+
+int32_t cpm_expected_sparse_grad_dest(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving, const double *g_next,
+                                      double *grad_p_drive, double *grad_pi0, double *grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_sparse_grad_dest: null cotangents");
+    if (!grad_p_drive || !grad_dest) return fail(CPM_ERR_ARG, "expected_sparse_grad_dest: null grad_p_drive or grad_dest");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, false, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected")) != CPM_OK) return rc;  // (state is refused before a cotangent is read or copied)
+    if ((rc = sdp_ready(c, "expected_sparse_grad_dest")) != CPM_OK) return rc;
+    return expected_grad_dest_blocking(c, pi0, flags, g_parking, g_driving, g_next, grad_p_drive, grad_pi0, grad_dest, true);
+}
+
+int32_t cpm_expected_sparse_grad_dest_batch_dev(cpm_ctx *c, const void *d_pi0, uint32_t flags, const void *d_cotangent, const void *d_gnext,
+                                                void *d_grad_p_drive, void *d_grad_pi0, void *d_grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_cotangent) return fail(CPM_ERR_ARG, "expected_sparse_grad_dest_batch_dev: null d_cotangent");
+    if (!d_grad_p_drive || !d_grad_dest) return fail(CPM_ERR_ARG, "expected_sparse_grad_dest_batch_dev: null d_grad_p_drive or d_grad_dest");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected")) != CPM_OK) return rc;
+    return expected_grad_batch_enqueue(c, static_cast<const double *>(d_pi0), flags, tb.B, tb.pd, tb.q_stride, static_cast<const double *>(d_cotangent),
+                                       static_cast<const double *>(d_gnext), static_cast<double *>(d_grad_p_drive), static_cast<double *>(d_grad_pi0),
+                                       static_cast<double *>(d_grad_dest), true);
+}
+
+int32_t cpm_expected_sparse_grad_dest_batch(cpm_ctx *c, const double *pi0, uint32_t flags, const double *g_parking, const double *g_driving,
+                                            const double *g_next, double *grad_p_drive, double *grad_pi0, double *grad_dest)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!g_parking || !g_driving) return fail(CPM_ERR_ARG, "expected_sparse_grad_dest_batch: null cotangents");
+    if (!grad_p_drive || !grad_dest) return fail(CPM_ERR_ARG, "expected_sparse_grad_dest_batch: null grad_p_drive or grad_dest");
+    ExpTables tb;
+    if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
+    if ((rc = exps_rows_ready(c, "expected")) != CPM_OK) return rc;  // (state is refused before a cotangent is read or copied)
+    if ((rc = sdp_ready(c, "expected_sparse_grad_dest_batch")) != CPM_OK) return rc;
+    return expected_grad_batch_blocking(c, "expected_sparse_grad_dest_batch", pi0, flags, tb.B, tb.pd, tb.q_stride, g_parking, g_driving, g_next, grad_p_drive,
+                                        grad_pi0, grad_dest, true);
+}
+
+int32_t cpm_expected_sparse_trip_tangent_dev(cpm_ctx *c, void *d_dw)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_dw) return fail(CPM_ERR_ARG, "expected_sparse_trip_tangent_dev: null d_dw");
+    CTX_TRY(c);
+    return trip_tangent_sparse_enqueue(c, static_cast<double *>(d_dw));
+}
+
+int32_t cpm_expected_sparse_trip_tangent(cpm_ctx *c, double *dw_sec, double *dw_km)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!dw_sec || !dw_km) return fail(CPM_ERR_ARG, "expected_sparse_trip_tangent: null outputs");
+    CTX_TRY(c);
+    const size_t zt = static_cast<size_t>(c->Z) * c->T;
+    HIP_TRY(c->d_tan_w.reserve(2 * zt));
+    if ((rc = trip_tangent_sparse_enqueue(c, c->d_tan_w)) != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(dw_sec, c->d_tan_w, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dw_km, c->d_tan_w + zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
 }
 
 // ------------------------------------------------------------------ forward tangent of the expected densities (include/cpm_expected_tangent.h)

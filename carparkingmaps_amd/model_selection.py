@@ -277,7 +277,12 @@ class Evaluator:
     refine_expected_lm, the adjoint, the trip weights and the fit are the dense calls as before: the tangent of p_destin is a dense
     array.  The bits are the default Evaluator's on one condition (include/cpm_expected_sparse_grad.h): every mean of the datamatrix
     and every distance at a cell p_destin does NOT store is finite.  The dense trip weights form 0 * value there, so a NaN mean at
-    a cell of zero count makes the default Evaluator's travel product, A_drive and their gradients NaN where the sparse ones are not."""
+    a cell of zero count makes the default Evaluator's travel product, A_drive and their gradients NaN where the sparse ones are not.
+
+    expected_sparse_dest=True (with expected_sparse=True) keeps the tangent of p_destin on the stored cells as well
+    (include/cpm_expected_sparse_dest.h): expected_gradient[_batch], expected_fit and refine_expected with dest=True then run from the
+    compact rows end to end, with the same bits, and neither the dense p_destin array nor the dense tangent is ever built.
+    expected_jacobian and refine_expected_lm with dest=True keep the dense tangent."""
     sampler: object
     C: int
     seed: int
@@ -293,13 +298,19 @@ class Evaluator:
     # expected_jacobian / refine_expected_lm, the adjoint, the trip weights and the fit are the dense calls as before: the tangent of
     # p_destin is a dense array.
     expected_sparse: bool = False
+    # expected_sparse_dest: behind expected_sparse, the calls above with dest=True read a compact tangent on the stored cells
+    # (include/cpm_expected_sparse_dest.h) and stay sparse; expected_jacobian / refine_expected_lm keep the dense tangent.
+    expected_sparse_dest: bool = False
     _e_dest: object = field(default=None, repr=False)
     _pipe: object = field(default=None, repr=False)
     _s_table: object = field(default=None, repr=False)   # build_p_drive(0, 1, 1): the datamatrix's own table, for expected_gradient
     _tangent: object = field(default=None, repr=False)   # the e_dest key whose d p_destin / d e_dest is installed (expected_gradient, dest=True)
+    _tangent_compact: object = field(default=None, repr=False)   # ... and the key whose compact tangent is (expected_sparse_dest)
     _fit_measured: object = field(default=None, repr=False)   # expected_fit has installed the measured arrays in the context
 
     def __post_init__(self):
+        if self.expected_sparse_dest and not self.expected_sparse:
+            raise ValueError("Evaluator: expected_sparse_dest=True needs expected_sparse=True: the compact tangent serves the sparse calls alone")
         if self.measured_parking is not None:   # Julia order, like the count tensors: the error is evaluated hour-major on contiguous rows
             self.measured_parking = np.asfortranarray(np.asarray(self.measured_parking, dtype=np.float64))
         if self.device_objectives:
@@ -315,11 +326,22 @@ class Evaluator:
             self.sampler.build_p_dest(e_dest, want=False)
             self._e_dest = key
             self._tangent = None             # (the library drops the tangent with the tables it belonged to)
+            self._tangent_compact = None
 
-    def _install_dest_tangent(self):
-        if self._tangent != self._e_dest:    # rebuilt only when e_dest changes, like the tables
+    def _install_dest_tangent(self, dense=False):
+        """d p_destin / d e_dest of the installed tables: the compact one under expected_sparse_dest, unless the caller reads the dense
+        array (dense=True: the forward tangent)."""
+        if self.expected_sparse_dest and not dense:
+            if self._tangent_compact != self._e_dest:
+                self.sampler.build_p_dest_tangent(want=False, sparse=True)
+                self._tangent_compact = self._e_dest
+        elif self._tangent != self._e_dest:  # rebuilt only when e_dest changes, like the tables
             self.sampler.build_p_dest_tangent(want=False)
             self._tangent = self._e_dest
+
+    def _sparse(self, dest):
+        """Whether a call runs from the compact rows: with dest only where the tangent is compact too."""
+        return self.expected_sparse and (not dest or self.expected_sparse_dest)
 
     def _objectives(self, pt, parking, driving, sum_tt_q16):
         act = traffic_activity(driving)
@@ -410,10 +432,10 @@ class Evaluator:
                 raise ValueError("expected_gradient: parking_error needs measured_parking")
             gp, gd = parking_density_error_grad(r["parking"], self.measured_parking), zero
         else:
-            gp, gd = zero, a_drive_grad(s.expected_trip(sparse=self.expected_sparse and not dest)[0])
+            gp, gd = zero, a_drive_grad(s.expected_trip(sparse=self._sparse(dest))[0])
         if dest:
             self._install_dest_tangent()
-            g = s.expected_grad_dest(gp, gd, ivp=ivp)
+            g = s.expected_grad_dest(gp, gd, ivp=ivp, sparse=self._sparse(dest))
         else:
             g = s.expected_grad(gp, gd, ivp=ivp, sparse=self.expected_sparse)
         d_min, d_max, d_e = p_drive_param_grads(g["grad_p_drive"], self._s_table, pt.p_min, pt.p_max, pt.e_drive)
@@ -422,7 +444,8 @@ class Evaluator:
         if dest:
             direct = objective == "A_drive"
             out["grad_dest"] = g["grad_dest"]
-            out["d_e_dest"] = e_dest_param_grad(g["grad_dest"], r["driving"] if direct else None, s.expected_trip_tangent()[0] if direct else None)
+            out["d_e_dest"] = e_dest_param_grad(g["grad_dest"], r["driving"] if direct else None,
+                                                s.expected_trip_tangent(sparse=self._sparse(dest))[0] if direct else None)
         return out
 
     def expected_gradient_batch(self, pts, objective, ivp=True, dest=False):
@@ -446,7 +469,7 @@ class Evaluator:
         B = len(pts)
         gp = np.zeros((s.Z, s.T, B), order="F")
         gd = np.zeros((s.Z, s.T, B), order="F")
-        sparse = self.expected_sparse and not dest
+        sparse = self._sparse(dest)
         w_sec = s.expected_trip(sparse=sparse)[0] if objective == "A_drive" else None
         for b, r in enumerate(rs):
             if objective == "activity_error":
@@ -457,9 +480,9 @@ class Evaluator:
                 gd[:, :, b] = a_drive_grad(w_sec)
         if dest:
             self._install_dest_tangent()
-        g = s.expected_grad_batch(gp, gd, ivp=ivp, dest=dest, sparse=sparse)
+        g = s.expected_grad_batch(gp, gd, ivp=ivp, dest=dest, sparse=sparse, compact_tangent=sparse and dest)
         direct = dest and objective == "A_drive"
-        dw_sec = s.expected_trip_tangent()[0] if direct else None
+        dw_sec = s.expected_trip_tangent(sparse=sparse)[0] if direct else None
         outs = []
         for b, (pt, r) in enumerate(zip(pts, rs)):
             grad = np.asfortranarray(g["grad_p_drive"][:, :, b])
@@ -495,7 +518,7 @@ class Evaluator:
         rec = torch.empty(B * words, dtype=torch.float64, device=f"cuda:{s.device}")
         torch.cuda.synchronize(s.device)
         s.expected_fit_dev([pt.p_min for pt in pts], [pt.p_max for pt in pts], [pt.e_drive for pt in pts], w, rec.data_ptr(), 0, ivp, dest,
-                           sparse=self.expected_sparse and not dest)
+                           sparse=self._sparse(dest), compact_tangent=self._sparse(dest) and dest)
         s.sync()
         r = s.fit_record(rec.cpu().numpy(), s.T)
         outs = []
@@ -517,12 +540,14 @@ class Evaluator:
         are installed as expected_gradient() installs them, the direction tables d p_drive / d (p_min, p_max, e_drive) are built on the
         device (Sampler.build_p_drive_tangent_dev) and ONE tangent call (Sampler.expected_tangent_dev, include/cpm_expected_tangent.h)
         carries K = 3 directions -- 4 with dest: the last one along d p_destin / d e_dest (pt.e_dest > 0).  Returns dict(parking,
-        driving (Z, T), d_parking, d_driving (P, Z, T)) in the parameter order (e_drive, p_min, p_max[, e_dest])."""
+        driving (Z, T), d_parking, d_driving (P, Z, T)) in the parameter order (e_drive, p_min, p_max[, e_dest]).  The forward
+        tangent reads the DENSE tangent of p_destin, under expected_sparse_dest as well: it needs dP along destination columns, which
+        the compact tangent does not store."""
         import torch
         s = self.sampler
         self._install(pt)
         if dest:
-            self._install_dest_tangent()
+            self._install_dest_tangent(dense=True)
         K, zt = (4 if dest else 3), s.Z * s.T
         dev = f"cuda:{s.device}"
         built = torch.empty(3 * zt, dtype=torch.float64, device=dev)      # (p_min, p_max, e_drive), as the builder lays them out
@@ -751,14 +776,16 @@ def _project(x, lo, hi, gap):
 
 
 def refine_expected(evaluator, pts, weights=None, steps=10, bounds=None, ivp=True, step0=1.0, shrink=0.5, armijo=1e-4, max_backtracks=12,
-                    min_gap=1e-3):
+                    min_gap=1e-3, dest=False):
     """Projected gradient descent with Armijo backtracking on (e_drive, p_min, p_max) for the noise-free F of Evaluator.expected_fit:
     B starting points that share e_dest, ALL advanced by one expected_fit call per trial step (a point whose trial is refused halves
     its own step and waits for the next call; an accepted point doubles it).  bounds: dict over "e_drive", "p_min", "p_max" of
     (low, high); default e_drive in [1e-3, 16], 0 <= p_min < p_max <= 1 (min_gap apart).  A trial x+ = P(x - a * g) is accepted when
     F(x+) <= F(x) - armijo * <g, x - x+>.  Returns per point dict(path: [(Point, F), ...] of the accepted points, the start first;
     gradient: (d_e_drive, d_p_min, d_p_max) at the last one; result: expected_fit's dict there; calls: expected_fit calls made).
-    Plain host Python over the device call: nothing here is a kernel."""
+    dest: every expected_fit call also forms dF/de_dest (the points share e_dest, which stays where it is: the batch reads one p_destin
+    table), and gradient gains it as a fourth entry -- the four-parameter gradient at every accepted point, for a caller that steps
+    e_dest between refinements.  Plain host Python over the device call: nothing here is a kernel."""
     b = dict(DEFAULT_FIT_BOUNDS)
     for k, v in (bounds or {}).items():
         if k not in b:
@@ -778,7 +805,8 @@ def refine_expected(evaluator, pts, weights=None, steps=10, bounds=None, ivp=Tru
     vec = lambda r: np.array([r["d_e_drive"], r["d_p_min"], r["d_p_max"]])
     point = lambda x: Point(e_drive=float(x[0]), p_min=float(x[1]), p_max=float(x[2]), e_dest=e_dest)
     x = [_project(np.array([pt.e_drive, pt.p_min, pt.p_max], dtype=np.float64), lo, hi, min_gap) for pt in pts]
-    cur = evaluator.expected_fit([point(v) for v in x], weights, ivp=ivp)
+    fit = (lambda q: evaluator.expected_fit(q, weights, ivp=ivp, dest=True)) if dest else (lambda q: evaluator.expected_fit(q, weights, ivp=ivp))
+    cur = fit([point(v) for v in x])
     calls = 1
     paths = [[(point(x[k]), cur[k]["F"])] for k in range(B)]
     alpha = [float(step0)] * B
@@ -790,7 +818,7 @@ def refine_expected(evaluator, pts, weights=None, steps=10, bounds=None, ivp=Tru
         trial = list(x)
         for k in live:
             trial[k] = _project(x[k] - alpha[k] * vec(cur[k]), lo, hi, min_gap)
-        new = evaluator.expected_fit([point(v) for v in trial], weights, ivp=ivp)
+        new = fit([point(v) for v in trial])
         calls += 1
         for k in live:
             moved = x[k] - trial[k]
@@ -806,7 +834,8 @@ def refine_expected(evaluator, pts, weights=None, steps=10, bounds=None, ivp=Tru
             else:
                 refused[k] += 1
                 alpha[k] = alpha[k] * shrink if refused[k] <= max_backtracks else 0.0
-    return [dict(path=paths[k], gradient=tuple(vec(cur[k])), result=cur[k], calls=calls) for k in range(B)]
+    grad = lambda r: tuple(vec(r)) + ((r["d_e_dest"],) if dest else ())
+    return [dict(path=paths[k], gradient=grad(cur[k]), result=cur[k], calls=calls) for k in range(B)]
 
 
 def _lm_terms(evaluator, jac, w, w_sec):
@@ -849,7 +878,9 @@ def refine_expected_lm(evaluator, pts, weights=None, steps=10, bounds=None, ivp=
     where A_drive is weighed -- any evaluator with measured_activity / measured_parking can drive it, a numpy one included.  Weights
     of the least-squares terms must not be negative.  bounds, min_gap: as in refine_expected.  Returns per point refine_expected's dict
     -- path: [(Point, F), ...] of the accepted points, the start first; gradient: dF/d(e_drive, p_min, p_max) at the last one; result:
-    dict(F and the weighed terms) there; calls: Jacobian calls made -- plus lam, the damping it ended with."""
+    dict(F and the weighed terms) there; calls: Jacobian calls made -- plus lam, the damping it ended with.  The default Jacobian is
+    the forward tangent, which reads the dense arrays: Evaluator.expected_sparse_dest changes nothing here (a Jacobian with dest=True
+    keeps the dense tangent of p_destin)."""
     b = dict(DEFAULT_FIT_BOUNDS)
     for k, v in (bounds or {}).items():
         if k not in b:

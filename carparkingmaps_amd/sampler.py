@@ -706,28 +706,38 @@ class Sampler:
                         p(d_grad_pi0_ptr)))
 
     # -- the adjoint along a tangent of p_destin (include/cpm_expected_grad_dest.h): the derivative for e_dest --
-    def set_p_dest_tangent(self, dp):
+    def set_p_dest_tangent(self, dp, sparse=False):
         """Install a tangent of the p_destin tables: (Z, Z, T) float64 [origin, destination, hour], the layout of set_p_dest.  Every
-        call that installs p_destin tables, and every new datamatrix, drops it."""
+        call that installs p_destin tables, and every new datamatrix, drops it.  sparse: onto the stored cells of sparse tables
+        (include/cpm_expected_sparse_dest.h), hour by hour; the dense device array is not allocated, and a non-zero entry at a cell the
+        rows do not store is refused.  The two tangents are independent of each other."""
         a = _f64(dp, (self.Z, self.Z, self.T))
-        _lib.check(self._L.cpm_set_p_dest_tangent(self._h, _vp(a)))
+        call = self._L.cpm_set_p_dest_tangent_sparse if sparse else self._L.cpm_set_p_dest_tangent
+        _lib.check(call(self._h, _vp(a)))
 
-    def build_p_dest_tangent(self, want=False):
+    def build_p_dest_tangent(self, want=False, sparse=False):
         """d p_destin / d e_dest of the installed tables, built on the device from the resident datamatrix at the e_dest of the last
-        build_p_dest (which must have installed the tables, with e_dest > 0).  want: also return it, (Z, Z, T) float64 F-order."""
+        build_p_dest (which must have installed the tables, with e_dest > 0).  want: also return it, (Z, Z, T) float64 F-order.
+        sparse: the compact tangent on the stored cells, the same operations per cell; as in set_p_dest_tangent()."""
+        if sparse:
+            _lib.check(self._L.cpm_build_p_dest_tangent_sparse(self._h))
+            return self.get_p_dest_tangent(sparse=True) if want else None
         out = np.zeros((self.Z, self.Z, self.T), dtype=np.float64, order="F") if want else None
         _lib.check(self._L.cpm_build_p_dest_tangent(self._h, _vp(out)))
         return out
 
-    def get_p_dest_tangent(self):
+    def get_p_dest_tangent(self, sparse=False):
+        """The installed tangent, (Z, Z, T) float64 F-order.  sparse: the compact one, +0.0 off the stored cells."""
         out = np.zeros((self.Z, self.Z, self.T), dtype=np.float64, order="F")
-        _lib.check(self._L.cpm_get_p_dest_tangent(self._h, _vp(out)))
+        call = self._L.cpm_get_p_dest_tangent_sparse if sparse else self._L.cpm_get_p_dest_tangent
+        _lib.check(call(self._h, _vp(out)))
         return out
 
-    def expected_grad_dest(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None):
+    def expected_grad_dest(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None, sparse=False):
         """expected_grad() with one more output: dict(grad_p_drive, grad_pi0, grad_dest (Z, T) float64 F-order).  grad_dest[o, t] is the
         derivative of L along the installed tangent restricted to row (o, t) of p_destin, the residual of the row held fixed;
-        grad_dest.sum() is the derivative of L along the tangent.  grad_p_drive and grad_pi0 carry expected_grad()'s bits."""
+        grad_dest.sum() is the derivative of L along the tangent.  grad_p_drive and grad_pi0 carry expected_grad()'s bits.  sparse: from
+        the compact rows and the compact tangent (include/cpm_expected_sparse_dest.h): the same bits, neither dense array read or built."""
         a = self._pi0(pi0)
         gp = np.asfortranarray(_f64(g_parking, (self.Z, self.T)))
         gd = np.asfortranarray(_f64(g_driving, (self.Z, self.T)))
@@ -735,25 +745,36 @@ class Sampler:
         grad = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
         grad_pi0 = np.zeros(self.Z, dtype=np.float64)
         grad_dest = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
-        _lib.check(self._L.cpm_expected_grad_dest(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(gp), _vp(gd), _vp(gn), _vp(grad),
-                                                  _vp(grad_pi0), _vp(grad_dest)))
+        call = self._L.cpm_expected_sparse_grad_dest if sparse else self._L.cpm_expected_grad_dest
+        _lib.check(call(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0), _vp(grad_dest)))
         return dict(grad_p_drive=grad, grad_pi0=grad_pi0, grad_dest=grad_dest)
 
-    def expected_grad_dest_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_grad_dest_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0):
-        """Enqueue on the context's stream: the arguments of expected_grad_dev, and d_grad_dest_ptr = device address of float64[T][Z]."""
+    def expected_grad_dest_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_grad_dest_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0,
+                               sparse=False):
+        """Enqueue on the context's stream: the arguments of expected_grad_dev, and d_grad_dest_ptr = device address of float64[T][Z].
+        sparse: as in expected_grad_dest()."""
         p = lambda v: C.c_void_p(int(v)) if v else None
-        _lib.check(self._L.cpm_expected_grad_dest_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr),
-                                                      p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr), p(d_grad_dest_ptr)))
+        call = self._L.cpm_expected_sparse_grad_dest_dev if sparse else self._L.cpm_expected_grad_dest_dev
+        _lib.check(call(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr), p(d_grad_p_drive_ptr),
+                        p(d_grad_pi0_ptr), p(d_grad_dest_ptr)))
 
     # -- the adjoint for the fleets of a batch (include/cpm_expected_grad_batch.h): B gradients in one pass over p_destin --
-    def expected_grad_batch(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None, dest=False, sparse=False):
+    @staticmethod
+    def _sparse_dest(what, dest, sparse, compact_tangent):
+        """The refusals of dest with sparse, before any device call: without compact_tangent the tangent is the dense array."""
+        if compact_tangent and not sparse:
+            raise ValueError(f"{what}: compact_tangent=True needs sparse=True: the dense calls read the dense tangent")
+        if sparse and dest and not compact_tangent:
+            raise ValueError(f"{what}: dest=True has no sparse form: the p_destin tangent is a dense array (compact_tangent=True reads the "
+                             "compact one of build_p_dest_tangent(sparse=True))")
+
+    def expected_grad_batch(self, g_parking, g_driving, pi0=None, ivp=False, g_next=None, dest=False, sparse=False, compact_tangent=False):
         """expected_grad() -- dest: expected_grad_dest() -- for every fleet of the installed batch tables, blocking.  g_parking /
         g_driving: (Z, T, B) cotangents, fleet b's in [:, :, b]; g_next: (Z, B) or None (zeros for all fleets); pi0 is shared.  Returns
         dict(grad_p_drive (Z, T, B) float64 F-order, grad_pi0 (Z, B)[, grad_dest (Z, T, B)]): fleet b's slices bit for bit what the
-        B = 1 call returns with p_drive[:, :, b] installed and fleet b's cotangents.  sparse: as in expected_grad(); not with dest (the
-        tangent of p_destin is a dense array)."""
-        if sparse and dest:
-            raise ValueError("expected_grad_batch: dest=True has no sparse form: the p_destin tangent is a dense array")
+        B = 1 call returns with p_drive[:, :, b] installed and fleet b's cotangents.  sparse: as in expected_grad(); with dest only
+        under compact_tangent=True, which reads the compact tangent (include/cpm_expected_sparse_dest.h) instead of the dense array."""
+        Sampler._sparse_dest("expected_grad_batch", dest, sparse, compact_tangent)
         a = self._pi0(pi0)
         B = self.get_info(_lib.CPM_INFO_BATCH)
         if B < 1:  # (the library names what is missing; it reads no array before it does)
@@ -769,7 +790,8 @@ class Sampler:
             _lib.check(call(self._h, _vp(a), flags, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0)))
             return dict(grad_p_drive=grad, grad_pi0=grad_pi0)
         grad_dest = np.zeros((self.Z, self.T, B), dtype=np.float64, order="F")
-        _lib.check(self._L.cpm_expected_grad_dest_batch(self._h, _vp(a), flags, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0), _vp(grad_dest)))
+        call = self._L.cpm_expected_sparse_grad_dest_batch if sparse else self._L.cpm_expected_grad_dest_batch
+        _lib.check(call(self._h, _vp(a), flags, _vp(gp), _vp(gd), _vp(gn), _vp(grad), _vp(grad_pi0), _vp(grad_dest)))
         return dict(grad_p_drive=grad, grad_pi0=grad_pi0, grad_dest=grad_dest)
 
     def expected_grad_batch_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0, d_grad_pi0_ptr=0, sparse=False):
@@ -782,24 +804,28 @@ class Sampler:
                         p(d_grad_pi0_ptr)))
 
     def expected_grad_dest_batch_dev(self, d_cotangent_ptr, d_grad_p_drive_ptr, d_grad_dest_ptr, d_pi0_ptr=0, ivp=False, d_gnext_ptr=0,
-                                     d_grad_pi0_ptr=0):
+                                     d_grad_pi0_ptr=0, sparse=False):
         """Enqueue on the context's stream: the arguments of expected_grad_batch_dev, and d_grad_dest_ptr = device address of
-        float64[B][T][Z]."""
+        float64[B][T][Z].  sparse: as in expected_grad_dest()."""
         p = lambda v: C.c_void_p(int(v)) if v else None
-        _lib.check(self._L.cpm_expected_grad_dest_batch_dev(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr),
-                                                            p(d_gnext_ptr), p(d_grad_p_drive_ptr), p(d_grad_pi0_ptr), p(d_grad_dest_ptr)))
+        call = self._L.cpm_expected_sparse_grad_dest_batch_dev if sparse else self._L.cpm_expected_grad_dest_batch_dev
+        _lib.check(call(self._h, p(d_pi0_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, p(d_cotangent_ptr), p(d_gnext_ptr), p(d_grad_p_drive_ptr),
+                        p(d_grad_pi0_ptr), p(d_grad_dest_ptr)))
 
-    def expected_trip_tangent(self):
+    def expected_trip_tangent(self, sparse=False):
         """(dw_sec, dw_km), each (Z, T) float64 F-order: the derivative of expected_trip()'s weights along the installed tangent, the
-        residual of every row held fixed."""
+        residual of every row held fixed.  sparse: along the compact tangent, from the stored cells (include/cpm_expected_sparse_dest.h)."""
         dw_sec = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
         dw_km = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
-        _lib.check(self._L.cpm_expected_trip_tangent(self._h, _vp(dw_sec), _vp(dw_km)))
+        call = self._L.cpm_expected_sparse_trip_tangent if sparse else self._L.cpm_expected_trip_tangent
+        _lib.check(call(self._h, _vp(dw_sec), _vp(dw_km)))
         return dw_sec, dw_km
 
-    def expected_trip_tangent_dev(self, d_dw_ptr):
-        """Enqueue on the context's stream: d_dw_ptr = device address of float64[2][T][Z], dw_sec then dw_km."""
-        _lib.check(self._L.cpm_expected_trip_tangent_dev(self._h, C.c_void_p(int(d_dw_ptr)) if d_dw_ptr else None))
+    def expected_trip_tangent_dev(self, d_dw_ptr, sparse=False):
+        """Enqueue on the context's stream: d_dw_ptr = device address of float64[2][T][Z], dw_sec then dw_km.  sparse: as in
+        expected_trip_tangent()."""
+        call = self._L.cpm_expected_sparse_trip_tangent_dev if sparse else self._L.cpm_expected_trip_tangent_dev
+        _lib.check(call(self._h, C.c_void_p(int(d_dw_ptr)) if d_dw_ptr else None))
 
     # -- value and four-parameter gradient of the noise-free objectives (include/cpm_expected_fit.h): one call, one forward pass --
     def set_measured_activity(self, activity):
@@ -826,15 +852,15 @@ class Sampler:
         return B, lo, hi, ex, w
 
     def expected_fit_dev(self, p_min, p_max, e_drive, weights, d_record_ptr, d_pi0_ptr=0, ivp=False, dest=False, d_expected_ptr=0,
-                         d_cotangent_ptr=0, d_grad_p_drive_ptr=0, d_grad_dest_ptr=0, sparse=False):
+                         d_cotangent_ptr=0, d_grad_p_drive_ptr=0, d_grad_dest_ptr=0, sparse=False, compact_tangent=False):
         """Enqueue on the context's stream: the B points (p_min, p_max, e_drive: (B,)) with weights (B, 3) or (3,) = (w_act, w_park,
         w_adrive) into d_record_ptr = device address of float64[B][fit_words()].  The batch tables hold these points afterwards.
         d_expected_ptr / d_cotangent_ptr = device address of float64[B][2][T][Z] or 0; d_grad_p_drive_ptr / d_grad_dest_ptr = device
         address of float64[B][T][Z] or 0 (kept in the library's workspace).  dest: also dF/de_dest, along the installed tangent.
         sparse: from the compact rows of sparse tables (include/cpm_expected_sparse_grad.h): the same bits where every mean and distance
-        at a cell that is not stored is finite (the dense trip weights form 0 * value there); not with dest."""
-        if sparse and dest:
-            raise ValueError("expected_fit_dev: dest=True has no sparse form: the p_destin tangent is a dense array")
+        at a cell that is not stored is finite (the dense trip weights form 0 * value there); with dest only under compact_tangent=True,
+        which reads the compact tangent (include/cpm_expected_sparse_dest.h) instead of the dense array."""
+        Sampler._sparse_dest("expected_fit_dev", dest, sparse, compact_tangent)
         B, lo, hi, ex, w = self._fit_args(p_min, p_max, e_drive, weights)
         p = lambda v: C.c_void_p(int(v)) if v else None
         flags = (_lib.CPM_EXPECT_IVP if ivp else 0) | (_lib.CPM_FIT_DEST if dest else 0)
@@ -854,14 +880,13 @@ class Sampler:
         out["record"] = rec
         return out
 
-    def expected_fit(self, p_min, p_max, e_drive, weights, pi0=None, ivp=False, dest=False, want=(), sparse=False):
+    def expected_fit(self, p_min, p_max, e_drive, weights, pi0=None, ivp=False, dest=False, want=(), sparse=False, compact_tangent=False):
         """Value and gradient of F = w_act * activity_error + w_park * parking_error + w_adrive * A_drive at B points, blocking: a dict
         of (B,) arrays F, activity_error, parking_error, A_drive, n_valid, d_p_min, d_p_max, d_e_drive, d_e_dest (NaN without dest),
         total_seconds, total_km, traffic_activity (B, T) and record (B, fit_words()).  want: names among "expected", "cotangent" (each
-        (B, 2, T, Z): parking then driving, hour-major), "grad_p_drive", "grad_dest" ((Z, T, B) F-order) to return as well.  sparse: as in
-        expected_fit_dev()."""
-        if sparse and dest:
-            raise ValueError("expected_fit: dest=True has no sparse form: the p_destin tangent is a dense array")
+        (B, 2, T, Z): parking then driving, hour-major), "grad_p_drive", "grad_dest" ((Z, T, B) F-order) to return as well.  sparse,
+        compact_tangent: as in expected_fit_dev()."""
+        Sampler._sparse_dest("expected_fit", dest, sparse, compact_tangent)
         unknown = set(want) - {"expected", "cotangent", "grad_p_drive", "grad_dest"}
         if unknown:
             raise ValueError(f"expected_fit: unknown outputs {sorted(unknown)}")
