@@ -338,6 +338,7 @@ constexpr size_t kRowLds = sizeof(double) * 2 * kRowTile * (kRowTile + 1) + size
 // itself (s_waitcnt vmcnt(32), 31, ... in front of the additions).  The last one or two tiles (the row's end and the pad) take a
 // plain path: rows beyond the table are clamped to its last row and their values unused.
 typedef uint32_t cpm_u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) cpm_u32x2 lds_u32x2;
 typedef uint32_t cpm_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ double row_load(__amdgpu_buffer_rsrc_t rows, uint32_t lane_off, uint32_t row_off)
 {
@@ -1015,8 +1016,10 @@ __device__ __forceinline__ void hand_off_done(uint32_t *done_chunk, int tid)
 // POLICY (store_policy): how the stayers' ids are stored and the pack is streamed; 0 = plain stores, default loads.
 // NARROW (the narrow twin of the one-launch hour, cpm_narrow.h): a.rp_t holds NARROW packs, NQ is the number of LDS-DMA instructions
 // they take (narrow_nq of the wide rung), and the search runs on 16-bit entries; the wide words behind an undecided draw are reached
-// through a.rare.  Everything else is the wide body's.
-template <int BLOCK, int CPT, int NQ, bool GROUPED, bool FUSED, bool WAIT = false, bool SPARSE = false, bool STAGED = false, int POLICY = 0, bool NARROW = false>
+// through a.rare.  Where DENSE_ON (dense_on(CPT, rung): it pays and the CU keeps its blocks), its waves compact their drivers into a
+// scratch behind the pack before the barrier and search and place from dense slots (DENSE below; cpm_narrow.h, "dense drivers").
+// Everything else is the wide body's.
+template <int BLOCK, int CPT, int NQ, bool GROUPED, bool FUSED, bool WAIT = false, bool SPARSE = false, bool STAGED = false, int POLICY = 0, bool NARROW = false, bool DENSE_ON = false>
 __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const int z, uint32_t *pack, SampleLds &sl, uint32_t *done_chunk,
                                                     const uint32_t *wait_on = nullptr, uint32_t wait_need = 0)
 {
@@ -1167,6 +1170,10 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
     const uint32_t *hi = pack + gw;
     const uint16_t *smap = SPARSE ? reinterpret_cast<const uint16_t *>(hi + a.Zq) : nullptr;
     uint32_t hi_last = 0;
+    constexpr bool DENSE = NARROW && GROUPED && DENSE_ON;  // (DENSE_ON: dense_on(CPT, the wide rung), cpm_narrow.h)
+    uint32_t ndrv = 0;  // DENSE: the wave's drivers among its register-resident cars (wave-uniform); otherwise unused
+    lds_u32x2 *scr = nullptr;  // DENSE: this wave's scratch behind the pack; otherwise no such memory exists
+    if constexpr (DENSE) scr = (lds_u32x2 *)(pack + rw) + static_cast<uint32_t>(tid >> 6) * dense_cap(CPT);
     auto first_pass = [&](auto kc) {
         constexpr int K = decltype(kc)::value;
         // Philox: needs the ids only
@@ -1180,6 +1187,23 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
             drive[c] = valid[c] & (kb <= thr);       // u <= p_drive[origin,t] (src/resampling.jl:15) in integers
             want[c] = drive[c] & (last != 0.0);      // stays, or zero row: destination = origin (:35-36)
         }
+        // DENSE (cpm_narrow.h, "dense drivers"): the wave's drivers go to its scratch behind the pack while the pack is landing -- at their
+        // rank among the wave's drivers, slot by slot -- and are searched and placed from dense slots behind the K variants below.  The
+        // scratch is this wave's alone (written here, read by the same wave: LDS operations of a wave keep their order): no barrier more.
+        if constexpr (DENSE && K > 0) {
+#pragma unroll
+            for (int c = 0; c < K; ++c) {
+                const unsigned long long m = ballot64(drive[c]);
+                const uint32_t rk = dense_rank(m, lane, ndrv);  // (below 64 K <= dense_cap(CPT) in every lane, a driver's or not)
+                if (drive[c]) {
+                    cpm_u32x2 v;
+                    v.x = id[c];
+                    v.y = khi[c];
+                    scr[rk] = v;
+                }
+                ndrv += static_cast<uint32_t>(__popcll(m));
+            }
+        }
         // This wave's pieces of the pack have landed (LDS-DMA counts in vmcnt; s_barrier itself waits for no counter), then the
         // barrier makes every wave's pieces visible to every wave.
         CPM_SSTAMP(2);
@@ -1189,7 +1213,26 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
         n = s_split ? static_cast<uint32_t>(CPT * BLOCK) : n_all;  // the cars this workgroup samples
         if constexpr (NARROW) hi_last = hi[0];  // (the header piece behind the guide)
         else hi_last = hi[(SPARSE ? a.Zc : a.Z) - 1];
-        if constexpr (K > 0) {
+        if constexpr (DENSE) {
+            // the stayers, from the original slots: one ticket per wave (their ids are out of the way before the search)
+            if constexpr (K > 0) {
+                unsigned long long mS[K];
+                uint32_t total = 0;
+#pragma unroll
+                for (int c = 0; c < K; ++c) {
+                    mS[c] = ballot64(valid[c] & !drive[c]);
+                    total += static_cast<uint32_t>(__popcll(mS[c]));
+                }
+                uint32_t bS = 0;
+                if (lane == 0 && total) bS = atomicAdd(&s_nstay, total);
+                bS = from_lane0(bS);
+#pragma unroll
+                for (int c = 0; c < K; ++c) {
+                    if (valid[c] & !drive[c]) put32<policy_stay(POLICY)>(stay_out, bS + static_cast<uint32_t>(__popcll(mS[c] & below)), id[c]);
+                    bS += static_cast<uint32_t>(__popcll(mS[c]));
+                }
+            }
+        } else if constexpr (K > 0) {
             if constexpr (NARROW) narrow_pack_search<K>(pack, gw, khi, want, sh, hi_last, a.Z, a.Zq, a.rare, a.hour, z, dest, ok);
             else pack_search<K>(guide, hi, khi, want, sh, hi_last, a.Zq, dest, ok, smap);
             {
@@ -1314,6 +1357,65 @@ __device__ __forceinline__ void grouped_sample_body(const GroupedArgs &a, const 
         } else {
             if (k == 0) first_pass(std::integral_constant<int, 0>{});
             else first_pass(std::integral_constant<int, 1>{});
+        }
+    }
+    if constexpr (DENSE) {
+        // KD = ceil(drivers / 64) dense slots: search, rank atomics, staging -- every slot but the last is full.  The KD variants follow
+        // the K variants of first_pass in sequence (K + CPT bodies, not K x CPT).
+        auto dense_pass = [&](auto kdc) {
+            constexpr int KD = decltype(kdc)::value;
+            uint32_t did[KD], dkhi[KD], ddest[KD], rank[KD];
+            bool live[KD], dwant[KD], dok[KD];
+#pragma unroll
+            for (int s = 0; s < KD; ++s) {
+                const cpm_u32x2 v = scr[dense_read_pos(s, lane)];
+                did[s] = v.x;
+                dkhi[s] = v.y;
+                live[s] = dense_live(s, KD, lane, ndrv);
+                dwant[s] = live[s] & (last != 0.0);
+            }
+            narrow_pack_search<KD>(pack, gw, dkhi, dwant, sh, hi_last, a.Z, a.Zq, a.rare, a.hour, z, ddest, dok);
+            bool anyx = false;
+#pragma unroll
+            for (int s = 0; s < KD; ++s) {
+                ddest[s] = dwant[s] ? ddest[s] : static_cast<uint32_t>(z);  // (zero row: the driver stays home, counted in `driving`)
+                anyx |= dwant[s] & !dok[s];
+            }
+            if (__builtin_expect(any64(anyx), 0)) {  // ties and draws above the row total: the f64 row in HBM (wave-uniform, rare)
+#pragma unroll
+                for (int s = 0; s < KD; ++s) {
+                    if (dwant[s] & !dok[s]) {
+                        long long kb;
+                        uint32_t lo_w, hi_w;  // (both words drawn again from the id, here where it is rare)
+                        car_draw_words(a.seed, a.cars.global(did[s]), a.step, kb, lo_w, hi_w);
+                        ddest[s] = search_exact_any<SPARSE>(a.rare, a.hour, z, u53(lo_w, hi_w), last, hi_w <= hi_last ? static_cast<int>(ddest[s]) : -1);
+                    }
+                }
+            }
+            CPM_SSTAMP(4);
+#pragma unroll
+            for (int s = 0; s < KD; ++s) rank[s] = live[s] ? atomicAdd(&gb[gdiv_group_t<SPARSE>(a.gdiv, ddest[s])], 1u) : 0u;
+#pragma unroll
+            for (int s = 0; s < KD; ++s) {
+                if (live[s]) {
+                    const uint32_t g = gdiv_group_t<SPARSE>(a.gdiv, ddest[s]);
+                    const uint32_t packed = did[s] | (gdiv_local_t<SPARSE>(a.gdiv, ddest[s], g) << a.idbits);
+                    if (rank[s] < static_cast<uint32_t>(kStage)) stage[g * kStage + rank[s]] = packed;
+                    else if (rank[s] < a.scap) hand_store<FUSED>(&runs[g * a.scap + rank[s]], packed);
+                }
+            }
+        };
+        static_assert(CPT <= 8, "the dispatch below");
+        switch (dense_round_slots(ndrv)) {
+        case 0: break;
+        case 1: dense_pass(std::integral_constant<int, 1>{}); break;
+        case 2: dense_pass(std::integral_constant<int, CPT >= 2 ? 2 : CPT>{}); break;
+        case 3: dense_pass(std::integral_constant<int, CPT >= 3 ? 3 : CPT>{}); break;
+        case 4: dense_pass(std::integral_constant<int, CPT >= 4 ? 4 : CPT>{}); break;
+        case 5: dense_pass(std::integral_constant<int, CPT >= 5 ? 5 : CPT>{}); break;
+        case 6: dense_pass(std::integral_constant<int, CPT >= 6 ? 6 : CPT>{}); break;
+        case 7: dense_pass(std::integral_constant<int, CPT >= 7 ? 7 : CPT>{}); break;
+        default: dense_pass(std::integral_constant<int, CPT>{}); break;
         }
     }
     for (uint32_t q0 = CPT * BLOCK; q0 < n; q0 += BLOCK) {  // buckets larger than CPT*BLOCK cars (wave-uniform trips)
@@ -2024,6 +2126,7 @@ __device__ __forceinline__ void grouped_hour_block(const GroupedArgs &a)
         SampleLds s;
         PlaceLds<kFusedThreads, kFusedKruns, kFusedZpg> p;
     } u;
+    static_assert(sizeof(u) == kFusedStaticLds && kFusedThreads == kDenseBlock, "dense_fits (cpm_narrow.h) counts these bytes");
     constexpr int per = kFusedChunk + kGroups;
     const int nchunk = (a.Z + kFusedChunk - 1) / kFusedChunk;
     int z = -1, g = 0, j = -1;  // the block's role: sampler workgroup of zone z, or placing block (g, j)
@@ -2051,7 +2154,7 @@ __device__ __forceinline__ void grouped_hour_block(const GroupedArgs &a)
         }
     }
     if (z >= 0) {
-        grouped_sample_body<kFusedThreads, CPT, NARROW ? narrow_nq(NQ) : NQ, true, true, false, SPARSE, false, policy_dense_pack_only(kPolicyHour, SPARSE), NARROW>(
+        grouped_sample_body<kFusedThreads, CPT, NARROW ? narrow_nq(NQ) : NQ, true, true, false, SPARSE, false, policy_dense_pack_only(kPolicyHour, SPARSE), NARROW, NARROW && dense_on(CPT, NQ)>(
             a, z, dyn, u.s, a.done_t + static_cast<size_t>((PERM ? static_cast<int>(blockIdx.x) : z) / kFusedChunk) * kDoneStride);
     } else {
         const uint32_t need = static_cast<uint32_t>(min(kFusedChunk, a.Z - j * kFusedChunk));
@@ -2514,9 +2617,11 @@ inline size_t fused_lds_bytes(int Zq, int G, int smap = 0)
 {
     return std::max(sizeof(uint32_t) * static_cast<size_t>(pack_row_words(Zq, G, smap)), static_cast<size_t>(4 + sizeof(PlaceLds<kFusedThreads, kFusedKruns, kFusedZpg>::zone_t)) * kFusedKruns * kFusedKdeep * kFusedThreads);
 }
-inline size_t fused_lds_bytes_narrow(int Zq, int G)  // (the narrow twin: max(narrow pack, placing list))
+static_assert((4 + sizeof(PlaceLds<kFusedThreads, kFusedKruns, kFusedZpg>::zone_t)) * kFusedKruns * kFusedKdeep * kFusedThreads == kFusedListLds,
+              "dense_fits (cpm_narrow.h) counts the placing list's bytes: CPM_FUSED_LIST_LDS");
+inline size_t fused_lds_bytes_narrow(int Zq, int G, int cpt, int rung)  // (the narrow twin: max(narrow pack + the dense drivers' scratch behind it, placing list))
 {
-    return std::max(sizeof(uint32_t) * static_cast<size_t>(narrow_row_words(Zq, G)), fused_lds_bytes(0, 3));
+    return std::max(sizeof(uint32_t) * static_cast<size_t>(narrow_row_words(Zq, G)) + dense_scratch_bytes(kFusedThreads, cpt, rung), fused_lds_bytes(0, 3));
 }
 template <int CPT, int NQ, bool SPARSE, bool PERM = false>
 inline hipError_t grouped_launch_hour_t(const GroupedArgs &a, hipStream_t stream)
@@ -2559,7 +2664,7 @@ inline hipError_t grouped_launch_hour_narrow_t(const GroupedArgs &a, hipStream_t
     static_assert(sizeof(uint32_t) * 1024 * narrow_nq(NQ) <= kPackLds, "the narrow pack of every Z of the rung fits");
     const int nchunk = (a.Z + kFusedChunk - 1) / kFusedChunk;
     constexpr auto kernel = k_grouped_hour_narrow<CPT, NQ>;
-    const size_t lds = fused_lds_bytes_narrow(a.Zq, a.G);
+    const size_t lds = fused_lds_bytes_narrow(a.Zq, a.G, CPT, NQ);
     if (narrow_need(a.Zq, a.G) > narrow_nq(NQ)) return hipErrorInvalidValue;  // (cannot happen: narrow_nq covers the rung's band)
     const hipError_t e = lds_opt_in<kernel>(lds, kPackLds);
     if (e != hipSuccess) return e;

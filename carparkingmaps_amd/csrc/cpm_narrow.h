@@ -180,6 +180,69 @@ CPM_HD inline void narrow_search(const A &a, const uint32_t (&khi)[CPT], const b
     }
 }
 
+// ------------------------------------------------------------------------------------------------ dense drivers
+// About half the cars of a wave drive: the search above and the drivers' slot work would run over all K register slots of the wave with
+// the stayers' lanes masked off.  The narrow twin's sampler waves therefore COMPACT their drivers first (cpm_grouped.h, first_pass): a
+// driver's payload {local car id, khi} goes to a per-wave LDS scratch behind the pack, at the driver's rank among the wave's drivers
+// (slot by slot, lanes in order), and after the pack's barrier the wave reads ceil(drivers / 64) DENSE slots back and searches and
+// places from those.  A wave's scratch holds the worst case, CPT x 64 payloads (every car drives).  The index arithmetic, free of HIP
+// (tests/dense_probe.cc runs it against a plain loop):
+constexpr uint32_t kDensePayloadBytes = 8;  // {id, khi}
+CPM_HD constexpr uint32_t dense_cap(int cpt) { return 64u * static_cast<uint32_t>(cpt); }  // payloads of a wave's scratch
+// Where compacting pays: a compile-time constant per instantiation (bit CPT of the mask), never a flag the kernel reads.  MEASURED at
+// Z = 4,096, the parent's kernel / the compacting one, interleaved runs on one box, ms per resample (profiles/dense_drivers_notes.md):
+// six cars per lane (x 1,000) 0.7251 / 0.7063, four (x 500) 0.5540 / 0.5448, two (x 300) 0.5179 / 0.5210 -- a loss, so it is off
+// there -- and one (x 150) 0.4931 / 0.4869.
+#ifndef CPM_DENSE_CPT_MASK
+#define CPM_DENSE_CPT_MASK (~(1u << 2))
+#endif
+CPM_HD constexpr bool dense_pays(int cpt) { return ((static_cast<uint32_t>(CPM_DENSE_CPT_MASK) >> cpt) & 1u) != 0u; }
+// ... and where the scratch leaves the CU as many blocks as it had: the twin <CPT, rung> compacts only if, at the LARGEST narrow pack of
+// the rung's band (narrow_band_top), pack + scratch + the static LDS still fit the blocks per CU that the uncompacted twin runs there
+// -- the smaller of what its registers allow (the resource remarks: six at six cars per lane, seven below) and what its own LDS
+// allows.  Sizes are rounded up to 1,280 bytes, the coarsest allocation step a 160 KiB LDS is assumed to have (the rounding only
+// ever switches compaction off).  At six cars per lane that is every rung up to 5 (Z <= 4,096: 26,864 B per block, six blocks in
+// 161,184 B); from Z = 4,097 the guide doubles, six blocks no longer fit, and the rungs above run the uncompacted body.
+constexpr size_t kCuLdsBytes = 160 * 1024, kLdsStep = 1280;
+constexpr size_t kFusedStaticLds = 4240;  // SampleLds / PlaceLds of a block of the one-launch hour (asserted in cpm_grouped.h)
+#ifndef CPM_FUSED_LIST_LDS
+#define CPM_FUSED_LIST_LDS 10240  // (tuning builds that change the placing list's geometry say its bytes here)
+#endif
+constexpr size_t kFusedListLds = CPM_FUSED_LIST_LDS;  // the placing blocks' sorted list: the floor of the launch's dynamic LDS (asserted likewise)
+constexpr int kDenseBlock = 256;          // threads of a block of the one-launch hour (kFusedThreads)
+constexpr int dense_blocks_by_registers(int cpt) { return cpt >= 6 ? 6 : 7; }
+constexpr size_t dense_scratch_raw(int block, int cpt) { return static_cast<size_t>(block / 64) * dense_cap(cpt) * kDensePayloadBytes; }
+constexpr size_t lds_step_up(size_t b) { return (b + kLdsStep - 1) / kLdsStep * kLdsStep; }
+constexpr bool dense_fits(int cpt, int rung)
+{
+    const int top = narrow_band_top(rung);
+    const size_t pack = sizeof(uint32_t) * static_cast<size_t>(narrow_row_words(pack_zq(top), pack_guide_bits(top)));
+    const size_t before = (pack > kFusedListLds ? pack : kFusedListLds) + kFusedStaticLds;
+    const size_t scr = pack + dense_scratch_raw(kDenseBlock, cpt);
+    const size_t after = lds_step_up((scr > kFusedListLds ? scr : kFusedListLds) + kFusedStaticLds);
+    const size_t by_lds = kCuLdsBytes / before, by_reg = static_cast<size_t>(dense_blocks_by_registers(cpt));
+    return after * (by_lds < by_reg ? by_lds : by_reg) <= kCuLdsBytes;
+}
+constexpr bool dense_on(int cpt, int rung) { return dense_pays(cpt) && dense_fits(cpt, rung); }
+static_assert(dense_fits(6, 5) && !dense_fits(6, 6) && dense_fits(4, 5) && !dense_fits(4, 6), "the headline compacts; six / seven blocks per CU are kept above Z = 4,096");
+constexpr size_t dense_scratch_bytes(int block, int cpt, int rung) { return dense_on(cpt, rung) ? dense_scratch_raw(block, cpt) : 0; }
+// rank of lane `lane` of a slot whose drivers' ballot is m, with `before` drivers in the wave's earlier slots: before + the drivers in
+// the lanes below.  Every lane gets a value <= before + 63 (only a driver's is its rank): an address inside the scratch either way.
+CPM_HD inline uint32_t dense_rank(unsigned long long m, int lane, uint32_t before)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)lane;
+    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), before));
+#else
+    return before + static_cast<uint32_t>(__builtin_popcountll(m & ((1ull << lane) - 1ull)));
+#endif
+}
+// the dense slots that `count` payloads fill; dense slot s, lane `lane` reads position s * 64 + lane, which holds a driver below
+// `count`.  With kd = dense_round_slots(count) every slot but the last is full.
+CPM_HD constexpr uint32_t dense_round_slots(uint32_t count) { return (count + 63u) >> 6; }
+CPM_HD constexpr uint32_t dense_read_pos(int s, int lane) { return static_cast<uint32_t>(s) * 64u + static_cast<uint32_t>(lane); }
+CPM_HD constexpr bool dense_live(int s, int kd, int lane, uint32_t count) { return s < kd - 1 || dense_read_pos(s, lane) < count; }
+
 // A draw the 16 bits could not decide, on the row's WIDE high words (w(j), j < Zq: the wide pack's entries and its 0xFFFFFFFF pad):
 // the first j >= dest with hi[j] >= khi, four independent reads at a time.  Returns j | (hi[j] > khi) << 31.  The draw searched, so
 // khi <= hi[Z - 1]: the walk ends inside the row.
