@@ -27,6 +27,7 @@
 #include "../../include/cpm_expected_grad_batch.h"
 #include "../../include/cpm_expected_fit.h"
 #include "../../include/cpm_expected_tangent.h"
+#include "../../include/cpm_expected_sparse_tangent.h"
 #include "../../include/cpm_expected_sparse.h"
 #include "../../include/cpm_expected_sparse_grad.h"
 #include "../../include/cpm_expected_sparse_dest.h"
@@ -52,6 +53,7 @@
 #include "cpm_expected_grad_batch.h"
 #include "cpm_expected_fit.h"
 #include "cpm_expected_tangent.h"
+#include "cpm_expected_sparse_tangent.h"
 #include "cpm_expected_sparse.h"
 #include "cpm_expected_sparse_grad.h"
 #include "cpm_expected_sparse_dest.h"
@@ -322,6 +324,10 @@ struct cpm_ctx {
     DevBuf<double> d_fits_dw;           // [2][T][Z] the trip weights' tangent of the sparse fit, kept while sdp and the sparse trip weights stay
     int64_t fits_dw_gen = -1, fits_dw_builds = -1;
     int64_t exps_trip_builds = 0;       // builds of d_exps_w so far
+    // ... and carried into the transposed cell order for the forward tangent (include/cpm_expected_sparse_tangent.h): beside d_exps_o /
+    // d_exps_p, built by the first tangent call with a non-zero c_dest, stale wherever sdp_gen moves or ensure_exps rebuilds
+    DevBuf<double> d_exps_dp;           // [exps_cells]
+    int64_t exps_dp_gen = -1;           // the sdp_gen it was built from (-1: none)
     // value and gradient of the noise-free objectives (include/cpm_expected_fit.h, cpm_expected_fit.h)
     DevBuf<double> d_act_meas;          // [T] measured traffic activity
     bool have_act_meas = false;
@@ -1385,6 +1391,7 @@ int32_t ensure_exps(cpm_ctx *c)
     if (!c->sparse_tables) return exps_no_rows();
     if (c->exps_valid) return CPM_OK;
     c->exps_trip_valid = false;  // (the sparse trip weights read l and r: never older than these)
+    c->exps_dp_gen = -1;         // (the transposed tangent follows the cells' order: never older than it)
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     if (Z > cpm::kExpsMaxZ) return fail(CPM_ERR_STATE, "expected_sparse: more than %d zones", cpm::kExpsMaxZ);
     const int64_t nrows = static_cast<int64_t>(Z) * T;
@@ -2401,7 +2408,7 @@ int32_t expected_fit_enqueue(cpm_ctx *c, int B, const double *p_min, const doubl
 
 // ------------------------------------------------------------------ forward tangent of the expected densities (include/cpm_expected_tangent.h)
 // what every entry checks behind exp_enter, before anything is read, copied or enqueued
-int32_t tangent_check(cpm_ctx *c, const char *what, int32_t K, uint32_t flags, const double *c_dest, const void *out)
+int32_t tangent_check(cpm_ctx *c, const char *what, int32_t K, uint32_t flags, const double *c_dest, const void *out, bool sparse = false)
 {
     if (K < 1 || K > CPM_TANGENT_MAX_DIRECTIONS) return fail(CPM_ERR_ARG, "%s: K = %d outside 1 .. %d", what, K, CPM_TANGENT_MAX_DIRECTIONS);
     if (!out) return fail(CPM_ERR_ARG, "%s: null tangent output", what);
@@ -2416,7 +2423,8 @@ int32_t tangent_check(cpm_ctx *c, const char *what, int32_t K, uint32_t flags, c
     CTX_TRY(c);
     if (!c->have_pdrive) return fail(CPM_ERR_STATE, "%s: p_drive not set", what);
     if ((rc = exp_tables_ready(c, what)) != CPM_OK) return rc;
-    if (any && (rc = tangent_ready(c, what)) != CPM_OK) return rc;
+    if (sparse && !c->sparse_tables) return exps_no_rows();
+    if (any && (rc = sparse ? sdp_ready(c, what) : tangent_ready(c, what)) != CPM_OK) return rc;
     return CPM_OK;
 }
 
@@ -2426,13 +2434,36 @@ void launch_tan_hour(cpm_ctx *c, const cpm::TanHour &a)
     cpm::launch(cpm::k_tan_hour<NB>, dim3(nblk(a.Z, cpm::kExpRows)), dim3(cpm::kExpBlock), 0, c->stream, a);
 }
 
+// the same operator from the transposed compact rows (k_exps_tan_hour; ensure_exps built them, ensure_exps_dp the tangent's cells)
+template <int NB>
+void launch_exps_tan_hour(cpm_ctx *c, const cpm::ExpsTanHour &b)
+{
+    const dim3 grid(nblk(b.h.Z, cpm::kExpRows)), block(cpm::kExpBlock);
+    if (b.h.u_mode == 1) cpm::launch(cpm::k_exps_tan_hour<NB, true>, grid, block, 0, c->stream, b);
+    else cpm::launch(cpm::k_exps_tan_hour<NB, false>, grid, block, 0, c->stream, b);
+}
+
+// The compact tangent in the transposed cell order (k_exps_cells_dp): once per compact tangent and table build.  Enqueued.
+int32_t ensure_exps_dp(cpm_ctx *c)
+{
+    if (c->exps_dp_gen == c->sdp_gen && c->d_exps_dp) return CPM_OK;
+    HIP_TRY(c->d_exps_dp.reserve(std::max<size_t>(c->exps_cells, 1)));
+    cpm::launch(cpm::k_exps_cells_dp, dim3(static_cast<unsigned>(c->Z), static_cast<unsigned>(c->T)), dim3(cpm::kExpBlock), 0, c->stream,
+                c->d_exps_colptr.get(), c->d_exps_o.get(), c->d_sdp.get(), c->d_sj.get(), c->d_scnt.get(), cpm::kDsCap, static_cast<int>(c->Z),
+                c->d_exps_dp.get());
+    HIP_TRY(hipGetLastError());
+    c->exps_dp_gen = c->sdp_gen;
+    return CPM_OK;
+}
+
 // The recurrence of expected_enqueue (B = 1, the installed p_drive) for the primal and K directions: operator-major, per operator one
 // launch per pass of at most kTanDirs directions.  dpi0: [K][Z], dpd: [K][T][Z], c_dest: host [K] (each or nullptr: zero).
 // out: [K][2][T][Z]; dpi_next: [K][Z] or nullptr; expected: [2][T][Z] or nullptr.
+// sparse: the operators read the transposed compact rows and the compact tangent (k_exps_tan_hour) and the per-table arrays of ensure_exps.
 int32_t expected_tangent_enqueue(cpm_ctx *c, int K, const double *d_pi0, uint32_t flags, const double *dpi0, const double *dpd, const double *c_dest,
-                                 double *out, double *dpi_next, double *expected)
+                                 double *out, double *dpi_next, double *expected, bool sparse = false)
 {
-    int32_t rc = ensure_exp_aux(c);
+    int32_t rc = sparse ? ensure_exps(c) : ensure_exp_aux(c);
     if (rc != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;  // (every vector starts on a 16-byte line)
@@ -2440,6 +2471,10 @@ int32_t expected_tangent_enqueue(cpm_ctx *c, int K, const double *d_pi0, uint32_
     bool with_u = false;
     if (c_dest)
         for (int k = 0; k < K; ++k) with_u = with_u || c_dest[k] != 0.0;
+    if (sparse && with_u) {
+        if ((rc = sdp_ready(c, "expected_sparse_tangent")) != CPM_OK) return rc;
+        if ((rc = ensure_exps_dp(c)) != CPM_OK) return rc;
+    }
     const int npass = (K + cpm::kTanDirs - 1) / cpm::kTanDirs;
     const size_t side = static_cast<size_t>(npass) * 2 * cpm::kExpMaxNB * Zs;   // [passes][pi | x][8][Zs]
     HIP_TRY(c->d_tanf_ws.reserve(2 * side + 3 * static_cast<size_t>(Zs)));  // (a grow frees first: hipFree waits for what still reads the old workspace)
@@ -2471,13 +2506,13 @@ int32_t expected_tangent_enqueue(cpm_ctx *c, int K, const double *d_pi0, uint32_
         for (int ps = 0; ps < npass; ++ps) {
             const int k0 = ps * cpm::kTanDirs, nv = std::min(K - k0, cpm::kTanDirs) + 1;
             cpm::TanHour a{};
-            a.p_t = c->d_p + row * Z;
+            a.p_t = sparse ? nullptr : c->d_p + row * Z;
             a.last_t = c->d_last + row;
-            a.r_t = c->d_exp_r + row;
-            a.start_t = c->d_exp_start + static_cast<size_t>(t) * (Z + 1);
-            a.list_t = c->d_exp_list + row;
+            a.r_t = (sparse ? c->d_exps_r : c->d_exp_r) + row;
+            a.start_t = (sparse ? c->d_exps_start : c->d_exp_start) + static_cast<size_t>(t) * (Z + 1);
+            a.list_t = (sparse ? c->d_exps_list : c->d_exp_list) + row;
             a.last_next = more ? c->d_last + static_cast<size_t>(t_next) * Z : nullptr;
-            a.dp_t = with_u ? c->d_tan + row * Z : nullptr;
+            a.dp_t = (with_u && !sparse) ? c->d_tan + row * Z : nullptr;
             a.u = ws_u;
             a.u_mode = !with_u ? 0 : ps == 0 ? 1 : 2;
             a.q_cur = pd + row;
@@ -2508,7 +2543,19 @@ int32_t expected_tangent_enqueue(cpm_ctx *c, int K, const double *d_pi0, uint32_
             a.Zs = Zs;
             a.nv = nv;
             // the smallest instantiation that holds the pass (vectors beyond nv repeat the last one and are not stored)
-            if (nv > 5) launch_tan_hour<8>(c, a);
+            if (sparse) {
+                cpm::ExpsTanHour b{};
+                b.h = a;
+                b.colptr_t = c->d_exps_colptr + static_cast<size_t>(t) * (Z + 1);
+                b.cell_o = c->d_exps_o.get();
+                b.cell_p = c->d_exps_p.get();
+                b.cell_dp = with_u ? c->d_exps_dp.get() : nullptr;
+                b.par = t & 1;
+                if (nv > 5) launch_exps_tan_hour<8>(c, b);
+                else if (nv > 4) launch_exps_tan_hour<5>(c, b);
+                else if (nv > 2) launch_exps_tan_hour<4>(c, b);
+                else launch_exps_tan_hour<2>(c, b);
+            } else if (nv > 5) launch_tan_hour<8>(c, a);
             else if (nv > 4) launch_tan_hour<5>(c, a);  // (K = 4: the model's four parameters)
             else if (nv > 2) launch_tan_hour<4>(c, a);
             else launch_tan_hour<2>(c, a);
@@ -4644,30 +4691,32 @@ int32_t cpm_expected_sparse_trip_tangent(cpm_ctx *c, double *dw_sec, double *dw_
 
 // ------------------------------------------------------------------ forward tangent of the expected densities (include/cpm_expected_tangent.h)
 
-int32_t cpm_expected_tangent_dev(cpm_ctx *c, int32_t K, const void *d_pi0, uint32_t flags, const void *d_dpi0, const void *d_dp_drive, const double *c_dest,
-                                 void *d_out, void *d_dpi_next, void *d_expected)
+// both forms for both table layouts (what: the entry's name in its error texts)
+static int32_t expected_tangent_dev_any(cpm_ctx *c, const char *what, bool sparse, int32_t K, const void *d_pi0, uint32_t flags, const void *d_dpi0,
+                                        const void *d_dp_drive, const double *c_dest, void *d_out, void *d_dpi_next, void *d_expected)
 {
     int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if ((rc = tangent_check(c, "expected_tangent_dev", K, flags, c_dest, d_out)) != CPM_OK) return rc;
+    if ((rc = tangent_check(c, what, K, flags, c_dest, d_out, sparse)) != CPM_OK) return rc;
     return expected_tangent_enqueue(c, K, static_cast<const double *>(d_pi0), flags, static_cast<const double *>(d_dpi0),
                                     static_cast<const double *>(d_dp_drive), c_dest, static_cast<double *>(d_out), static_cast<double *>(d_dpi_next),
-                                    static_cast<double *>(d_expected));
+                                    static_cast<double *>(d_expected), sparse);
 }
 
-int32_t cpm_expected_tangent(cpm_ctx *c, int32_t K, const double *pi0, uint32_t flags, const double *dpi0, const double *dp_drive, const double *c_dest,
-                             double *d_parking, double *d_driving, double *dpi_next, double *parking, double *driving)
+static int32_t expected_tangent_any(cpm_ctx *c, const char *what, bool sparse, int32_t K, const double *pi0, uint32_t flags, const double *dpi0,
+                                    const double *dp_drive, const double *c_dest, double *d_parking, double *d_driving, double *dpi_next, double *parking,
+                                    double *driving)
 {
     int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if ((rc = tangent_check(c, "expected_tangent", K, flags, c_dest, d_parking)) != CPM_OK) return rc;
-    if (!d_driving) return fail(CPM_ERR_ARG, "expected_tangent: null tangent output");
-    if ((parking == nullptr) != (driving == nullptr)) return fail(CPM_ERR_ARG, "expected_tangent: parking and driving go together");
+    if ((rc = tangent_check(c, what, K, flags, c_dest, d_parking, sparse)) != CPM_OK) return rc;
+    if (!d_driving) return fail(CPM_ERR_ARG, "%s: null tangent output", what);
+    if ((parking == nullptr) != (driving == nullptr)) return fail(CPM_ERR_ARG, "%s: parking and driving go together", what);
     if ((rc = check_pi0(c, pi0)) != CPM_OK) return rc;
     const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nk = static_cast<size_t>(K);
-    if ((rc = check_finite("expected_tangent", "dpi0", dpi0, nk * Z)) != CPM_OK) return rc;
-    if ((rc = check_finite("expected_tangent", "dp_drive", dp_drive, nk * zt)) != CPM_OK) return rc;
-    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;  // (the row-total check: CPM_ERR_TABLE in front of the first copy)
+    if ((rc = check_finite(what, "dpi0", dpi0, nk * Z)) != CPM_OK) return rc;
+    if ((rc = check_finite(what, "dp_drive", dp_drive, nk * zt)) != CPM_OK) return rc;
+    if ((rc = sparse ? ensure_exps(c) : ensure_exp_aux(c)) != CPM_OK) return rc;  // (the row-total check: CPM_ERR_TABLE in front of the first copy)
     // [K][2][T][Z] out | [2][T][Z] primal | [K][Z] d pi_next | [Z] pi_0 | [K][Z] d pi_0 | [K][T][Z] d p_drive
     HIP_TRY(c->d_tanf_io.reserve(nk * 2 * zt + 2 * zt + nk * Z + Z + nk * Z + nk * zt));
     double *d_out = c->d_tanf_io, *d_exp = d_out + nk * 2 * zt, *d_next = d_exp + 2 * zt, *d_pi0 = d_next + nk * Z, *d_dpi0 = d_pi0 + Z,
@@ -4676,7 +4725,7 @@ int32_t cpm_expected_tangent(cpm_ctx *c, int32_t K, const double *pi0, uint32_t 
     if (dpi0) HIP_TRY(hipMemcpyAsync(d_dpi0, dpi0, sizeof(double) * nk * Z, hipMemcpyHostToDevice, c->stream));
     if (dp_drive) HIP_TRY(hipMemcpyAsync(d_dpd, dp_drive, sizeof(double) * nk * zt, hipMemcpyHostToDevice, c->stream));
     rc = expected_tangent_enqueue(c, K, pi0 ? d_pi0 : nullptr, flags, dpi0 ? d_dpi0 : nullptr, dp_drive ? d_dpd : nullptr, c_dest, d_out,
-                                  dpi_next ? d_next : nullptr, parking ? d_exp : nullptr);
+                                  dpi_next ? d_next : nullptr, parking ? d_exp : nullptr, sparse);
     if (rc != CPM_OK) return rc;
     for (size_t k = 0; k < nk; ++k) {
         HIP_TRY(hipMemcpyAsync(d_parking + k * zt, d_out + k * 2 * zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
@@ -4689,6 +4738,31 @@ int32_t cpm_expected_tangent(cpm_ctx *c, int32_t K, const double *pi0, uint32_t 
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
+}
+
+int32_t cpm_expected_tangent_dev(cpm_ctx *c, int32_t K, const void *d_pi0, uint32_t flags, const void *d_dpi0, const void *d_dp_drive, const double *c_dest,
+                                 void *d_out, void *d_dpi_next, void *d_expected)
+{
+    return expected_tangent_dev_any(c, "expected_tangent_dev", false, K, d_pi0, flags, d_dpi0, d_dp_drive, c_dest, d_out, d_dpi_next, d_expected);
+}
+
+int32_t cpm_expected_tangent(cpm_ctx *c, int32_t K, const double *pi0, uint32_t flags, const double *dpi0, const double *dp_drive, const double *c_dest,
+                             double *d_parking, double *d_driving, double *dpi_next, double *parking, double *driving)
+{
+    return expected_tangent_any(c, "expected_tangent", false, K, pi0, flags, dpi0, dp_drive, c_dest, d_parking, d_driving, dpi_next, parking, driving);
+}
+
+// ... from the compact rows and the compact tangent (include/cpm_expected_sparse_tangent.h)
+int32_t cpm_expected_sparse_tangent_dev(cpm_ctx *c, int32_t K, const void *d_pi0, uint32_t flags, const void *d_dpi0, const void *d_dp_drive,
+                                        const double *c_dest, void *d_out, void *d_dpi_next, void *d_expected)
+{
+    return expected_tangent_dev_any(c, "expected_sparse_tangent_dev", true, K, d_pi0, flags, d_dpi0, d_dp_drive, c_dest, d_out, d_dpi_next, d_expected);
+}
+
+int32_t cpm_expected_sparse_tangent(cpm_ctx *c, int32_t K, const double *pi0, uint32_t flags, const double *dpi0, const double *dp_drive, const double *c_dest,
+                                    double *d_parking, double *d_driving, double *dpi_next, double *parking, double *driving)
+{
+    return expected_tangent_any(c, "expected_sparse_tangent", true, K, pi0, flags, dpi0, dp_drive, c_dest, d_parking, d_driving, dpi_next, parking, driving);
 }
 
 int32_t cpm_build_p_drive_tangent_dev(cpm_ctx *c, double p_min, double p_max, double e_drive, void *d_out)

@@ -282,7 +282,11 @@ class Evaluator:
     expected_sparse_dest=True (with expected_sparse=True) keeps the tangent of p_destin on the stored cells as well
     (include/cpm_expected_sparse_dest.h): expected_gradient[_batch], expected_fit and refine_expected with dest=True then run from the
     compact rows end to end, with the same bits, and neither the dense p_destin array nor the dense tangent is ever built.
-    expected_jacobian and refine_expected_lm with dest=True keep the dense tangent."""
+    expected_jacobian and refine_expected_lm with dest=True keep the dense tangent unless expected_sparse_tangent=True.
+
+    expected_sparse_tangent=True (with expected_sparse=True) runs the forward tangent from the compact rows as well
+    (include/cpm_expected_sparse_tangent.h): expected_jacobian, and so refine_expected_lm, with the same bits and without the dense
+    p_destin array; with dest=True (which needs expected_sparse_dest=True too) without the dense tangent either."""
     sampler: object
     C: int
     seed: int
@@ -301,6 +305,9 @@ class Evaluator:
     # expected_sparse_dest: behind expected_sparse, the calls above with dest=True read a compact tangent on the stored cells
     # (include/cpm_expected_sparse_dest.h) and stay sparse; expected_jacobian / refine_expected_lm keep the dense tangent.
     expected_sparse_dest: bool = False
+    # expected_sparse_tangent: behind expected_sparse, expected_jacobian / refine_expected_lm call the forward tangent of the compact
+    # rows (include/cpm_expected_sparse_tangent.h); with dest=True they read the compact tangent, which expected_sparse_dest keeps.
+    expected_sparse_tangent: bool = False
     _e_dest: object = field(default=None, repr=False)
     _pipe: object = field(default=None, repr=False)
     _s_table: object = field(default=None, repr=False)   # build_p_drive(0, 1, 1): the datamatrix's own table, for expected_gradient
@@ -311,6 +318,8 @@ class Evaluator:
     def __post_init__(self):
         if self.expected_sparse_dest and not self.expected_sparse:
             raise ValueError("Evaluator: expected_sparse_dest=True needs expected_sparse=True: the compact tangent serves the sparse calls alone")
+        if self.expected_sparse_tangent and not self.expected_sparse:
+            raise ValueError("Evaluator: expected_sparse_tangent=True needs expected_sparse=True: the sparse forward tangent reads the compact rows")
         if self.measured_parking is not None:   # Julia order, like the count tensors: the error is evaluated hour-major on contiguous rows
             self.measured_parking = np.asfortranarray(np.asarray(self.measured_parking, dtype=np.float64))
         if self.device_objectives:
@@ -541,13 +550,17 @@ class Evaluator:
         device (Sampler.build_p_drive_tangent_dev) and ONE tangent call (Sampler.expected_tangent_dev, include/cpm_expected_tangent.h)
         carries K = 3 directions -- 4 with dest: the last one along d p_destin / d e_dest (pt.e_dest > 0).  Returns dict(parking,
         driving (Z, T), d_parking, d_driving (P, Z, T)) in the parameter order (e_drive, p_min, p_max[, e_dest]).  The forward
-        tangent reads the DENSE tangent of p_destin, under expected_sparse_dest as well: it needs dP along destination columns, which
-        the compact tangent does not store."""
+        tangent reads the DENSE tangent of p_destin, under expected_sparse_dest alone as well.  Under expected_sparse_tangent=True the
+        call is the one of include/cpm_expected_sparse_tangent.h instead: the same bits from the compact rows, and with dest (which
+        then needs expected_sparse_dest=True) from the compact tangent, carried into destination columns once per tangent."""
         import torch
         s = self.sampler
+        sparse = self.expected_sparse_tangent
+        if sparse and dest and not self.expected_sparse_dest:
+            raise ValueError("expected_jacobian: dest=True under expected_sparse_tangent=True needs expected_sparse_dest=True (the compact tangent)")
         self._install(pt)
         if dest:
-            self._install_dest_tangent(dense=True)
+            self._install_dest_tangent(dense=not sparse)
         K, zt = (4 if dest else 3), s.Z * s.T
         dev = f"cuda:{s.device}"
         built = torch.empty(3 * zt, dtype=torch.float64, device=dev)      # (p_min, p_max, e_drive), as the builder lays them out
@@ -559,7 +572,8 @@ class Evaluator:
         s.sync()
         dpd[:zt], dpd[zt:2 * zt], dpd[2 * zt:3 * zt] = built[2 * zt:], built[:zt], built[zt:2 * zt]
         torch.cuda.synchronize(s.device)
-        s.expected_tangent_dev(K, out.data_ptr(), dpd.data_ptr(), c_dest=[0.0, 0.0, 0.0, 1.0][:K], ivp=ivp, d_expected_ptr=primal.data_ptr())
+        s.expected_tangent_dev(K, out.data_ptr(), dpd.data_ptr(), c_dest=[0.0, 0.0, 0.0, 1.0][:K], ivp=ivp, d_expected_ptr=primal.data_ptr(),
+                               sparse=sparse)
         s.sync()
         both = out.cpu().numpy().reshape(K, 2, s.T, s.Z)
         prim = primal.cpu().numpy().reshape(2, s.T, s.Z)
@@ -880,7 +894,8 @@ def refine_expected_lm(evaluator, pts, weights=None, steps=10, bounds=None, ivp=
     -- path: [(Point, F), ...] of the accepted points, the start first; gradient: dF/d(e_drive, p_min, p_max) at the last one; result:
     dict(F and the weighed terms) there; calls: Jacobian calls made -- plus lam, the damping it ended with.  The default Jacobian is
     the forward tangent, which reads the dense arrays: Evaluator.expected_sparse_dest changes nothing here (a Jacobian with dest=True
-    keeps the dense tangent of p_destin)."""
+    keeps the dense tangent of p_destin) unless Evaluator.expected_sparse_tangent=True, under which the same path, point for point and
+    bit for bit, comes from the compact rows (include/cpm_expected_sparse_tangent.h) and neither dense array is built."""
     b = dict(DEFAULT_FIT_BOUNDS)
     for k, v in (bounds or {}).items():
         if k not in b:
@@ -911,7 +926,8 @@ def refine_expected_lm(evaluator, pts, weights=None, steps=10, bounds=None, ivp=
             jac = jacobian(point(x))
             w_sec = None
             if w[k, 2] != 0:   # (after the call: the weights belong to the tables it installed)
-                w_sec = np.asarray(jac["w_sec"] if "w_sec" in jac else evaluator.sampler.expected_trip()[0], dtype=np.float64)
+                sparse = bool(getattr(evaluator, "expected_sparse_tangent", False))   # (the compact rows' weights: the dense array stays unbuilt)
+                w_sec = np.asarray(jac["w_sec"] if "w_sec" in jac else evaluator.sampler.expected_trip(sparse=sparse)[0], dtype=np.float64)
             return _lm_terms(evaluator, jac, w[k], w_sec)
 
         x = _project(np.array([pt.e_drive, pt.p_min, pt.p_max], dtype=np.float64), lo, hi, min_gap)

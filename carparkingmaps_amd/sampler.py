@@ -913,11 +913,14 @@ class Sampler:
     def _tangent_c(c_dest, K):
         return None if c_dest is None else np.ascontiguousarray(_f64(np.atleast_1d(c_dest), (K,)))
 
-    def expected_tangent(self, K, d_p_drive=None, d_pi0=None, c_dest=None, pi0=None, ivp=False, want_next=False, want_expected=False):
+    def expected_tangent(self, K, d_p_drive=None, d_pi0=None, c_dest=None, pi0=None, ivp=False, want_next=False, want_expected=False,
+                         sparse=False):
         """The derivative of expected()'s densities in K directions at the installed tables, blocking.  Direction k is
         (d_pi0[:, k], d_p_drive[:, :, k], c_dest[k] times the installed tangent of p_destin); d_p_drive: (Z, T, K), d_pi0: (Z, K),
         c_dest: (K,), each or None (zero).  Returns dict(d_parking, d_driving: (Z, T, K) float64 F-order[, d_pi_next (Z, K)][, parking,
-        driving (Z, T): expected()'s bits]).  A direction of p_drive counts only where the installed p_drive is strictly inside (0, 1)."""
+        driving (Z, T): expected()'s bits]).  A direction of p_drive counts only where the installed p_drive is strictly inside (0, 1).
+        sparse=True: the same bits from the compact rows and the compact tangent of sparse tables, neither dense array read, built or
+        allocated (include/cpm_expected_sparse_tangent.h)."""
         K = int(K)
         n = max(K, 1)                              # (the library names a K out of range; it reads no array before it does)
         a = self._pi0(pi0)
@@ -932,8 +935,9 @@ class Sampler:
         nxt = np.zeros((self.Z, n), dtype=np.float64, order="F") if want_next else None
         parking = np.zeros((self.Z, self.T), dtype=np.float64, order="F") if want_expected else None
         driving = np.zeros((self.Z, self.T), dtype=np.float64, order="F") if want_expected else None
-        _lib.check(self._L.cpm_expected_tangent(self._h, K, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(dp0), _vp(dpd), _vp(cd), _vp(d_parking),
-                                                _vp(d_driving), _vp(nxt), _vp(parking), _vp(driving)))
+        call = self._L.cpm_expected_sparse_tangent if sparse else self._L.cpm_expected_tangent
+        _lib.check(call(self._h, K, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(dp0), _vp(dpd), _vp(cd), _vp(d_parking), _vp(d_driving), _vp(nxt),
+                        _vp(parking), _vp(driving)))
         out = dict(d_parking=d_parking, d_driving=d_driving)
         if want_next:
             out["d_pi_next"] = nxt
@@ -942,18 +946,19 @@ class Sampler:
         return out
 
     def expected_tangent_dev(self, K, d_out_ptr, d_dp_drive_ptr=0, d_dpi0_ptr=0, c_dest=None, d_pi0_ptr=0, ivp=False, d_dpi_next_ptr=0,
-                             d_expected_ptr=0, flags=None):
+                             d_expected_ptr=0, flags=None, sparse=False):
         """Enqueue on the context's stream: d_out_ptr = device address of float64[K][2][T][Z] (per direction d parking, then d driving);
         d_dp_drive_ptr = device address of float64[K][T][Z] or 0, d_dpi0_ptr of float64[K][Z] or 0 (zero); c_dest: host (K,) or None;
         d_pi0_ptr = device address of float64[Z] or 0 (uniform); d_dpi_next_ptr = float64[K][Z] or 0; d_expected_ptr =
-        float64[expected_words()] or 0 (the primal).  flags: the raw flag word in place of ivp."""
+        float64[expected_words()] or 0 (the primal).  flags: the raw flag word in place of ivp.  sparse=True: from the compact rows
+        and the compact tangent (include/cpm_expected_sparse_tangent.h)."""
         p = lambda v: C.c_void_p(int(v)) if v else None
         K = int(K)
         cd = self._tangent_c(c_dest, K) if 1 <= K <= _lib.CPM_TANGENT_MAX_DIRECTIONS else (
             None if c_dest is None else np.ascontiguousarray(c_dest, dtype=np.float64))   # (whatever its shape: CPM_ERR_ARG names K)
         f = (_lib.CPM_EXPECT_IVP if ivp else 0) if flags is None else int(flags)
-        _lib.check(self._L.cpm_expected_tangent_dev(self._h, K, p(d_pi0_ptr), f, p(d_dpi0_ptr), p(d_dp_drive_ptr), _vp(cd), p(d_out_ptr),
-                                                    p(d_dpi_next_ptr), p(d_expected_ptr)))
+        call = self._L.cpm_expected_sparse_tangent_dev if sparse else self._L.cpm_expected_tangent_dev
+        _lib.check(call(self._h, K, p(d_pi0_ptr), f, p(d_dpi0_ptr), p(d_dp_drive_ptr), _vp(cd), p(d_out_ptr), p(d_dpi_next_ptr), p(d_expected_ptr)))
 
     def build_p_drive_tangent(self, p_min, p_max, e_drive):
         """d p_drive / d (p_min, p_max, e_drive) at the point, from the resident datamatrix: (Z, T, 3) float64 F-order, the direction

@@ -44,7 +44,7 @@
  * cpm_expected_sparse_fit*: cpm_expected_fit with the propagation, the trip weights and the adjoint from the compact rows.
  * CPM_FIT_DEST is refused with CPM_ERR_ARG: the e_dest direction needs the tangent of p_destin, which is a dense [T][Z][Z] array;
  * use cpm_expected_fit for it.  The sparse form of cpm_expected_grad_dest*, on a compact tangent that lifts this refusal, is
- * cpm_expected_sparse_dest.h; there is no sparse form of cpm_expected_tangent.
+ * cpm_expected_sparse_dest.h; the sparse form of cpm_expected_tangent is cpm_expected_sparse_tangent.h.
  *
  * Argument lists, layouts, flags and errors are those of the namesakes, with the two additions of cpm_expected_sparse.h:
  *   CPM_ERR_STATE when the installed p_destin tables have no compact rows; cpm_last_error() names the two routes that produce them;
