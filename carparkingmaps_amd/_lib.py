@@ -100,6 +100,9 @@ CPM_INFO_DEST_TANGENT_DENSE, CPM_INFO_DEST_TANGENT_COMPACT = 25, 26
 # every symbol include/cpm_expected_sparse_tangent.h declares (checked by tests/test_expected_sparse_tangent.py); a header and a list of its own, likewise
 EXPECTED_SPARSE_TANGENT_SYMBOLS = ["cpm_expected_sparse_tangent_dev", "cpm_expected_sparse_tangent"]
 
+# every symbol include/cpm_expected_var.h declares (checked by tests/test_expected_var.py); a header and a list of its own, likewise
+EXPECTED_VAR_SYMBOLS = ["cpm_expected_var_dev", "cpm_expected_var"]
+
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
 CPM_KERNEL_ZONE_GROUPED = 5
@@ -161,6 +164,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_sparse_grad.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_sparse_dest.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_sparse_tangent.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_var.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -305,10 +309,12 @@ def load():
     L.cpm_expected_sparse_tangent.argtypes = L.cpm_expected_tangent.argtypes
     L.cpm_build_p_drive_tangent_dev.argtypes = [vp, dbl, dbl, dbl, vp]
     L.cpm_build_p_drive_tangent.argtypes = [vp, dbl, dbl, dbl, vp]
+    L.cpm_expected_var_dev.argtypes = [vp, vp, u32, vp]
+    L.cpm_expected_var.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
                  + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS + EXPECTED_GRAD_BATCH_SYMBOLS
                  + EXPECTED_FIT_SYMBOLS + EXPECTED_TANGENT_SYMBOLS + EXPECTED_SPARSE_SYMBOLS + EXPECTED_SPARSE_GRAD_SYMBOLS
-                 + EXPECTED_SPARSE_DEST_SYMBOLS + EXPECTED_SPARSE_TANGENT_SYMBOLS):
+                 + EXPECTED_SPARSE_DEST_SYMBOLS + EXPECTED_SPARSE_TANGENT_SYMBOLS + EXPECTED_VAR_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32

@@ -31,6 +31,7 @@
 #include "../../include/cpm_expected_sparse.h"
 #include "../../include/cpm_expected_sparse_grad.h"
 #include "../../include/cpm_expected_sparse_dest.h"
+#include "../../include/cpm_expected_var.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -57,6 +58,7 @@
 #include "cpm_expected_sparse.h"
 #include "cpm_expected_sparse_grad.h"
 #include "cpm_expected_sparse_dest.h"
+#include "cpm_expected_var.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -288,6 +290,10 @@ struct cpm_ctx {
     bool exps_valid = false;
     DevBuf<double> d_exp_ws;            // [4][cap / 4] pi and x, ping and pong, of as many fleets ([Zs] each) as it was last grown for
     DevBuf<double> d_exp_out;           // [B][2][T][Z] + [Z] + [Z]: the blocking calls' outputs; pi_next and pi_0 end the allocation (exp_out_tail)
+    // exact variances (include/cpm_expected_var.h, cpm_expected_var.h): allocated on first use
+    DevBuf<double> d_var_p;             // [2][Z][Z] the transition matrix P_t, ping and pong
+    DevBuf<double> d_var_part;          // [ceil(Z / 64)][4][Z] the start-row chunks' partial sums of one hour
+    DevBuf<double> d_var_out;           // [4][T][Z] + [Z]: the blocking call's outputs, then its start weights
     // expected travel (include/cpm_expected_travel.h, cpm_expected_travel.h): the trip weights, built on first use and stale wherever
     // the p_destin tables (exp_aux_valid), d_dm or d_dist change
     DevBuf<double> d_exp_w;             // [2][T][Z] w_sec | w_km
@@ -3960,6 +3966,102 @@ int32_t cpm_expected_batch(cpm_ctx *c, const double *pi0, uint32_t flags, double
     ExpTables tb;
     if ((rc = exp_tables(c, flags, true, tb)) != CPM_OK) return rc;
     return expected_blocking(c, pi0, flags, tb.B, tb.pd, tb.q_stride, parking, driving, nullptr);
+}
+
+// ------------------------------------------------------------------ exact variances of the counts (include/cpm_expected_var.h)
+
+namespace {
+
+// a workspace of the variance call: a failed allocation names the bytes asked for
+int32_t var_reserve(DevBuf<double> &b, size_t words, const char *what)
+{
+    if (b.reserve(words) == hipSuccess) return CPM_OK;
+    (void)hipGetLastError();
+    return fail(CPM_ERR_NOMEM, "expected_var: cannot allocate %s: %zu bytes asked for", what, words * sizeof(double));
+}
+
+// P_t through the day (and, with the IVP, through hours 0 .. T-2 in front of it) and the four weighted column sums of every hour:
+// enqueued on the context's stream.  out: [4][T][Z].
+int32_t expected_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t flags, double *out)
+{
+    int32_t rc = exp_tables_ready(c, "expected_var");
+    if (rc != CPM_OK) return rc;
+    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;  // (expands sparse tables to the dense array; the row-total check)
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t zz = static_cast<size_t>(Z) * Z;
+    const int chunks = static_cast<int>(nblk(Z, cpm::kVarRedRows));
+    if ((rc = var_reserve(c->d_var_p, 2 * zz, "the two transition matrices")) != CPM_OK) return rc;
+    if ((rc = var_reserve(c->d_var_part, static_cast<size_t>(chunks) * 4 * Z, "the partial sums")) != CPM_OK) return rc;
+    double *const pm[2] = {c->d_var_p, c->d_var_p + c->d_var_p.cap / 2};
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0;  // operators in front of the day
+    const dim3 block(cpm::kVarBlock);
+    const dim3 ggrid(nblk(Z, cpm::kVarTile), nblk(Z, cpm::kVarTile));
+    auto sums = [&](const double *P, int t) {
+        cpm::launch(cpm::k_var_reduce, dim3(nblk(Z, cpm::kVarBlock), static_cast<unsigned>(chunks)), block, 0, c->stream, P, d_start,
+                    static_cast<const double *>(c->d_pdrive) + static_cast<size_t>(t) * Z, Z, c->d_var_part.get());
+        cpm::launch(cpm::k_var_final, dim3(nblk(Z, cpm::kVarBlock), 4), block, 0, c->stream, static_cast<const double *>(c->d_var_part.get()), chunks, Z, T, t,
+                    out);
+    };
+    cpm::launch(cpm::k_var_eye, dim3(nblk(static_cast<int64_t>(zz), cpm::kVarBlock)), block, 0, c->stream, pm[0], Z);
+    HIP_TRY(hipGetLastError());
+    if (pre == 0) sums(pm[0], 0);
+    // step s applies the operator of hour (s < pre ? s : s - pre); the matrix behind step pre - 1 (or I) is hour 0 of the outputs
+    const int steps = pre + T - 1;
+    for (int s = 0; s < steps; ++s) {
+        const int t = s < pre ? s : s - pre;
+        const size_t row = static_cast<size_t>(t) * Z;
+        const int in = s & 1, ot = in ^ 1;
+        cpm::launch(cpm::k_var_gemm, ggrid, block, 0, c->stream, static_cast<const double *>(pm[in]), static_cast<const double *>(c->d_p + row * Z),
+                    static_cast<const double *>(c->d_last + row), static_cast<const double *>(c->d_exp_r + row),
+                    static_cast<const int *>(c->d_exp_ell + row), static_cast<const double *>(c->d_pdrive) + row, pm[ot], Z);
+        const int day_next = s + 1 - pre;  // the hour of the day whose matrix this step produces (< 0: still in front of it)
+        if (day_next >= 0) sums(pm[ot], day_next);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipGetLastError());
+    return CPM_OK;
+}
+
+int32_t var_enter(cpm_ctx *c, uint32_t flags)
+{
+    int32_t rc = exp_flags_check(flags);
+    if (rc != CPM_OK) return rc;
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected_var: p_drive not set");
+    return CPM_OK;
+}
+
+}  // namespace
+
+int32_t cpm_expected_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, void *d_out)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_out) return fail(CPM_ERR_ARG, "expected_var_dev: null d_out");
+    if ((rc = var_enter(c, flags)) != CPM_OK) return rc;
+    return expected_var_enqueue(c, static_cast<const double *>(d_start), flags, static_cast<double *>(d_out));
+}
+
+int32_t cpm_expected_var(cpm_ctx *c, const double *start, uint32_t flags, double *mean_parking, double *mean_driving, double *var_parking,
+                         double *var_driving)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = var_enter(c, flags)) != CPM_OK) return rc;
+    if (start)
+        for (int64_t z = 0; z < c->Z; ++z)
+            if (!std::isfinite(start[z]) || start[z] < 0.0)
+                return fail(CPM_ERR_ARG, "expected_var: start of zone %lld is NaN, infinite or negative", (long long)z + 1);
+    const size_t zt = static_cast<size_t>(c->Z) * c->T;
+    if ((rc = var_reserve(c->d_var_out, 4 * zt + c->Z, "the outputs")) != CPM_OK) return rc;
+    double *const d_w = c->d_var_out + 4 * zt;
+    if (start) HIP_TRY(hipMemcpyAsync(d_w, start, sizeof(double) * c->Z, hipMemcpyHostToDevice, c->stream));
+    if ((rc = expected_var_enqueue(c, start ? d_w : nullptr, flags, c->d_var_out)) != CPM_OK) return rc;
+    double *const host[4] = {mean_parking, mean_driving, var_parking, var_driving};
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], c->d_var_out + k * zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
 }
 
 // ------------------------------------------------------------------ the same from sparse tables (include/cpm_expected_sparse.h)

@@ -83,6 +83,30 @@ def expected_objectives(parking_density, driving_density, measured_activity=None
     return out
 
 
+def count_zscores(parking, driving, ev):
+    """Per-cell z-scores (N - mean) / sqrt(var) of resample()'s (Z, T) count arrays against Sampler.expected_var()'s dict ev (with
+    start = the cars per zone the resample started from: cars_per_zone of init_states, or np.bincount(get_state() - 1,
+    minlength=Z)).  Returns dict(parking, driving: (Z, T) float64, NaN where the variance is 0; parking_fixed, driving_fixed: (Z, T)
+    bool, the cells of variance 0, reported apart; parking_fixed_ok, driving_fixed_ok: bool, every such count equals its mean, as
+    it must)."""
+    out = {}
+    for name, n in (("parking", parking), ("driving", driving)):
+        n = np.asarray(n, dtype=np.float64)
+        mean = np.asarray(ev["mean_" + name], dtype=np.float64)
+        var = np.asarray(ev["var_" + name], dtype=np.float64)
+        if n.shape != mean.shape or var.shape != mean.shape:
+            raise ValueError(f"count_zscores: {name} counts {n.shape}, mean {mean.shape}, variance {var.shape}")
+        if (var < 0).any() or np.isnan(var).any():
+            raise ValueError(f"count_zscores: a {name} variance is negative or NaN")
+        fixed = var == 0
+        z = np.full(mean.shape, np.nan)
+        np.divide(n - mean, np.sqrt(var), out=z, where=~fixed)
+        out[name] = z
+        out[name + "_fixed"] = fixed
+        out[name + "_fixed_ok"] = bool((n[fixed] == mean[fixed]).all())
+    return out
+
+
 # ------------------------------------------------------------------ host cotangents of the noise-free objectives (for Sampler.expected_grad)
 def _minmax_mse_grad(v, m, axis):
     """d/dv of mean over `axis` of ((v - lo) / (hi - lo) - m)^2, lo / hi the minimum / maximum of v along `axis` (the first one where

@@ -600,6 +600,31 @@ class Sampler:
         _lib.check(call(self._h, C.c_void_p(int(d_pi0_ptr)) if d_pi0_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
                         C.c_void_p(int(d_out_ptr)) if d_out_ptr else None, C.c_void_p(int(d_pi_next_ptr)) if d_pi_next_ptr else None))
 
+    # -- exact variances of the counts from the day's transition matrix (include/cpm_expected_var.h) --
+    def expected_var(self, start=None, ivp=False):
+        """Mean and exact variance of resample()'s counts over the seed, given the cars' start zones, blocking: a dict of four
+        (Z, T) float64 F-order arrays, mean_parking, mean_driving, var_parking, var_driving.  start: (Z,) cars that start in each
+        zone, or None (1 per zone); the outputs are linear in it.  After init_states(C, cars_per_zone) start is
+        np.full(Z, cars_per_zone); for any other state it is np.bincount(get_state() - 1, minlength=Z) (get_state() is 1-based).
+        ivp: the variances of solve_ivp() followed by resample(), given the placement in front of the IVP.  The standard error of a
+        count is sqrt(var); model_selection.count_zscores() applies it."""
+        a = None if start is None else np.ascontiguousarray(_f64(start, (self.Z,)))
+        out = {k: np.zeros((self.Z, self.T), dtype=np.float64, order="F") for k in ("mean_parking", "mean_driving", "var_parking", "var_driving")}
+        _lib.check(self._L.cpm_expected_var(self._h, _vp(a), _lib.CPM_EXPECT_IVP if ivp else 0, _vp(out["mean_parking"]), _vp(out["mean_driving"]),
+                                            _vp(out["var_parking"]), _vp(out["var_driving"])))
+        return out
+
+    def expected_var_words(self):
+        """float64 words of the expected_var_dev tensor: 4*T*Z (mean_parking[T][Z], mean_driving, var_parking, var_driving)."""
+        return 4 * self.T * self.Z
+
+    def expected_var_dev(self, d_out_ptr, d_start_ptr=0, ivp=False):
+        """Enqueue on the context's stream: d_out_ptr = device address of float64[expected_var_words()]; d_start_ptr = device address
+        of float64[Z] (the cars that start in each zone: cars_per_zone of init_states, or np.bincount of get_state()) or 0 (1 per
+        zone).  (The first call after the p_destin tables changed builds its per-table arrays and synchronises once.)"""
+        _lib.check(self._L.cpm_expected_var_dev(self._h, C.c_void_p(int(d_start_ptr)) if d_start_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
+                                                C.c_void_p(int(d_out_ptr)) if d_out_ptr else None))
+
     def expected_batch_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False, sparse=False):
         """Enqueue on the context's stream: d_out_ptr = device address of float64[B][expected_words()] for the installed batch tables.
         sparse: cpm_expected_sparse_batch_dev, as in expected()."""
