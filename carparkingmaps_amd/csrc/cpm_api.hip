@@ -32,6 +32,7 @@
 #include "../../include/cpm_expected_sparse_grad.h"
 #include "../../include/cpm_expected_sparse_dest.h"
 #include "../../include/cpm_expected_var.h"
+#include "../../include/cpm_expected_linear_var.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -59,6 +60,7 @@
 #include "cpm_expected_sparse_grad.h"
 #include "cpm_expected_sparse_dest.h"
 #include "cpm_expected_var.h"
+#include "cpm_expected_linear_var.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -294,6 +296,9 @@ struct cpm_ctx {
     DevBuf<double> d_var_p;             // [2][Z][Z] the transition matrix P_t, ping and pong
     DevBuf<double> d_var_part;          // [ceil(Z / 64)][4][Z] the start-row chunks' partial sums of one hour
     DevBuf<double> d_var_out;           // [4][T][Z] + [Z]: the blocking call's outputs, then its start weights
+    // the variance of linear functionals (include/cpm_expected_linear_var.h, cpm_expected_linear_var.h): allocated on first use
+    DevBuf<double> d_elv_ws;            // the passes' state [2][K4][2][Zs], the segments' sums [nseg][3][4][Zs], [K][2][Z] where the caller wants no d_zone
+    DevBuf<double> d_elv_io;            // [K][2][T][Z] + [K][2] + [K][2][Z] + [Z]: the blocking call's coefficients, outputs, per-zone outputs and start weights
     // expected travel (include/cpm_expected_travel.h, cpm_expected_travel.h): the trip weights, built on first use and stale wherever
     // the p_destin tables (exp_aux_valid), d_dm or d_dist change
     DevBuf<double> d_exp_w;             // [2][T][Z] w_sec | w_km
@@ -4061,6 +4066,133 @@ int32_t cpm_expected_var(cpm_ctx *c, const double *start, uint32_t flags, double
     for (int k = 0; k < 4; ++k)
         if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], c->d_var_out + k * zt, sizeof(double) * zt, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ the variance of linear functionals (include/cpm_expected_linear_var.h)
+
+namespace {
+
+int32_t elv_reserve(DevBuf<double> &b, size_t words, const char *what)
+{
+    if (b.reserve(words) == hipSuccess) return CPM_OK;
+    (void)hipGetLastError();
+    return fail(CPM_ERR_NOMEM, "expected_linear_var: cannot allocate %s: %zu bytes asked for", what, words * sizeof(double));
+}
+
+// one backward product of a pass: the smallest instantiation that holds it
+void launch_elv_u(cpm_ctx *c, int NB, const double *p_t, const double *st, int Zs, int nseg, int seg_len, int nf, double *part)
+{
+    const int Z = static_cast<int>(c->Z);
+    const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg)), block(cpm::kExpBlock);
+    const auto k = NB == 4 ? ((Z & 1) ? cpm::k_elv_u<4, true> : cpm::k_elv_u<4, false>)
+                 : NB == 2 ? ((Z & 1) ? cpm::k_elv_u<2, true> : cpm::k_elv_u<2, false>)
+                           : ((Z & 1) ? cpm::k_elv_u<1, true> : cpm::k_elv_u<1, false>);
+    cpm::launch(k, grid, block, 0, c->stream, p_t, st, Z, Zs, seg_len, nf, part);
+}
+
+// The backward pass for K functionals, operator-major with the passes of at most kElvNB functionals inside an operator (the hour's
+// block of p is read once per pass), then the weighted totals: enqueued on the context's stream.  coeff: [K][2][T][Z]; out: [K][2];
+// zone: [K][2][Z] or nullptr.
+// d_elv_ws, in vectors of Zs words: the state ping and pong, [K4][2] each (K4 = K rounded up to whole passes; a pass's state is
+// [Zs][2][NB] at its first functional's place), the segments' sums [nseg][3][kElvNB], and [K][2][Z] words where zone is nullptr.
+int32_t expected_linear_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t flags, int K, const double *coeff, double *out, double *zone)
+{
+    int32_t rc = exp_tables_ready(c, "expected_linear_var");
+    if (rc != CPM_OK) return rc;
+    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;  // (expands sparse tables to the dense array; the row-total check)
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const int Zs = (Z + 1) & ~1;
+    const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
+    const size_t nk = static_cast<size_t>(K), k4 = (nk + cpm::kElvNB - 1) / cpm::kElvNB * cpm::kElvNB;
+    const size_t state_words = k4 * 2 * Zs, part_words = static_cast<size_t>(nseg) * 3 * cpm::kElvNB * Zs, zone_words = nk * 2 * Z;
+    if ((rc = elv_reserve(c->d_elv_ws, 2 * state_words + part_words + zone_words, "the workspace")) != CPM_OK) return rc;
+    double *const ws_st[2] = {c->d_elv_ws, c->d_elv_ws + state_words};
+    double *const part = c->d_elv_ws + 2 * state_words;
+    if (!zone) zone = part + part_words;
+    const size_t zt = static_cast<size_t>(Z) * T, cot_stride = 2 * zt;
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
+    for (int s = steps - 1; s >= 0; --s) {
+        const int t = s < pre ? s : s - pre, j = s - pre;
+        const size_t row = static_cast<size_t>(t) * Z;
+        const double *p_t = c->d_p + row * Z;
+        const bool have = s != steps - 1;  // (false: mu = nu = 0 by construction, no product is formed)
+        for (int f0 = 0; f0 < K; f0 += cpm::kElvNB) {
+            const int nf = std::min(K - f0, cpm::kElvNB);
+            const int NB = nf > 2 ? 4 : nf > 1 ? 2 : 1;
+            const size_t w0 = static_cast<size_t>(f0) * 2 * Zs;
+            const double *st = have ? ws_st[(s + 1) & 1] + w0 : nullptr;
+            if (st) launch_elv_u(c, NB, p_t, st, Zs, nseg, seg_len, nf, part);
+            const double *gp = j >= 0 ? coeff + f0 * cot_stride + static_cast<size_t>(j) * Z : nullptr;
+            const double *gd = j >= 0 ? gp + zt : nullptr;
+            cpm::launch(cpm::k_elv_finish, dim3(nblk(Z, cpm::kFinishBlock), static_cast<unsigned>(NB)), dim3(cpm::kFinishBlock), 0, c->stream,
+                        static_cast<const double *>(part), nseg, Zs, static_cast<const double *>(c->d_last + row), static_cast<const int *>(c->d_exp_ell + row),
+                        static_cast<const double *>(c->d_exp_r + row), static_cast<const double *>(c->d_pdrive) + row, st, NB, gp, gd, cot_stride, Z, nf,
+                        ws_st[s & 1] + w0, s == 0 ? zone + static_cast<size_t>(f0) * 2 * Z : static_cast<double *>(nullptr));
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    cpm::launch(cpm::k_elv_total, dim3(2, static_cast<unsigned>(K)), dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(zone), d_start, Z, out);
+    HIP_TRY(hipGetLastError());
+    return CPM_OK;
+}
+
+int32_t elv_enter(cpm_ctx *c, uint32_t flags, int32_t K)
+{
+    int32_t rc = exp_flags_check(flags);
+    if (rc != CPM_OK) return rc;
+    if (K < 1 || K > CPM_MAX_BATCH) return fail(CPM_ERR_ARG, "expected_linear_var: K = %d outside 1..%d", K, CPM_MAX_BATCH);
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected_linear_var: p_drive not set");
+    return CPM_OK;
+}
+
+}  // namespace
+
+int32_t cpm_expected_linear_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_coeff) return fail(CPM_ERR_ARG, "expected_linear_var_dev: null d_coeff");
+    if (!d_out) return fail(CPM_ERR_ARG, "expected_linear_var_dev: null d_out");
+    if ((rc = elv_enter(c, flags, K)) != CPM_OK) return rc;
+    return expected_linear_var_enqueue(c, static_cast<const double *>(d_start), flags, K, static_cast<const double *>(d_coeff), static_cast<double *>(d_out),
+                                       static_cast<double *>(d_zone));
+}
+
+int32_t cpm_expected_linear_var(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving, double *mean,
+                                double *var, double *zone_mean, double *zone_var)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!a_parking || !b_driving) return fail(CPM_ERR_ARG, "expected_linear_var: null coefficients");
+    if (!mean || !var) return fail(CPM_ERR_ARG, "expected_linear_var: null mean or var");
+    if ((rc = elv_enter(c, flags, K)) != CPM_OK) return rc;
+    const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nk = static_cast<size_t>(K);
+    if (start)
+        for (size_t z = 0; z < Z; ++z)
+            if (!std::isfinite(start[z]) || start[z] < 0.0)
+                return fail(CPM_ERR_ARG, "expected_linear_var: start of zone %lld is NaN, infinite or negative", (long long)z + 1);
+    for (size_t i = 0; i < nk * zt; ++i)
+        if (!std::isfinite(a_parking[i]) || !std::isfinite(b_driving[i]))
+            return fail(CPM_ERR_ARG, "expected_linear_var: the coefficient of functional %lld, zone %lld, hour %lld is not finite", (long long)(i / zt) + 1,
+                        (long long)(i % Z) + 1, (long long)(i % zt / Z) + 1);
+    if ((rc = elv_reserve(c->d_elv_io, nk * (2 * zt + 2 + 2 * Z) + Z, "the blocking call's arrays")) != CPM_OK) return rc;
+    double *const d_coeff = c->d_elv_io, *const d_out = d_coeff + nk * 2 * zt, *const d_zone = d_out + nk * 2, *const d_w = d_zone + nk * 2 * Z;
+    for (size_t k = 0; k < nk; ++k) {
+        HIP_TRY(hipMemcpyAsync(d_coeff + k * 2 * zt, a_parking + k * zt, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_coeff + k * 2 * zt + zt, b_driving + k * zt, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+    }
+    if (start) HIP_TRY(hipMemcpyAsync(d_w, start, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    if ((rc = expected_linear_var_enqueue(c, start ? d_w : nullptr, flags, K, d_coeff, d_out, d_zone)) != CPM_OK) return rc;
+    std::vector<double> h_out(nk * 2);
+    HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, sizeof(double) * nk * 2, hipMemcpyDeviceToHost, c->stream));
+    for (size_t k = 0; k < nk; ++k) {
+        if (zone_mean) HIP_TRY(hipMemcpyAsync(zone_mean + k * Z, d_zone + k * 2 * Z, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
+        if (zone_var) HIP_TRY(hipMemcpyAsync(zone_var + k * Z, d_zone + k * 2 * Z + Z, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < nk; ++k) mean[k] = h_out[2 * k], var[k] = h_out[2 * k + 1];
     return CPM_OK;
 }
 

@@ -107,6 +107,50 @@ def count_zscores(parking, driving, ev):
     return out
 
 
+# ------------------------------------------------------------------ the seed noise of the objectives (Sampler.expected_linear_var)
+def activity_noise(sampler, start, ivp=False):
+    """Exact mean and variance over the seed of driving_sum[t] = sum over z of resample()'s driving[z, t], for every hour: T
+    functionals with B_k = 1 on hour k (Sampler.expected_linear_var).  start: (Z,) cars per start zone, or None (1 per zone).  Returns
+    dict(mean (T,), var (T,)).  T is at most CPM_MAX_BATCH."""
+    Z, T = sampler.Z, sampler.T
+    b = np.zeros((Z, T, T), order="F")
+    for k in range(T):
+        b[:, k, k] = 1.0
+    return sampler.expected_linear_var(np.zeros((Z, T, T), order="F"), b, start=start, ivp=ivp)
+
+
+def objective_noise_functionals(densities, C, measured_activity=None, measured_parking=None):
+    """The coefficient arrays objective_noise() passes to Sampler.expected_linear_var: (names, a_parking (Z, T, K), b_driving
+    (Z, T, K)), the objectives' gradients at the expected densities over C."""
+    parking, driving = (np.asarray(d, dtype=np.float64) for d in densities)
+    names, a, b = [], [], []
+    zero = np.zeros(parking.shape, order="F")
+    if measured_activity is not None:
+        names.append("activity_error")
+        a.append(zero)
+        b.append(traffic_activity_error_grad(driving, measured_activity) / float(C))
+    if measured_parking is not None:
+        names.append("parking_error")
+        a.append(parking_density_error_grad(parking, measured_parking) / float(C))
+        b.append(zero)
+    if not names:
+        raise ValueError("objective_noise: neither measured_activity nor measured_parking is given")
+    return names, np.asfortranarray(np.stack(a, axis=2)), np.asfortranarray(np.stack(b, axis=2))
+
+
+def objective_noise(sampler, densities, C, start, measured_activity=None, measured_parking=None, ivp=False):
+    """The FIRST-ORDER (delta-method) standard deviation over the seed of activity_error and parking_error of ONE resample of C cars:
+    the objective is linearised at the expected densities (parking, driving) = densities (Sampler.expected() with pi_0 = start / C),
+    its gradient (traffic_activity_error_grad / parking_density_error_grad, per density) over C is a linear functional of the counts,
+    and Sampler.expected_linear_var gives that functional's exact variance.  Exact only for an objective that is linear in the
+    counts; the errors are quadratic and min-max normalised, so this is the leading term for large C, and it is 0 where the gradient
+    vanishes (a perfect fit), where the true spread is of second order.  start: (Z,) cars per start zone (sum C), or None.  Returns
+    dict(activity_error_std, parking_error_std) for the objectives whose measured data is given."""
+    names, a, b = objective_noise_functionals(densities, C, measured_activity, measured_parking)
+    r = sampler.expected_linear_var(a, b, start=start, ivp=ivp)
+    return {name + "_std": float(np.sqrt(r["var"][k])) for k, name in enumerate(names)}
+
+
 # ------------------------------------------------------------------ host cotangents of the noise-free objectives (for Sampler.expected_grad)
 def _minmax_mse_grad(v, m, axis):
     """d/dv of mean over `axis` of ((v - lo) / (hi - lo) - m)^2, lo / hi the minimum / maximum of v along `axis` (the first one where
@@ -430,6 +474,19 @@ class Evaluator:
         from.  `parking` / `driving` are densities (counts / C in the mean).  Needs no cars."""
         self._install(pt)
         return self._expected_from_device([pt], ivp, False)[0]
+
+    def expected_noise(self, pt, ivp=True):
+        """The seed noise of one point's resample of C cars: installs pt's tables and returns dict(activity: activity_noise()'s mean
+        and var of driving_sum[t], and objective_noise()'s first-order activity_error_std / parking_error_std where the measured data
+        is given).  The cars start C / Z per zone (init_states' uniform placement; ivp: in front of the IVP), the start of
+        evaluate_expected()."""
+        self._install(pt)
+        s = self.sampler
+        start = np.full(s.Z, self.C / s.Z)
+        out = {"activity": activity_noise(s, start, ivp=ivp)}
+        if self.measured_activity is not None or self.measured_parking is not None:
+            out.update(objective_noise(s, s.expected(None, ivp=ivp), self.C, start, self.measured_activity, self.measured_parking, ivp=ivp))
+        return out
 
     def evaluate_expected_batch(self, pts, ivp=True):
         """The same for points that share e_dest, as the fleets of ONE batched propagation (build_p_drive_batch, expected_batch_dev,

@@ -625,6 +625,40 @@ class Sampler:
         _lib.check(self._L.cpm_expected_var_dev(self._h, C.c_void_p(int(d_start_ptr)) if d_start_ptr else None, _lib.CPM_EXPECT_IVP if ivp else 0,
                                                 C.c_void_p(int(d_out_ptr)) if d_out_ptr else None))
 
+    # -- the exact seed variance of linear functionals of the counts (include/cpm_expected_linear_var.h) --
+    def expected_linear_var(self, a_parking, b_driving, start=None, ivp=False, per_zone=False):
+        """Exact mean and variance over the seed of L = sum(a_parking * parking) + sum(b_driving * driving) of resample()'s (Z, T)
+        count arrays, given the cars' start zones, blocking: one backward pass over the p_destin tables, with every covariance between
+        zones and between hours in it.  a_parking / b_driving: (Z, T), or (Z, T, K) for K functionals (at most CPM_MAX_BATCH) in one
+        call; functional k carries the bits of a call on it alone.  start, ivp: as in expected_var().  Returns dict(mean, var): floats
+        for (Z, T) inputs, (K,) arrays otherwise; per_zone: also zone_mean, zone_var ((Z,) or (Z, K)): the mean and the variance one
+        car that starts in each zone contributes -- mean = start @ zone_mean, var = start @ zone_var."""
+        a, b = np.asarray(a_parking, dtype=np.float64), np.asarray(b_driving, dtype=np.float64)
+        single = a.ndim == 2
+        if a.shape != b.shape or a.ndim not in (2, 3) or a.shape[:2] != (self.Z, self.T) or (a.ndim == 3 and a.shape[2] < 1):
+            raise ValueError(f"expected_linear_var: coefficients {a.shape} and {b.shape}, expected two of ({self.Z}, {self.T}) or ({self.Z}, {self.T}, K)")
+        K = 1 if single else a.shape[2]
+        a, b = np.asfortranarray(a.reshape(self.Z, self.T, K, order="F")), np.asfortranarray(b.reshape(self.Z, self.T, K, order="F"))
+        w = None if start is None else np.ascontiguousarray(_f64(start, (self.Z,)))
+        mean, var = np.zeros(K), np.zeros(K)
+        zm = np.zeros((self.Z, K), order="F") if per_zone else None
+        zv = np.zeros((self.Z, K), order="F") if per_zone else None
+        _lib.check(self._L.cpm_expected_linear_var(self._h, _vp(w), _lib.CPM_EXPECT_IVP if ivp else 0, K, _vp(a), _vp(b), _vp(mean), _vp(var),
+                                                   _vp(zm), _vp(zv)))
+        out = {"mean": float(mean[0]), "var": float(var[0])} if single else {"mean": mean, "var": var}
+        if per_zone:
+            out["zone_mean"], out["zone_var"] = (zm[:, 0], zv[:, 0]) if single else (zm, zv)
+        return out
+
+    def expected_linear_var_dev(self, K, d_coeff_ptr, d_out_ptr, d_start_ptr=0, ivp=False, d_zone_ptr=0):
+        """Enqueue on the context's stream: d_coeff_ptr = device address of float64[K][2][T][Z] (A_k then B_k, the layout of
+        expected_grad_dev's cotangent); d_out_ptr = device address of float64[K][2] (mean, variance); d_start_ptr = device address of
+        float64[Z] or 0 (1 per zone); d_zone_ptr = device address of float64[K][2][Z] (per start zone) or 0.  (The first call after the
+        p_destin tables changed builds its per-table arrays and synchronises once.)"""
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        _lib.check(self._L.cpm_expected_linear_var_dev(self._h, p(d_start_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, int(K), p(d_coeff_ptr), p(d_out_ptr),
+                                                       p(d_zone_ptr)))
+
     def expected_batch_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False, sparse=False):
         """Enqueue on the context's stream: d_out_ptr = device address of float64[B][expected_words()] for the installed batch tables.
         sparse: cpm_expected_sparse_batch_dev, as in expected()."""
