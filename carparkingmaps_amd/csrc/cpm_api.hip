@@ -33,6 +33,7 @@
 #include "../../include/cpm_expected_sparse_dest.h"
 #include "../../include/cpm_expected_var.h"
 #include "../../include/cpm_expected_linear_var.h"
+#include "../../include/cpm_expected_travel_var.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -61,6 +62,7 @@
 #include "cpm_expected_sparse_dest.h"
 #include "cpm_expected_var.h"
 #include "cpm_expected_linear_var.h"
+#include "cpm_expected_travel_var.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -305,6 +307,13 @@ struct cpm_ctx {
     DevBuf<double> d_exp_wpart;         // [segments][2][T][Z] the destination segments' sums
     bool exp_trip_valid = false;
     int64_t exp_trip_builds = 0;
+    // the trip variance weights (include/cpm_expected_travel_var.h, cpm_expected_travel_var.h): built behind the trip weights, and again
+    // whenever those were rebuilt (exp_tvar_trip_build is the value of exp_trip_builds they were built at) -- one invalidation for both
+    DevBuf<double> d_exp_vsec;          // [T][Z] v_sec
+    int64_t exp_tvar_trip_build = 0;    // 0: never built
+    int64_t exp_tvar_builds = 0;
+    DevBuf<double> d_etv_ws;            // the passes' state [2][K2][2][Zs], the segments' sums [nseg][3][2][Zs], [K][2][Z] where the caller wants no d_zone
+    DevBuf<double> d_etv_io;            // [K][4][T][Z] + [K][2] + [K][2][Z] + [Z]: the blocking call's coefficients, outputs, per-zone outputs and start weights
     // ... and the same weights from the compact rows (include/cpm_expected_sparse_grad.h): a cache of their own, so that a sparse call
     // never changes what a later dense call returns; stale wherever exp_trip_valid or exps_valid is
     DevBuf<double> d_exps_w;            // [2][T][Z] w_sec | w_km
@@ -4185,6 +4194,195 @@ int32_t cpm_expected_linear_var(cpm_ctx *c, const double *start, uint32_t flags,
     }
     if (start) HIP_TRY(hipMemcpyAsync(d_w, start, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
     if ((rc = expected_linear_var_enqueue(c, start ? d_w : nullptr, flags, K, d_coeff, d_out, d_zone)) != CPM_OK) return rc;
+    std::vector<double> h_out(nk * 2);
+    HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, sizeof(double) * nk * 2, hipMemcpyDeviceToHost, c->stream));
+    for (size_t k = 0; k < nk; ++k) {
+        if (zone_mean) HIP_TRY(hipMemcpyAsync(zone_mean + k * Z, d_zone + k * 2 * Z, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
+        if (zone_var) HIP_TRY(hipMemcpyAsync(zone_var + k * Z, d_zone + k * 2 * Z + Z, sizeof(double) * Z, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < nk; ++k) mean[k] = h_out[2 * k], var[k] = h_out[2 * k + 1];
+    return CPM_OK;
+}
+
+// ------------------------------------------------------------------ the variance of travel functionals (include/cpm_expected_travel_var.h)
+
+namespace {
+
+int32_t etv_reserve(DevBuf<double> &b, size_t words, const char *what)
+{
+    if (b.reserve(words) == hipSuccess) return CPM_OK;
+    (void)hipGetLastError();
+    return fail(CPM_ERR_NOMEM, "expected_travel_var: cannot allocate %s: %zu bytes asked for", what, words * sizeof(double));
+}
+
+// The trip variance weights of the installed p_destin tables and datamatrix in d_exp_vsec: once per build of the trip weights
+// (ensure_exp_trip reports a missing table, datamatrix or distance matrix and rebuilds under every condition these share).
+int32_t ensure_exp_trip_var(cpm_ctx *c)
+{
+    int32_t rc = ensure_exp_trip(c);
+    if (rc != CPM_OK) return rc;
+    if ((rc = ensure_dense_p(c)) != CPM_OK) return rc;  // (the callers read d_p)
+    if (c->exp_tvar_trip_build == c->exp_trip_builds) return CPM_OK;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const size_t zt = static_cast<size_t>(Z) * T, plane = zt * Z;
+    const int nseg = cpm::trip_segments(Z, T), seg_len = cpm::trip_segment_len(Z, nseg);
+    if ((rc = etv_reserve(c->d_exp_vsec, zt, "the trip variance weights")) != CPM_OK) return rc;
+    HIP_TRY(c->d_exp_wpart.reserve(2 * zt * nseg));  // (scratch of every build of trip weights: nothing reads it afterwards)
+    const double *mean = c->d_dm.get(), *sdev = mean + plane;
+    const dim3 grid(nblk(Z, cpm::kTripStrip), static_cast<unsigned>(T), static_cast<unsigned>(nseg));
+    if (Z & 1) cpm::launch(cpm::k_exp_trip_var<true>, grid, dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(c->d_p.get()), mean, sdev, Z, T,
+                           seg_len, c->d_exp_wpart.get());
+    else cpm::launch(cpm::k_exp_trip_var<false>, grid, dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(c->d_p.get()), mean, sdev, Z, T,
+                     seg_len, c->d_exp_wpart.get());
+    HIP_TRY(hipGetLastError());
+    cpm::launch(cpm::k_exp_trip_var_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream,
+                static_cast<const double *>(c->d_exp_wpart.get()), nseg, mean, sdev, static_cast<const double *>(c->d_last),
+                static_cast<const int *>(c->d_exp_ell.get()), static_cast<const double *>(c->d_exp_r.get()), Z, T, c->d_exp_vsec.get());
+    HIP_TRY(hipGetLastError());
+    c->exp_tvar_trip_build = c->exp_trip_builds;
+    ++c->exp_tvar_builds;
+    return CPM_OK;
+}
+
+// one backward product of a pass: the smallest instantiation that holds it
+void launch_etv_u(cpm_ctx *c, int NB, const double *p_t, const double *m_t, const double *st, const double *cs, const double *cd, size_t cot_stride, int Zs,
+                  int nseg, int seg_len, int nf, double *part)
+{
+    const int Z = static_cast<int>(c->Z);
+    const dim3 grid(nblk(Z, cpm::kGradStrip), static_cast<unsigned>(nseg)), block(cpm::kExpBlock);
+    const auto k = NB == 2 ? ((Z & 1) ? cpm::k_etv_u<2, true> : cpm::k_etv_u<2, false>) : ((Z & 1) ? cpm::k_etv_u<1, true> : cpm::k_etv_u<1, false>);
+    cpm::launch(k, grid, block, 0, c->stream, p_t, m_t, static_cast<const double *>(c->d_dist.get()), st, cs, cd, cot_stride, Z, Zs, seg_len, nf, part);
+}
+
+// The backward pass for K functionals, operator-major with the passes of at most kEtvNB functionals inside an operator, then the
+// weighted totals: enqueued on the context's stream.  coeff: [K][4][T][Z] (A, B, S, D); out: [K][2]; zone: [K][2][Z] or nullptr.
+// d_etv_ws, in vectors of Zs words: the state ping and pong, [K2][2] each (K2 = K rounded up to whole passes; a pass's state is
+// [Zs][2][NB] at its first functional's place), the segments' sums [nseg][3][kEtvNB], and [K][2][Z] words where zone is nullptr.
+// The state behind the last operator is zeroed and its product is formed like every other: zeta = e there.
+int32_t expected_travel_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t flags, int K, const double *coeff, double *out, double *zone)
+{
+    int32_t rc = ensure_exp_trip_var(c);  // (the tables, the datamatrix and the distances; expands sparse tables to the dense array)
+    if (rc != CPM_OK) return rc;
+    const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+    const int Zs = (Z + 1) & ~1;
+    const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
+    const size_t nk = static_cast<size_t>(K), k2 = (nk + cpm::kEtvNB - 1) / cpm::kEtvNB * cpm::kEtvNB;
+    const size_t state_words = k2 * 2 * Zs, part_words = static_cast<size_t>(nseg) * 3 * cpm::kEtvNB * Zs, zone_words = nk * 2 * Z;
+    if ((rc = etv_reserve(c->d_etv_ws, 2 * state_words + part_words + zone_words, "the workspace")) != CPM_OK) return rc;
+    double *const ws_st[2] = {c->d_etv_ws, c->d_etv_ws + state_words};
+    double *const part = c->d_etv_ws + 2 * state_words;
+    if (!zone) zone = part + part_words;
+    const size_t zt = static_cast<size_t>(Z) * T, cot_stride = 4 * zt;
+    const int pre = (flags & CPM_EXPECT_IVP) ? T - 1 : 0, steps = pre + T;
+    HIP_TRY(hipMemsetAsync(ws_st[steps & 1], 0, sizeof(double) * state_words, c->stream));  // mu = nu = 0 behind the last operator
+    for (int s = steps - 1; s >= 0; --s) {
+        const int t = s < pre ? s : s - pre, j = s - pre;
+        const size_t row = static_cast<size_t>(t) * Z;
+        const double *p_t = c->d_p + row * Z, *m_t = c->d_dm + row * Z;
+        for (int f0 = 0; f0 < K; f0 += cpm::kEtvNB) {
+            const int nf = std::min(K - f0, cpm::kEtvNB);
+            const int NB = nf > 1 ? 2 : 1;
+            const size_t w0 = static_cast<size_t>(f0) * 2 * Zs;
+            const double *st = ws_st[(s + 1) & 1] + w0;
+            const double *gp = j >= 0 ? coeff + f0 * cot_stride + static_cast<size_t>(j) * Z : nullptr;
+            const double *gd = j >= 0 ? gp + zt : nullptr, *cs = j >= 0 ? gp + 2 * zt : nullptr, *cd = j >= 0 ? gp + 3 * zt : nullptr;
+            launch_etv_u(c, NB, p_t, m_t, st, cs, cd, cot_stride, Zs, nseg, seg_len, nf, part);
+            cpm::launch(cpm::k_etv_finish, dim3(nblk(Z, cpm::kFinishBlock), static_cast<unsigned>(NB)), dim3(cpm::kFinishBlock), 0, c->stream,
+                        static_cast<const double *>(part), nseg, Zs, static_cast<const double *>(c->d_last + row), static_cast<const int *>(c->d_exp_ell + row),
+                        static_cast<const double *>(c->d_exp_r + row), static_cast<const double *>(c->d_pdrive) + row, m_t,
+                        static_cast<const double *>(c->d_dist.get()), static_cast<const double *>(c->d_exp_vsec + row), st, NB, gp, gd, cs, cd, cot_stride, Z,
+                        nf, ws_st[s & 1] + w0, s == 0 ? zone + static_cast<size_t>(f0) * 2 * Z : static_cast<double *>(nullptr));
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    cpm::launch(cpm::k_elv_total, dim3(2, static_cast<unsigned>(K)), dim3(cpm::kExpBlock), 0, c->stream, static_cast<const double *>(zone), d_start, Z, out);
+    HIP_TRY(hipGetLastError());
+    return CPM_OK;
+}
+
+int32_t etv_enter(cpm_ctx *c, uint32_t flags, int32_t K)
+{
+    int32_t rc = exp_flags_check(flags);
+    if (rc != CPM_OK) return rc;
+    if (K < 1 || K > CPM_MAX_BATCH) return fail(CPM_ERR_ARG, "expected_travel_var: K = %d outside 1..%d", K, CPM_MAX_BATCH);
+    CTX_TRY(c);
+    if (!c->have_pdrive) return fail(CPM_ERR_STATE, "expected_travel_var: p_drive not set");
+    return CPM_OK;
+}
+
+}  // namespace
+
+int32_t cpm_expected_trip_var_dev(cpm_ctx *c, void *d_v)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_v) return fail(CPM_ERR_ARG, "expected_trip_var_dev: null d_v");
+    CTX_TRY(c);
+    if ((rc = ensure_exp_trip_var(c)) != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(d_v, c->d_exp_vsec, sizeof(double) * c->Z * c->T, hipMemcpyDeviceToDevice, c->stream));
+    return CPM_OK;
+}
+
+int32_t cpm_expected_trip_var(cpm_ctx *c, double *v_sec)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!v_sec) return fail(CPM_ERR_ARG, "expected_trip_var: null v_sec");
+    CTX_TRY(c);
+    if ((rc = ensure_exp_trip_var(c)) != CPM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(v_sec, c->d_exp_vsec, sizeof(double) * c->Z * c->T, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CPM_OK;
+}
+
+int64_t cpm_expected_trip_var_builds(const cpm_ctx *c)
+{
+    const int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    return c->exp_tvar_builds;
+}
+
+int32_t cpm_expected_travel_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!d_coeff) return fail(CPM_ERR_ARG, "expected_travel_var_dev: null d_coeff");
+    if (!d_out) return fail(CPM_ERR_ARG, "expected_travel_var_dev: null d_out");
+    if ((rc = etv_enter(c, flags, K)) != CPM_OK) return rc;
+    return expected_travel_var_enqueue(c, static_cast<const double *>(d_start), flags, K, static_cast<const double *>(d_coeff), static_cast<double *>(d_out),
+                                       static_cast<double *>(d_zone));
+}
+
+int32_t cpm_expected_travel_var(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving,
+                                const double *s_seconds, const double *d_km, double *mean, double *var, double *zone_mean, double *zone_var)
+{
+    int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    if (!a_parking || !b_driving) return fail(CPM_ERR_ARG, "expected_travel_var: null coefficients");
+    if (!mean || !var) return fail(CPM_ERR_ARG, "expected_travel_var: null mean or var");
+    if ((rc = etv_enter(c, flags, K)) != CPM_OK) return rc;
+    const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nk = static_cast<size_t>(K);
+    if (start)
+        for (size_t z = 0; z < Z; ++z)
+            if (!std::isfinite(start[z]) || start[z] < 0.0)
+                return fail(CPM_ERR_ARG, "expected_travel_var: start of zone %lld is NaN, infinite or negative", (long long)z + 1);
+    const double *const host[4] = {a_parking, b_driving, s_seconds, d_km};
+    for (size_t i = 0; i < nk * zt; ++i)
+        for (int a = 0; a < 4; ++a)
+            if (host[a] && !std::isfinite(host[a][i]))
+                return fail(CPM_ERR_ARG, "expected_travel_var: the coefficient of functional %lld, zone %lld, hour %lld is not finite", (long long)(i / zt) + 1,
+                            (long long)(i % Z) + 1, (long long)(i % zt / Z) + 1);
+    if ((rc = etv_reserve(c->d_etv_io, nk * (4 * zt + 2 + 2 * Z) + Z, "the blocking call's arrays")) != CPM_OK) return rc;
+    double *const d_coeff = c->d_etv_io, *const d_out = d_coeff + nk * 4 * zt, *const d_zone = d_out + nk * 2, *const d_w = d_zone + nk * 2 * Z;
+    for (size_t k = 0; k < nk; ++k)
+        for (int a = 0; a < 4; ++a) {
+            double *const dst = d_coeff + (k * 4 + a) * zt;
+            if (host[a]) HIP_TRY(hipMemcpyAsync(dst, host[a] + k * zt, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
+            else HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * zt, c->stream));  // (a NULL trip array: zeros)
+        }
+    if (start) HIP_TRY(hipMemcpyAsync(d_w, start, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
+    if ((rc = expected_travel_var_enqueue(c, start ? d_w : nullptr, flags, K, d_coeff, d_out, d_zone)) != CPM_OK) return rc;
     std::vector<double> h_out(nk * 2);
     HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, sizeof(double) * nk * 2, hipMemcpyDeviceToHost, c->stream));
     for (size_t k = 0; k < nk; ++k) {

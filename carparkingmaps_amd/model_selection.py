@@ -151,6 +151,23 @@ def objective_noise(sampler, densities, C, start, measured_activity=None, measur
     return {name + "_std": float(np.sqrt(r["var"][k])) for k, name in enumerate(names)}
 
 
+def travel_noise(sampler, start, ivp=False):
+    """Exact mean and standard deviation over the seed of the travel of ONE resample(travel=True): the total seconds, the total
+    kilometres and A_drive = total seconds / (C * T * 3600), the formula of a_drive(), with C = sum(start)
+    (Sampler.expected_travel_var with S = 1, and with D = 1).  start: (Z,) cars per start zone.  Returns dict(seconds_mean,
+    seconds_std, km_mean, km_std, A_drive_mean, A_drive_std)."""
+    Z, T = sampler.Z, sampler.T
+    zero = np.zeros((Z, T, 2), order="F")
+    s, d = np.zeros((Z, T, 2), order="F"), np.zeros((Z, T, 2), order="F")
+    s[:, :, 0] = 1.0
+    d[:, :, 1] = 1.0
+    r = sampler.expected_travel_var(zero, zero, s, d, start=start, ivp=ivp)
+    C = float(np.asarray(start, dtype=np.float64).sum())
+    std = np.sqrt(r["var"])
+    return {"seconds_mean": float(r["mean"][0]), "seconds_std": float(std[0]), "km_mean": float(r["mean"][1]), "km_std": float(std[1]),
+            "A_drive_mean": float(r["mean"][0]) / (C * T * 60 * 60), "A_drive_std": float(std[0]) / (C * T * 60 * 60)}
+
+
 # ------------------------------------------------------------------ host cotangents of the noise-free objectives (for Sampler.expected_grad)
 def _minmax_mse_grad(v, m, axis):
     """d/dv of mean over `axis` of ((v - lo) / (hi - lo) - m)^2, lo / hi the minimum / maximum of v along `axis` (the first one where
@@ -475,17 +492,19 @@ class Evaluator:
         self._install(pt)
         return self._expected_from_device([pt], ivp, False)[0]
 
-    def expected_noise(self, pt, ivp=True):
+    def expected_noise(self, pt, ivp=True, travel=False):
         """The seed noise of one point's resample of C cars: installs pt's tables and returns dict(activity: activity_noise()'s mean
         and var of driving_sum[t], and objective_noise()'s first-order activity_error_std / parking_error_std where the measured data
         is given).  The cars start C / Z per zone (init_states' uniform placement; ivp: in front of the IVP), the start of
-        evaluate_expected()."""
+        evaluate_expected().  travel: also A_drive: travel_noise()'s dict (exact, no linearisation)."""
         self._install(pt)
         s = self.sampler
         start = np.full(s.Z, self.C / s.Z)
         out = {"activity": activity_noise(s, start, ivp=ivp)}
         if self.measured_activity is not None or self.measured_parking is not None:
             out.update(objective_noise(s, s.expected(None, ivp=ivp), self.C, start, self.measured_activity, self.measured_parking, ivp=ivp))
+        if travel:
+            out["A_drive"] = travel_noise(s, start, ivp=ivp)
         return out
 
     def evaluate_expected_batch(self, pts, ivp=True):
