@@ -107,6 +107,10 @@ EXPECTED_LINEAR_VAR_SYMBOLS = ["cpm_expected_linear_var_dev", "cpm_expected_line
 # every symbol include/cpm_expected_travel_var.h declares (checked by tests/test_expected_travel_var.py); likewise
 EXPECTED_TRAVEL_VAR_SYMBOLS = ["cpm_expected_trip_var_dev", "cpm_expected_trip_var", "cpm_expected_trip_var_builds", "cpm_expected_travel_var_dev",
                                "cpm_expected_travel_var"]
+# every symbol include/cpm_expected_sparse_var.h declares (checked by tests/test_expected_sparse_var.py); likewise
+EXPECTED_SPARSE_VAR_SYMBOLS = ["cpm_expected_sparse_linear_var_dev", "cpm_expected_sparse_linear_var", "cpm_expected_sparse_trip_var_dev",
+                               "cpm_expected_sparse_trip_var", "cpm_expected_sparse_trip_var_builds", "cpm_expected_sparse_travel_var_dev",
+                               "cpm_expected_sparse_travel_var"]
 
 CPM_FLAG_TRAVEL = 1
 CPM_KERNEL_AUTO, CPM_KERNEL_CAR, CPM_KERNEL_ZONE_LDS = 0, 1, 2
@@ -172,6 +176,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_var.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_linear_var.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_travel_var.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "cpm_expected_sparse_var.h"))
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
         return LIB_PATH
@@ -325,16 +330,24 @@ def load():
     L.cpm_expected_trip_var_builds.argtypes = [vp]
     L.cpm_expected_travel_var_dev.argtypes = [vp, vp, u32, i32, vp, vp, vp]
     L.cpm_expected_travel_var.argtypes = [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.cpm_expected_sparse_linear_var_dev.argtypes = L.cpm_expected_linear_var_dev.argtypes
+    L.cpm_expected_sparse_linear_var.argtypes = L.cpm_expected_linear_var.argtypes
+    L.cpm_expected_sparse_trip_var_dev.argtypes = L.cpm_expected_trip_var_dev.argtypes
+    L.cpm_expected_sparse_trip_var.argtypes = L.cpm_expected_trip_var.argtypes
+    L.cpm_expected_sparse_trip_var_builds.argtypes = L.cpm_expected_trip_var_builds.argtypes
+    L.cpm_expected_sparse_travel_var_dev.argtypes = L.cpm_expected_travel_var_dev.argtypes
+    L.cpm_expected_sparse_travel_var.argtypes = L.cpm_expected_travel_var.argtypes
     for name in (SYMBOLS + BATCH_SYMBOLS + FLOWS_SYMBOLS + FLOWS_CSR_SYMBOLS + STAYS_SYMBOLS + PATHS_SYMBOLS + CHARGE_SYMBOLS + OBJECTIVES_SYMBOLS
                  + EXPECTED_SYMBOLS + EXPECTED_TRAVEL_SYMBOLS + EXPECTED_GRAD_SYMBOLS + EXPECTED_GRAD_DEST_SYMBOLS + EXPECTED_GRAD_BATCH_SYMBOLS
                  + EXPECTED_FIT_SYMBOLS + EXPECTED_TANGENT_SYMBOLS + EXPECTED_SPARSE_SYMBOLS + EXPECTED_SPARSE_GRAD_SYMBOLS
                  + EXPECTED_SPARSE_DEST_SYMBOLS + EXPECTED_SPARSE_TANGENT_SYMBOLS + EXPECTED_VAR_SYMBOLS + EXPECTED_LINEAR_VAR_SYMBOLS
-                 + EXPECTED_TRAVEL_VAR_SYMBOLS):
+                 + EXPECTED_TRAVEL_VAR_SYMBOLS + EXPECTED_SPARSE_VAR_SYMBOLS):
         fn = getattr(L, name)
         if name not in ("cpm_last_error",):
             fn.restype = i32
     L.cpm_expected_trip_builds.restype = i64  # (a counter; negative: a status code)
     L.cpm_expected_trip_var_builds.restype = i64
+    L.cpm_expected_sparse_trip_var_builds.restype = i64
     _lib = L
     return L
 

@@ -34,6 +34,7 @@
 #include "../../include/cpm_expected_var.h"
 #include "../../include/cpm_expected_linear_var.h"
 #include "../../include/cpm_expected_travel_var.h"
+#include "../../include/cpm_expected_sparse_var.h"
 #include "cpm_kernels.h"
 #include "cpm_flows.h"
 #include "cpm_flows_csr.h"
@@ -63,6 +64,7 @@
 #include "cpm_expected_var.h"
 #include "cpm_expected_linear_var.h"
 #include "cpm_expected_travel_var.h"
+#include "cpm_expected_sparse_var.h"
 #include "cpm_buf.h"
 
 static hipError_t ensure_stream(cpm_ctx *c);
@@ -344,6 +346,11 @@ struct cpm_ctx {
     DevBuf<double> d_fits_dw;           // [2][T][Z] the trip weights' tangent of the sparse fit, kept while sdp and the sparse trip weights stay
     int64_t fits_dw_gen = -1, fits_dw_builds = -1;
     int64_t exps_trip_builds = 0;       // builds of d_exps_w so far
+    // ... and the trip variance weights from the compact rows (include/cpm_expected_sparse_var.h): a cache of their own behind d_exps_w,
+    // as d_exp_vsec is behind d_exp_w (exps_tvar_trip_build is the value of exps_trip_builds they were built at)
+    DevBuf<double> d_exps_vsec;         // [T][Z] v_sec
+    int64_t exps_tvar_trip_build = 0;   // 0: never built
+    int64_t exps_tvar_builds = 0;
     // ... and carried into the transposed cell order for the forward tangent (include/cpm_expected_sparse_tangent.h): beside d_exps_o /
     // d_exps_p, built by the first tangent call with a non-zero c_dest, stale wherever sdp_gen moves or ensure_exps rebuilds
     DevBuf<double> d_exps_dp;           // [exps_cells]
@@ -4080,6 +4087,8 @@ int32_t cpm_expected_var(cpm_ctx *c, const double *start, uint32_t flags, double
 
 // ------------------------------------------------------------------ the variance of linear functionals (include/cpm_expected_linear_var.h)
 
+static int32_t exps_rows_ready(const cpm_ctx *c, const char *what);  // (below, with the sparse entries)
+
 namespace {
 
 int32_t elv_reserve(DevBuf<double> &b, size_t words, const char *what)
@@ -4100,20 +4109,36 @@ void launch_elv_u(cpm_ctx *c, int NB, const double *p_t, const double *st, int Z
     cpm::launch(k, grid, block, 0, c->stream, p_t, st, Z, Zs, seg_len, nf, part);
 }
 
+// ... from the compact rows of the hour whose first row is `row` (k_exps_elv_u<NB>; ensure_exps has run)
+void launch_exps_elv_u(cpm_ctx *c, int NB, size_t row, const double *st, int Zs, int nseg, int seg_len, int nf, double *part)
+{
+    const int Z = static_cast<int>(c->Z);
+    const auto k = NB == 4 ? cpm::k_exps_elv_u<4> : NB == 2 ? cpm::k_exps_elv_u<2> : cpm::k_exps_elv_u<1>;
+    cpm::launch(k, dim3(static_cast<unsigned>(Z)), dim3(cpm::kExpsGradBlock), 0, c->stream, static_cast<const double *>(c->d_sp + row * cpm::kDsCap),
+                static_cast<const uint32_t *>(c->d_sj + row * cpm::kDsCap), static_cast<const uint32_t *>(c->d_scnt + row), cpm::kDsCap, st, Z, Zs, seg_len, nseg,
+                nf, part);
+}
+
 // The backward pass for K functionals, operator-major with the passes of at most kElvNB functionals inside an operator (the hour's
 // block of p is read once per pass), then the weighted totals: enqueued on the context's stream.  coeff: [K][2][T][Z]; out: [K][2];
 // zone: [K][2][Z] or nullptr.
 // d_elv_ws, in vectors of Zs words: the state ping and pong, [K4][2] each (K4 = K rounded up to whole passes; a pass's state is
 // [Zs][2][NB] at its first functional's place), the segments' sums [nseg][3][kElvNB], and [K][2][Z] words where zone is nullptr.
-int32_t expected_linear_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t flags, int K, const double *coeff, double *out, double *zone)
+// sparse: the products read the compact rows (k_exps_elv_u, passes of kExpsElvNB) and the per-table arrays of ensure_exps; d_p is
+// neither read nor built.
+int32_t expected_linear_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t flags, int K, const double *coeff, double *out, double *zone,
+                                    bool sparse = false)
 {
     int32_t rc = exp_tables_ready(c, "expected_linear_var");
     if (rc != CPM_OK) return rc;
-    if ((rc = ensure_exp_aux(c)) != CPM_OK) return rc;  // (expands sparse tables to the dense array; the row-total check)
+    if ((rc = sparse ? ensure_exps(c) : ensure_exp_aux(c)) != CPM_OK) return rc;  // (dense: expands sparse tables to the dense array; the row-total check)
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;
     const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
-    const size_t nk = static_cast<size_t>(K), k4 = (nk + cpm::kElvNB - 1) / cpm::kElvNB * cpm::kElvNB;
+    const int pass = sparse ? cpm::kExpsElvNB : cpm::kElvNB;
+    const int *const ell = sparse ? c->d_exps_ell.get() : c->d_exp_ell.get();
+    const double *const res = sparse ? c->d_exps_r.get() : c->d_exp_r.get();
+    const size_t nk = static_cast<size_t>(K), k4 = (nk + pass - 1) / pass * pass;
     const size_t state_words = k4 * 2 * Zs, part_words = static_cast<size_t>(nseg) * 3 * cpm::kElvNB * Zs, zone_words = nk * 2 * Z;
     if ((rc = elv_reserve(c->d_elv_ws, 2 * state_words + part_words + zone_words, "the workspace")) != CPM_OK) return rc;
     double *const ws_st[2] = {c->d_elv_ws, c->d_elv_ws + state_words};
@@ -4124,19 +4149,20 @@ int32_t expected_linear_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t 
     for (int s = steps - 1; s >= 0; --s) {
         const int t = s < pre ? s : s - pre, j = s - pre;
         const size_t row = static_cast<size_t>(t) * Z;
-        const double *p_t = c->d_p + row * Z;
+        const double *p_t = sparse ? nullptr : c->d_p + row * Z;
         const bool have = s != steps - 1;  // (false: mu = nu = 0 by construction, no product is formed)
-        for (int f0 = 0; f0 < K; f0 += cpm::kElvNB) {
-            const int nf = std::min(K - f0, cpm::kElvNB);
+        for (int f0 = 0; f0 < K; f0 += pass) {
+            const int nf = std::min(K - f0, pass);
             const int NB = nf > 2 ? 4 : nf > 1 ? 2 : 1;
             const size_t w0 = static_cast<size_t>(f0) * 2 * Zs;
             const double *st = have ? ws_st[(s + 1) & 1] + w0 : nullptr;
-            if (st) launch_elv_u(c, NB, p_t, st, Zs, nseg, seg_len, nf, part);
+            if (st && sparse) launch_exps_elv_u(c, NB, row, st, Zs, nseg, seg_len, nf, part);
+            else if (st) launch_elv_u(c, NB, p_t, st, Zs, nseg, seg_len, nf, part);
             const double *gp = j >= 0 ? coeff + f0 * cot_stride + static_cast<size_t>(j) * Z : nullptr;
             const double *gd = j >= 0 ? gp + zt : nullptr;
             cpm::launch(cpm::k_elv_finish, dim3(nblk(Z, cpm::kFinishBlock), static_cast<unsigned>(NB)), dim3(cpm::kFinishBlock), 0, c->stream,
-                        static_cast<const double *>(part), nseg, Zs, static_cast<const double *>(c->d_last + row), static_cast<const int *>(c->d_exp_ell + row),
-                        static_cast<const double *>(c->d_exp_r + row), static_cast<const double *>(c->d_pdrive) + row, st, NB, gp, gd, cot_stride, Z, nf,
+                        static_cast<const double *>(part), nseg, Zs, static_cast<const double *>(c->d_last + row), ell + row, res + row,
+                        static_cast<const double *>(c->d_pdrive) + row, st, NB, gp, gd, cot_stride, Z, nf,
                         ws_st[s & 1] + w0, s == 0 ? zone + static_cast<size_t>(f0) * 2 * Z : static_cast<double *>(nullptr));
         }
         HIP_TRY(hipGetLastError());
@@ -4156,27 +4182,28 @@ int32_t elv_enter(cpm_ctx *c, uint32_t flags, int32_t K)
     return CPM_OK;
 }
 
-}  // namespace
-
-int32_t cpm_expected_linear_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone)
+int32_t expected_linear_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone, bool sparse)
 {
     int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
     if (!d_coeff) return fail(CPM_ERR_ARG, "expected_linear_var_dev: null d_coeff");
     if (!d_out) return fail(CPM_ERR_ARG, "expected_linear_var_dev: null d_out");
     if ((rc = elv_enter(c, flags, K)) != CPM_OK) return rc;
+    if (sparse && (rc = exps_rows_ready(c, "expected_linear_var")) != CPM_OK) return rc;
     return expected_linear_var_enqueue(c, static_cast<const double *>(d_start), flags, K, static_cast<const double *>(d_coeff), static_cast<double *>(d_out),
-                                       static_cast<double *>(d_zone));
+                                       static_cast<double *>(d_zone), sparse);
 }
 
-int32_t cpm_expected_linear_var(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving, double *mean,
-                                double *var, double *zone_mean, double *zone_var)
+// the blocking call: the checks of the host arrays, the copies in, the pass and the copies out (dense and sparse entries share it)
+int32_t expected_linear_var_blocking(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving,
+                                     double *mean, double *var, double *zone_mean, double *zone_var, bool sparse)
 {
     int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
     if (!a_parking || !b_driving) return fail(CPM_ERR_ARG, "expected_linear_var: null coefficients");
     if (!mean || !var) return fail(CPM_ERR_ARG, "expected_linear_var: null mean or var");
     if ((rc = elv_enter(c, flags, K)) != CPM_OK) return rc;
+    if (sparse && (rc = exps_rows_ready(c, "expected_linear_var")) != CPM_OK) return rc;  // (state is refused before a coefficient is read or copied)
     const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nk = static_cast<size_t>(K);
     if (start)
         for (size_t z = 0; z < Z; ++z)
@@ -4193,7 +4220,7 @@ int32_t cpm_expected_linear_var(cpm_ctx *c, const double *start, uint32_t flags,
         HIP_TRY(hipMemcpyAsync(d_coeff + k * 2 * zt + zt, b_driving + k * zt, sizeof(double) * zt, hipMemcpyHostToDevice, c->stream));
     }
     if (start) HIP_TRY(hipMemcpyAsync(d_w, start, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
-    if ((rc = expected_linear_var_enqueue(c, start ? d_w : nullptr, flags, K, d_coeff, d_out, d_zone)) != CPM_OK) return rc;
+    if ((rc = expected_linear_var_enqueue(c, start ? d_w : nullptr, flags, K, d_coeff, d_out, d_zone, sparse)) != CPM_OK) return rc;
     std::vector<double> h_out(nk * 2);
     HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, sizeof(double) * nk * 2, hipMemcpyDeviceToHost, c->stream));
     for (size_t k = 0; k < nk; ++k) {
@@ -4203,6 +4230,19 @@ int32_t cpm_expected_linear_var(cpm_ctx *c, const double *start, uint32_t flags,
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < nk; ++k) mean[k] = h_out[2 * k], var[k] = h_out[2 * k + 1];
     return CPM_OK;
+}
+
+}  // namespace
+
+int32_t cpm_expected_linear_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone)
+{
+    return expected_linear_var_dev(c, d_start, flags, K, d_coeff, d_out, d_zone, false);
+}
+
+int32_t cpm_expected_linear_var(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving, double *mean,
+                                double *var, double *zone_mean, double *zone_var)
+{
+    return expected_linear_var_blocking(c, start, flags, K, a_parking, b_driving, mean, var, zone_mean, zone_var, false);
 }
 
 // ------------------------------------------------------------------ the variance of travel functionals (include/cpm_expected_travel_var.h)
@@ -4218,8 +4258,32 @@ int32_t etv_reserve(DevBuf<double> &b, size_t words, const char *what)
 
 // The trip variance weights of the installed p_destin tables and datamatrix in d_exp_vsec: once per build of the trip weights
 // (ensure_exp_trip reports a missing table, datamatrix or distance matrix and rebuilds under every condition these share).
-int32_t ensure_exp_trip_var(cpm_ctx *c)
+// sparse: the weights of the compact rows in d_exps_vsec, once per build of the sparse trip weights (ensure_exps_trip): d_p is neither
+// read nor built, and neither d_exp_vsec nor exp_tvar_builds moves.
+int32_t ensure_exp_trip_var(cpm_ctx *c, bool sparse = false)
 {
+    if (sparse) {
+        int32_t rc = ensure_exps_trip(c);
+        if (rc != CPM_OK) return rc;
+        if (c->exps_tvar_trip_build == c->exps_trip_builds) return CPM_OK;
+        const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
+        const size_t zt = static_cast<size_t>(Z) * T, plane = zt * Z;
+        const int nseg = cpm::trip_segments(Z, T), seg_len = cpm::trip_segment_len(Z, nseg);
+        if ((rc = etv_reserve(c->d_exps_vsec, zt, "the trip variance weights")) != CPM_OK) return rc;
+        HIP_TRY(c->d_exp_wpart.reserve(2 * zt * nseg));  // (scratch of every build of trip weights: nothing reads it afterwards)
+        const double *mean = c->d_dm.get(), *sdev = mean + plane;
+        cpm::launch(cpm::k_exps_trip_var, dim3(static_cast<unsigned>(Z), static_cast<unsigned>(T)), dim3(cpm::kExpsGradBlock), 0, c->stream,
+                    static_cast<const double *>(c->d_sp.get()), static_cast<const uint32_t *>(c->d_sj.get()), static_cast<const uint32_t *>(c->d_scnt.get()),
+                    cpm::kDsCap, mean, sdev, Z, T, seg_len, nseg, c->d_exp_wpart.get());
+        HIP_TRY(hipGetLastError());
+        cpm::launch(cpm::k_exp_trip_var_finish, dim3(nblk(Z, cpm::kExpBlock), static_cast<unsigned>(T)), dim3(cpm::kExpBlock), 0, c->stream,
+                    static_cast<const double *>(c->d_exp_wpart.get()), nseg, mean, sdev, static_cast<const double *>(c->d_last),
+                    static_cast<const int *>(c->d_exps_ell.get()), static_cast<const double *>(c->d_exps_r.get()), Z, T, c->d_exps_vsec.get());
+        HIP_TRY(hipGetLastError());
+        c->exps_tvar_trip_build = c->exps_trip_builds;
+        ++c->exps_tvar_builds;
+        return CPM_OK;
+    }
     int32_t rc = ensure_exp_trip(c);
     if (rc != CPM_OK) return rc;
     if ((rc = ensure_dense_p(c)) != CPM_OK) return rc;  // (the callers read d_p)
@@ -4255,18 +4319,35 @@ void launch_etv_u(cpm_ctx *c, int NB, const double *p_t, const double *m_t, cons
     cpm::launch(k, grid, block, 0, c->stream, p_t, m_t, static_cast<const double *>(c->d_dist.get()), st, cs, cd, cot_stride, Z, Zs, seg_len, nf, part);
 }
 
+// ... from the compact rows of the hour whose first row is `row` (k_exps_etv_u<NB>; ensure_exps has run)
+void launch_exps_etv_u(cpm_ctx *c, int NB, size_t row, const double *m_t, const double *st, const double *cs, const double *cd, size_t cot_stride, int Zs,
+                       int nseg, int seg_len, int nf, double *part)
+{
+    const int Z = static_cast<int>(c->Z);
+    const auto k = NB == 2 ? cpm::k_exps_etv_u<2> : cpm::k_exps_etv_u<1>;
+    cpm::launch(k, dim3(static_cast<unsigned>(Z)), dim3(cpm::kExpsGradBlock), 0, c->stream, static_cast<const double *>(c->d_sp + row * cpm::kDsCap),
+                static_cast<const uint32_t *>(c->d_sj + row * cpm::kDsCap), static_cast<const uint32_t *>(c->d_scnt + row), cpm::kDsCap, m_t,
+                static_cast<const double *>(c->d_dist.get()), st, cs, cd, cot_stride, Z, Zs, seg_len, nseg, nf, part);
+}
+
 // The backward pass for K functionals, operator-major with the passes of at most kEtvNB functionals inside an operator, then the
 // weighted totals: enqueued on the context's stream.  coeff: [K][4][T][Z] (A, B, S, D); out: [K][2]; zone: [K][2][Z] or nullptr.
 // d_etv_ws, in vectors of Zs words: the state ping and pong, [K2][2] each (K2 = K rounded up to whole passes; a pass's state is
 // [Zs][2][NB] at its first functional's place), the segments' sums [nseg][3][kEtvNB], and [K][2][Z] words where zone is nullptr.
 // The state behind the last operator is zeroed and its product is formed like every other: zeta = e there.
-int32_t expected_travel_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t flags, int K, const double *coeff, double *out, double *zone)
+// sparse: the products read the compact rows (k_exps_etv_u), the per-table arrays of ensure_exps and the weights of d_exps_vsec; d_p is
+// neither read nor built.
+int32_t expected_travel_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t flags, int K, const double *coeff, double *out, double *zone,
+                                    bool sparse = false)
 {
-    int32_t rc = ensure_exp_trip_var(c);  // (the tables, the datamatrix and the distances; expands sparse tables to the dense array)
+    int32_t rc = ensure_exp_trip_var(c, sparse);  // (the tables, the datamatrix and the distances; dense: expands sparse tables to the dense array)
     if (rc != CPM_OK) return rc;
     const int Z = static_cast<int>(c->Z), T = static_cast<int>(c->T);
     const int Zs = (Z + 1) & ~1;
     const int nseg = cpm::grad_segments(Z), seg_len = cpm::grad_segment_len(Z, nseg);
+    const int *const ell = sparse ? c->d_exps_ell.get() : c->d_exp_ell.get();
+    const double *const res = sparse ? c->d_exps_r.get() : c->d_exp_r.get();
+    const double *const vsec = sparse ? c->d_exps_vsec.get() : c->d_exp_vsec.get();
     const size_t nk = static_cast<size_t>(K), k2 = (nk + cpm::kEtvNB - 1) / cpm::kEtvNB * cpm::kEtvNB;
     const size_t state_words = k2 * 2 * Zs, part_words = static_cast<size_t>(nseg) * 3 * cpm::kEtvNB * Zs, zone_words = nk * 2 * Z;
     if ((rc = etv_reserve(c->d_etv_ws, 2 * state_words + part_words + zone_words, "the workspace")) != CPM_OK) return rc;
@@ -4279,7 +4360,7 @@ int32_t expected_travel_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t 
     for (int s = steps - 1; s >= 0; --s) {
         const int t = s < pre ? s : s - pre, j = s - pre;
         const size_t row = static_cast<size_t>(t) * Z;
-        const double *p_t = c->d_p + row * Z, *m_t = c->d_dm + row * Z;
+        const double *p_t = sparse ? nullptr : c->d_p + row * Z, *m_t = c->d_dm + row * Z;
         for (int f0 = 0; f0 < K; f0 += cpm::kEtvNB) {
             const int nf = std::min(K - f0, cpm::kEtvNB);
             const int NB = nf > 1 ? 2 : 1;
@@ -4287,12 +4368,12 @@ int32_t expected_travel_var_enqueue(cpm_ctx *c, const double *d_start, uint32_t 
             const double *st = ws_st[(s + 1) & 1] + w0;
             const double *gp = j >= 0 ? coeff + f0 * cot_stride + static_cast<size_t>(j) * Z : nullptr;
             const double *gd = j >= 0 ? gp + zt : nullptr, *cs = j >= 0 ? gp + 2 * zt : nullptr, *cd = j >= 0 ? gp + 3 * zt : nullptr;
-            launch_etv_u(c, NB, p_t, m_t, st, cs, cd, cot_stride, Zs, nseg, seg_len, nf, part);
+            if (sparse) launch_exps_etv_u(c, NB, row, m_t, st, cs, cd, cot_stride, Zs, nseg, seg_len, nf, part);
+            else launch_etv_u(c, NB, p_t, m_t, st, cs, cd, cot_stride, Zs, nseg, seg_len, nf, part);
             cpm::launch(cpm::k_etv_finish, dim3(nblk(Z, cpm::kFinishBlock), static_cast<unsigned>(NB)), dim3(cpm::kFinishBlock), 0, c->stream,
-                        static_cast<const double *>(part), nseg, Zs, static_cast<const double *>(c->d_last + row), static_cast<const int *>(c->d_exp_ell + row),
-                        static_cast<const double *>(c->d_exp_r + row), static_cast<const double *>(c->d_pdrive) + row, m_t,
-                        static_cast<const double *>(c->d_dist.get()), static_cast<const double *>(c->d_exp_vsec + row), st, NB, gp, gd, cs, cd, cot_stride, Z,
-                        nf, ws_st[s & 1] + w0, s == 0 ? zone + static_cast<size_t>(f0) * 2 * Z : static_cast<double *>(nullptr));
+                        static_cast<const double *>(part), nseg, Zs, static_cast<const double *>(c->d_last + row), ell + row, res + row,
+                        static_cast<const double *>(c->d_pdrive) + row, m_t, static_cast<const double *>(c->d_dist.get()), vsec + row, st, NB, gp, gd, cs, cd,
+                        cot_stride, Z, nf, ws_st[s & 1] + w0, s == 0 ? zone + static_cast<size_t>(f0) * 2 * Z : static_cast<double *>(nullptr));
         }
         HIP_TRY(hipGetLastError());
     }
@@ -4311,57 +4392,44 @@ int32_t etv_enter(cpm_ctx *c, uint32_t flags, int32_t K)
     return CPM_OK;
 }
 
-}  // namespace
-
-int32_t cpm_expected_trip_var_dev(cpm_ctx *c, void *d_v)
+// v_sec to a device (to_host false) or a host array; sparse: the weights of the compact rows
+int32_t expected_trip_var_copy(cpm_ctx *c, void *v, bool to_host, bool sparse)
 {
     int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
-    if (!d_v) return fail(CPM_ERR_ARG, "expected_trip_var_dev: null d_v");
+    if (!v) return to_host ? fail(CPM_ERR_ARG, "expected_trip_var: null v_sec") : fail(CPM_ERR_ARG, "expected_trip_var_dev: null d_v");
     CTX_TRY(c);
-    if ((rc = ensure_exp_trip_var(c)) != CPM_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(d_v, c->d_exp_vsec, sizeof(double) * c->Z * c->T, hipMemcpyDeviceToDevice, c->stream));
+    if (sparse && (rc = exps_rows_ready(c, "expected travel")) != CPM_OK) return rc;
+    if ((rc = ensure_exp_trip_var(c, sparse)) != CPM_OK) return rc;
+    const double *const src = sparse ? c->d_exps_vsec.get() : c->d_exp_vsec.get();
+    HIP_TRY(hipMemcpyAsync(v, src, sizeof(double) * c->Z * c->T, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (to_host) HIP_TRY(hipStreamSynchronize(c->stream));
     return CPM_OK;
 }
 
-int32_t cpm_expected_trip_var(cpm_ctx *c, double *v_sec)
-{
-    int32_t rc = exp_enter(c);
-    if (rc != CPM_OK) return rc;
-    if (!v_sec) return fail(CPM_ERR_ARG, "expected_trip_var: null v_sec");
-    CTX_TRY(c);
-    if ((rc = ensure_exp_trip_var(c)) != CPM_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(v_sec, c->d_exp_vsec, sizeof(double) * c->Z * c->T, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return CPM_OK;
-}
-
-int64_t cpm_expected_trip_var_builds(const cpm_ctx *c)
-{
-    const int32_t rc = exp_enter(c);
-    if (rc != CPM_OK) return rc;
-    return c->exp_tvar_builds;
-}
-
-int32_t cpm_expected_travel_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone)
+int32_t expected_travel_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone, bool sparse)
 {
     int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
     if (!d_coeff) return fail(CPM_ERR_ARG, "expected_travel_var_dev: null d_coeff");
     if (!d_out) return fail(CPM_ERR_ARG, "expected_travel_var_dev: null d_out");
     if ((rc = etv_enter(c, flags, K)) != CPM_OK) return rc;
+    if (sparse && (rc = exps_rows_ready(c, "expected travel")) != CPM_OK) return rc;
     return expected_travel_var_enqueue(c, static_cast<const double *>(d_start), flags, K, static_cast<const double *>(d_coeff), static_cast<double *>(d_out),
-                                       static_cast<double *>(d_zone));
+                                       static_cast<double *>(d_zone), sparse);
 }
 
-int32_t cpm_expected_travel_var(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving,
-                                const double *s_seconds, const double *d_km, double *mean, double *var, double *zone_mean, double *zone_var)
+// the blocking call: the checks of the host arrays, the copies in, the pass and the copies out (dense and sparse entries share it)
+int32_t expected_travel_var_blocking(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving,
+                                     const double *s_seconds, const double *d_km, double *mean, double *var, double *zone_mean, double *zone_var,
+                                     bool sparse)
 {
     int32_t rc = exp_enter(c);
     if (rc != CPM_OK) return rc;
     if (!a_parking || !b_driving) return fail(CPM_ERR_ARG, "expected_travel_var: null coefficients");
     if (!mean || !var) return fail(CPM_ERR_ARG, "expected_travel_var: null mean or var");
     if ((rc = etv_enter(c, flags, K)) != CPM_OK) return rc;
+    if (sparse && (rc = exps_rows_ready(c, "expected travel")) != CPM_OK) return rc;  // (state is refused before a coefficient is read or copied)
     const size_t Z = static_cast<size_t>(c->Z), zt = Z * static_cast<size_t>(c->T), nk = static_cast<size_t>(K);
     if (start)
         for (size_t z = 0; z < Z; ++z)
@@ -4382,7 +4450,7 @@ int32_t cpm_expected_travel_var(cpm_ctx *c, const double *start, uint32_t flags,
             else HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * zt, c->stream));  // (a NULL trip array: zeros)
         }
     if (start) HIP_TRY(hipMemcpyAsync(d_w, start, sizeof(double) * Z, hipMemcpyHostToDevice, c->stream));
-    if ((rc = expected_travel_var_enqueue(c, start ? d_w : nullptr, flags, K, d_coeff, d_out, d_zone)) != CPM_OK) return rc;
+    if ((rc = expected_travel_var_enqueue(c, start ? d_w : nullptr, flags, K, d_coeff, d_out, d_zone, sparse)) != CPM_OK) return rc;
     std::vector<double> h_out(nk * 2);
     HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, sizeof(double) * nk * 2, hipMemcpyDeviceToHost, c->stream));
     for (size_t k = 0; k < nk; ++k) {
@@ -4392,6 +4460,78 @@ int32_t cpm_expected_travel_var(cpm_ctx *c, const double *start, uint32_t flags,
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < nk; ++k) mean[k] = h_out[2 * k], var[k] = h_out[2 * k + 1];
     return CPM_OK;
+}
+
+}  // namespace
+
+int32_t cpm_expected_trip_var_dev(cpm_ctx *c, void *d_v)
+{
+    return expected_trip_var_copy(c, d_v, false, false);
+}
+
+int32_t cpm_expected_trip_var(cpm_ctx *c, double *v_sec)
+{
+    return expected_trip_var_copy(c, v_sec, true, false);
+}
+
+int64_t cpm_expected_trip_var_builds(const cpm_ctx *c)
+{
+    const int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    return c->exp_tvar_builds;
+}
+
+int32_t cpm_expected_travel_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone)
+{
+    return expected_travel_var_dev(c, d_start, flags, K, d_coeff, d_out, d_zone, false);
+}
+
+int32_t cpm_expected_travel_var(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving,
+                                const double *s_seconds, const double *d_km, double *mean, double *var, double *zone_mean, double *zone_var)
+{
+    return expected_travel_var_blocking(c, start, flags, K, a_parking, b_driving, s_seconds, d_km, mean, var, zone_mean, zone_var, false);
+}
+
+// ------------------------------------------------------------------ the same variances from the compact rows (include/cpm_expected_sparse_var.h):
+// the namesakes' bodies with sparse = true, and CPM_ERR_STATE without compact rows in front of anything that is read, copied or enqueued
+
+int32_t cpm_expected_sparse_linear_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone)
+{
+    return expected_linear_var_dev(c, d_start, flags, K, d_coeff, d_out, d_zone, true);
+}
+
+int32_t cpm_expected_sparse_linear_var(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving,
+                                       double *mean, double *var, double *zone_mean, double *zone_var)
+{
+    return expected_linear_var_blocking(c, start, flags, K, a_parking, b_driving, mean, var, zone_mean, zone_var, true);
+}
+
+int32_t cpm_expected_sparse_trip_var_dev(cpm_ctx *c, void *d_v)
+{
+    return expected_trip_var_copy(c, d_v, false, true);
+}
+
+int32_t cpm_expected_sparse_trip_var(cpm_ctx *c, double *v_sec)
+{
+    return expected_trip_var_copy(c, v_sec, true, true);
+}
+
+int64_t cpm_expected_sparse_trip_var_builds(const cpm_ctx *c)
+{
+    const int32_t rc = exp_enter(c);
+    if (rc != CPM_OK) return rc;
+    return c->exps_tvar_builds;
+}
+
+int32_t cpm_expected_sparse_travel_var_dev(cpm_ctx *c, const void *d_start, uint32_t flags, int32_t K, const void *d_coeff, void *d_out, void *d_zone)
+{
+    return expected_travel_var_dev(c, d_start, flags, K, d_coeff, d_out, d_zone, true);
+}
+
+int32_t cpm_expected_sparse_travel_var(cpm_ctx *c, const double *start, uint32_t flags, int32_t K, const double *a_parking, const double *b_driving,
+                                       const double *s_seconds, const double *d_km, double *mean, double *var, double *zone_mean, double *zone_var)
+{
+    return expected_travel_var_blocking(c, start, flags, K, a_parking, b_driving, s_seconds, d_km, mean, var, zone_mean, zone_var, true);
 }
 
 // ------------------------------------------------------------------ the same from sparse tables (include/cpm_expected_sparse.h)

@@ -108,15 +108,16 @@ def count_zscores(parking, driving, ev):
 
 
 # ------------------------------------------------------------------ the seed noise of the objectives (Sampler.expected_linear_var)
-def activity_noise(sampler, start, ivp=False):
+def activity_noise(sampler, start, ivp=False, sparse=False):
     """Exact mean and variance over the seed of driving_sum[t] = sum over z of resample()'s driving[z, t], for every hour: T
     functionals with B_k = 1 on hour k (Sampler.expected_linear_var).  start: (Z,) cars per start zone, or None (1 per zone).  Returns
-    dict(mean (T,), var (T,)).  T is at most CPM_MAX_BATCH."""
+    dict(mean (T,), var (T,)).  T is at most CPM_MAX_BATCH.  sparse: Sampler.expected_linear_var(sparse=True), the same bits from the
+    compact rows of sparse tables."""
     Z, T = sampler.Z, sampler.T
     b = np.zeros((Z, T, T), order="F")
     for k in range(T):
         b[:, k, k] = 1.0
-    return sampler.expected_linear_var(np.zeros((Z, T, T), order="F"), b, start=start, ivp=ivp)
+    return sampler.expected_linear_var(np.zeros((Z, T, T), order="F"), b, start=start, ivp=ivp, sparse=sparse)
 
 
 def objective_noise_functionals(densities, C, measured_activity=None, measured_parking=None):
@@ -138,30 +139,31 @@ def objective_noise_functionals(densities, C, measured_activity=None, measured_p
     return names, np.asfortranarray(np.stack(a, axis=2)), np.asfortranarray(np.stack(b, axis=2))
 
 
-def objective_noise(sampler, densities, C, start, measured_activity=None, measured_parking=None, ivp=False):
+def objective_noise(sampler, densities, C, start, measured_activity=None, measured_parking=None, ivp=False, sparse=False):
     """The FIRST-ORDER (delta-method) standard deviation over the seed of activity_error and parking_error of ONE resample of C cars:
     the objective is linearised at the expected densities (parking, driving) = densities (Sampler.expected() with pi_0 = start / C),
     its gradient (traffic_activity_error_grad / parking_density_error_grad, per density) over C is a linear functional of the counts,
     and Sampler.expected_linear_var gives that functional's exact variance.  Exact only for an objective that is linear in the
     counts; the errors are quadratic and min-max normalised, so this is the leading term for large C, and it is 0 where the gradient
     vanishes (a perfect fit), where the true spread is of second order.  start: (Z,) cars per start zone (sum C), or None.  Returns
-    dict(activity_error_std, parking_error_std) for the objectives whose measured data is given."""
+    dict(activity_error_std, parking_error_std) for the objectives whose measured data is given.  sparse: as in activity_noise()."""
     names, a, b = objective_noise_functionals(densities, C, measured_activity, measured_parking)
-    r = sampler.expected_linear_var(a, b, start=start, ivp=ivp)
+    r = sampler.expected_linear_var(a, b, start=start, ivp=ivp, sparse=sparse)
     return {name + "_std": float(np.sqrt(r["var"][k])) for k, name in enumerate(names)}
 
 
-def travel_noise(sampler, start, ivp=False):
+def travel_noise(sampler, start, ivp=False, sparse=False):
     """Exact mean and standard deviation over the seed of the travel of ONE resample(travel=True): the total seconds, the total
     kilometres and A_drive = total seconds / (C * T * 3600), the formula of a_drive(), with C = sum(start)
     (Sampler.expected_travel_var with S = 1, and with D = 1).  start: (Z,) cars per start zone.  Returns dict(seconds_mean,
-    seconds_std, km_mean, km_std, A_drive_mean, A_drive_std)."""
+    seconds_std, km_mean, km_std, A_drive_mean, A_drive_std).  sparse: Sampler.expected_travel_var(sparse=True), the same bits from the
+    compact rows of sparse tables under its condition on the cells that are not stored."""
     Z, T = sampler.Z, sampler.T
     zero = np.zeros((Z, T, 2), order="F")
     s, d = np.zeros((Z, T, 2), order="F"), np.zeros((Z, T, 2), order="F")
     s[:, :, 0] = 1.0
     d[:, :, 1] = 1.0
-    r = sampler.expected_travel_var(zero, zero, s, d, start=start, ivp=ivp)
+    r = sampler.expected_travel_var(zero, zero, s, d, start=start, ivp=ivp, sparse=sparse)
     C = float(np.asarray(start, dtype=np.float64).sum())
     std = np.sqrt(r["var"])
     return {"seconds_mean": float(r["mean"][0]), "seconds_std": float(std[0]), "km_mean": float(r["mean"][1]), "km_std": float(std[1]),
@@ -363,6 +365,8 @@ class Evaluator:
     array.  The bits are the default Evaluator's on one condition (include/cpm_expected_sparse_grad.h): every mean of the datamatrix
     and every distance at a cell p_destin does NOT store is finite.  The dense trip weights form 0 * value there, so a NaN mean at
     a cell of zero count makes the default Evaluator's travel product, A_drive and their gradients NaN where the sparse ones are not.
+    expected_noise runs from the compact rows too (include/cpm_expected_sparse_var.h), with travel=True on the further condition that
+    var_sec of every cell that is not stored is finite (that header says which mean and std words are not).
 
     expected_sparse_dest=True (with expected_sparse=True) keeps the tangent of p_destin on the stored cells as well
     (include/cpm_expected_sparse_dest.h): expected_gradient[_batch], expected_fit and refine_expected with dest=True then run from the
@@ -496,15 +500,18 @@ class Evaluator:
         """The seed noise of one point's resample of C cars: installs pt's tables and returns dict(activity: activity_noise()'s mean
         and var of driving_sum[t], and objective_noise()'s first-order activity_error_std / parking_error_std where the measured data
         is given).  The cars start C / Z per zone (init_states' uniform placement; ivp: in front of the IVP), the start of
-        evaluate_expected().  travel: also A_drive: travel_noise()'s dict (exact, no linearisation)."""
+        evaluate_expected().  travel: also A_drive: travel_noise()'s dict (exact, no linearisation).  Under expected_sparse every call
+        here reads the compact rows (include/cpm_expected_sparse_var.h): the same bits, and the dense p_destin array is not built."""
         self._install(pt)
         s = self.sampler
+        sparse = self.expected_sparse
         start = np.full(s.Z, self.C / s.Z)
-        out = {"activity": activity_noise(s, start, ivp=ivp)}
+        out = {"activity": activity_noise(s, start, ivp=ivp, sparse=sparse)}
         if self.measured_activity is not None or self.measured_parking is not None:
-            out.update(objective_noise(s, s.expected(None, ivp=ivp), self.C, start, self.measured_activity, self.measured_parking, ivp=ivp))
+            out.update(objective_noise(s, s.expected(None, ivp=ivp, sparse=sparse), self.C, start, self.measured_activity, self.measured_parking,
+                                       ivp=ivp, sparse=sparse))
         if travel:
-            out["A_drive"] = travel_noise(s, start, ivp=ivp)
+            out["A_drive"] = travel_noise(s, start, ivp=ivp, sparse=sparse)
         return out
 
     def evaluate_expected_batch(self, pts, ivp=True):

@@ -626,13 +626,14 @@ class Sampler:
                                                 C.c_void_p(int(d_out_ptr)) if d_out_ptr else None))
 
     # -- the exact seed variance of linear functionals of the counts (include/cpm_expected_linear_var.h) --
-    def expected_linear_var(self, a_parking, b_driving, start=None, ivp=False, per_zone=False):
+    def expected_linear_var(self, a_parking, b_driving, start=None, ivp=False, per_zone=False, sparse=False):
         """Exact mean and variance over the seed of L = sum(a_parking * parking) + sum(b_driving * driving) of resample()'s (Z, T)
         count arrays, given the cars' start zones, blocking: one backward pass over the p_destin tables, with every covariance between
         zones and between hours in it.  a_parking / b_driving: (Z, T), or (Z, T, K) for K functionals (at most CPM_MAX_BATCH) in one
         call; functional k carries the bits of a call on it alone.  start, ivp: as in expected_var().  Returns dict(mean, var): floats
         for (Z, T) inputs, (K,) arrays otherwise; per_zone: also zone_mean, zone_var ((Z,) or (Z, K)): the mean and the variance one
-        car that starts in each zone contributes -- mean = start @ zone_mean, var = start @ zone_var."""
+        car that starts in each zone contributes -- mean = start @ zone_mean, var = start @ zone_var.  sparse: from the compact rows of
+        sparse tables (include/cpm_expected_sparse_var.h): the same bits, the dense p_destin array neither read nor built."""
         a, b = np.asarray(a_parking, dtype=np.float64), np.asarray(b_driving, dtype=np.float64)
         single = a.ndim == 2
         if a.shape != b.shape or a.ndim not in (2, 3) or a.shape[:2] != (self.Z, self.T) or (a.ndim == 3 and a.shape[2] < 1):
@@ -643,43 +644,48 @@ class Sampler:
         mean, var = np.zeros(K), np.zeros(K)
         zm = np.zeros((self.Z, K), order="F") if per_zone else None
         zv = np.zeros((self.Z, K), order="F") if per_zone else None
-        _lib.check(self._L.cpm_expected_linear_var(self._h, _vp(w), _lib.CPM_EXPECT_IVP if ivp else 0, K, _vp(a), _vp(b), _vp(mean), _vp(var),
-                                                   _vp(zm), _vp(zv)))
+        call = self._L.cpm_expected_sparse_linear_var if sparse else self._L.cpm_expected_linear_var
+        _lib.check(call(self._h, _vp(w), _lib.CPM_EXPECT_IVP if ivp else 0, K, _vp(a), _vp(b), _vp(mean), _vp(var), _vp(zm), _vp(zv)))
         out = {"mean": float(mean[0]), "var": float(var[0])} if single else {"mean": mean, "var": var}
         if per_zone:
             out["zone_mean"], out["zone_var"] = (zm[:, 0], zv[:, 0]) if single else (zm, zv)
         return out
 
-    def expected_linear_var_dev(self, K, d_coeff_ptr, d_out_ptr, d_start_ptr=0, ivp=False, d_zone_ptr=0):
+    def expected_linear_var_dev(self, K, d_coeff_ptr, d_out_ptr, d_start_ptr=0, ivp=False, d_zone_ptr=0, sparse=False):
         """Enqueue on the context's stream: d_coeff_ptr = device address of float64[K][2][T][Z] (A_k then B_k, the layout of
         expected_grad_dev's cotangent); d_out_ptr = device address of float64[K][2] (mean, variance); d_start_ptr = device address of
         float64[Z] or 0 (1 per zone); d_zone_ptr = device address of float64[K][2][Z] (per start zone) or 0.  (The first call after the
-        p_destin tables changed builds its per-table arrays and synchronises once.)"""
+        p_destin tables changed builds its per-table arrays and synchronises once.)  sparse: as in expected_linear_var(); the
+        coefficients must be finite (this call does not check them)."""
         p = lambda v: C.c_void_p(int(v)) if v else None
-        _lib.check(self._L.cpm_expected_linear_var_dev(self._h, p(d_start_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, int(K), p(d_coeff_ptr), p(d_out_ptr),
-                                                       p(d_zone_ptr)))
+        call = self._L.cpm_expected_sparse_linear_var_dev if sparse else self._L.cpm_expected_linear_var_dev
+        _lib.check(call(self._h, p(d_start_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, int(K), p(d_coeff_ptr), p(d_out_ptr), p(d_zone_ptr)))
 
     # -- the exact seed variance of travel seconds, km and count functionals together (include/cpm_expected_travel_var.h) --
-    def expected_trip_var(self):
+    def expected_trip_var(self, sparse=False):
         """v_sec, (Z, T) float64 F-order: the variance of the seconds of ONE trip that starts in zone o in hour t that comes from the
         truncated-normal draw alone, sum over d of p_destin[o, d, t] * var_sec(o, d, t), from the installed p_destin tables and the
-        datamatrix.  Cached in the context until one of them changes (expected_trip_var_builds())."""
+        datamatrix.  Cached in the context until one of them changes (expected_trip_var_builds()).  sparse: from the compact rows of
+        sparse tables (include/cpm_expected_sparse_var.h), in a cache of its own: the same bits where the means, the distances and
+        var_sec of every cell that is not stored are finite."""
         v = np.zeros((self.Z, self.T), dtype=np.float64, order="F")
-        _lib.check(self._L.cpm_expected_trip_var(self._h, _vp(v)))
+        call = self._L.cpm_expected_sparse_trip_var if sparse else self._L.cpm_expected_trip_var
+        _lib.check(call(self._h, _vp(v)))
         return v
 
-    def expected_trip_var_dev(self, d_v_ptr):
-        """Enqueue on the context's stream: d_v_ptr = device address of float64[T][Z], v_sec."""
-        _lib.check(self._L.cpm_expected_trip_var_dev(self._h, C.c_void_p(int(d_v_ptr)) if d_v_ptr else None))
+    def expected_trip_var_dev(self, d_v_ptr, sparse=False):
+        """Enqueue on the context's stream: d_v_ptr = device address of float64[T][Z], v_sec.  sparse: as in expected_trip_var()."""
+        call = self._L.cpm_expected_sparse_trip_var_dev if sparse else self._L.cpm_expected_trip_var_dev
+        _lib.check(call(self._h, C.c_void_p(int(d_v_ptr)) if d_v_ptr else None))
 
-    def expected_trip_var_builds(self):
-        """How often this context has built the trip variance weights."""
-        n = int(self._L.cpm_expected_trip_var_builds(self._h))
+    def expected_trip_var_builds(self, sparse=False):
+        """How often this context has built the trip variance weights.  sparse: those of expected_trip_var(sparse=True), counted apart."""
+        n = int((self._L.cpm_expected_sparse_trip_var_builds if sparse else self._L.cpm_expected_trip_var_builds)(self._h))
         if n < 0:
             _lib.check(n)
         return n
 
-    def expected_travel_var(self, a_parking, b_driving, s_seconds=None, d_km=None, start=None, ivp=False, per_zone=False):
+    def expected_travel_var(self, a_parking, b_driving, s_seconds=None, d_km=None, start=None, ivp=False, per_zone=False, sparse=False):
         """Exact mean and variance over the seed of
         L = sum(a_parking * parking) + sum(b_driving * driving) + sum over the trips of (s_seconds[o, t] * seconds + d_km[o, t] * km)
         of resample(travel=True), the trips counted at their origin o and hour t, given the cars' start zones, blocking: one backward
@@ -687,7 +693,8 @@ class Sampler:
         travel-time draw and their covariance with where the car is afterwards are all in it.  s_seconds = 1 alone is the run's
         travel-time sum (sum_tt_q16 / 65536).  Coefficients: (Z, T), or (Z, T, K) for K functionals (at most CPM_MAX_BATCH);
         s_seconds / d_km None: zeros, and then every word is expected_linear_var()'s.  start, ivp, per_zone and the result: as in
-        expected_linear_var()."""
+        expected_linear_var().  sparse: from the compact rows of sparse tables (include/cpm_expected_sparse_var.h): the same bits under
+        expected_trip_var(sparse=True)'s condition, the dense p_destin array neither read nor built."""
         a, b = np.asarray(a_parking, dtype=np.float64), np.asarray(b_driving, dtype=np.float64)
         sd = [None if x is None else np.asarray(x, dtype=np.float64) for x in (s_seconds, d_km)]
         single = a.ndim == 2
@@ -702,20 +709,22 @@ class Sampler:
         mean, var = np.zeros(K), np.zeros(K)
         zm = np.zeros((self.Z, K), order="F") if per_zone else None
         zv = np.zeros((self.Z, K), order="F") if per_zone else None
-        _lib.check(self._L.cpm_expected_travel_var(self._h, _vp(w), _lib.CPM_EXPECT_IVP if ivp else 0, K, _vp(a), _vp(b), _vp(sd[0]), _vp(sd[1]),
-                                                   _vp(mean), _vp(var), _vp(zm), _vp(zv)))
+        call = self._L.cpm_expected_sparse_travel_var if sparse else self._L.cpm_expected_travel_var
+        _lib.check(call(self._h, _vp(w), _lib.CPM_EXPECT_IVP if ivp else 0, K, _vp(a), _vp(b), _vp(sd[0]), _vp(sd[1]), _vp(mean), _vp(var), _vp(zm),
+                        _vp(zv)))
         out = {"mean": float(mean[0]), "var": float(var[0])} if single else {"mean": mean, "var": var}
         if per_zone:
             out["zone_mean"], out["zone_var"] = (zm[:, 0], zv[:, 0]) if single else (zm, zv)
         return out
 
-    def expected_travel_var_dev(self, K, d_coeff_ptr, d_out_ptr, d_start_ptr=0, ivp=False, d_zone_ptr=0):
+    def expected_travel_var_dev(self, K, d_coeff_ptr, d_out_ptr, d_start_ptr=0, ivp=False, d_zone_ptr=0, sparse=False):
         """Enqueue on the context's stream: d_coeff_ptr = device address of float64[K][4][T][Z] (A_k, B_k, S_k, D_k); d_out_ptr =
         device address of float64[K][2] (mean, variance); d_start_ptr = device address of float64[Z] or 0 (1 per zone); d_zone_ptr =
-        device address of float64[K][2][Z] (per start zone) or 0."""
+        device address of float64[K][2][Z] (per start zone) or 0.  sparse: as in expected_travel_var(); the coefficients must be
+        finite (this call does not check them)."""
         p = lambda v: C.c_void_p(int(v)) if v else None
-        _lib.check(self._L.cpm_expected_travel_var_dev(self._h, p(d_start_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, int(K), p(d_coeff_ptr), p(d_out_ptr),
-                                                       p(d_zone_ptr)))
+        call = self._L.cpm_expected_sparse_travel_var_dev if sparse else self._L.cpm_expected_travel_var_dev
+        _lib.check(call(self._h, p(d_start_ptr), _lib.CPM_EXPECT_IVP if ivp else 0, int(K), p(d_coeff_ptr), p(d_out_ptr), p(d_zone_ptr)))
 
     def expected_batch_dev(self, d_out_ptr, d_pi0_ptr=0, ivp=False, sparse=False):
         """Enqueue on the context's stream: d_out_ptr = device address of float64[B][expected_words()] for the installed batch tables.

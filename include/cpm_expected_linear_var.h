@@ -76,7 +76,8 @@
  * The calls need no cars, run no forward propagation, keep no Z x Z workspace and change no state of the context that a later call
  * reads.  They keep the state vectors of the passes and the segments' partial sums in a workspace of the context.  The first call
  * after the p_destin tables changed builds l and r and reads the row-total check back: it synchronises the stream once
- * (cpm_expected.h).  Tables with sparse row packs are expanded to the dense array first, as cpm_expected_var does.
+ * (cpm_expected.h).  Tables with sparse row packs are expanded to the dense array first, as cpm_expected_var does; the same words
+ * straight from the compact rows, without that array: cpm_expected_sparse_var.h.
  *
  * Status codes are those of cpm_expected_var: CPM_ERR_STATE without p_drive or p_destin tables, CPM_ERR_TABLE for a row total above
  * 1 (cpm_last_error() names the hour and the origin), CPM_ERR_HIP without a usable device, CPM_ERR_NOMEM for a failed allocation;

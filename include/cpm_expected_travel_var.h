@@ -92,8 +92,8 @@
  * The exact value is that of the recurrence with the exact v(a) of every cell's f64 word a.  A word whose magnitude is 0 is 0.
  *
  * The calls need no cars, run no forward propagation, keep no Z x Z workspace and change no state of the context that a later call
- * reads.  Tables with sparse row packs are expanded to the dense array first, as cpm_expected_linear_var does; there is no sparse
- * twin.  The first call after the tables changed synchronises the stream once (cpm_expected.h).
+ * reads.  Tables with sparse row packs are expanded to the dense array first, as cpm_expected_linear_var does; the sparse twins,
+ * which read the compact rows instead, are in cpm_expected_sparse_var.h.  The first call after the tables changed synchronises the stream once (cpm_expected.h).
  *
  * Status codes are those of cpm_expected_linear_var (CPM_ERR_STATE without p_drive or p_destin tables, CPM_ERR_TABLE, CPM_ERR_HIP,
  * CPM_ERR_NOMEM, CPM_ERR_ARG for a NULL coefficient or output array, unknown flag bits, K outside 1 .. CPM_MAX_BATCH and, in the
